@@ -3,11 +3,20 @@
 synthetic "shell" 1024^3 u8 volume (1 GiB, resident in HBM) rendered at 2048 x 2048, one frame per step, cycling
 through the reference's 8 benchmark views (2 projections x 4 poses at distance 2, VolR.cpp:225-253).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--simulate-ranks 2,4,8]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full [--simulate-ranks 2,4,8]]
 
 --config selects another BASELINE.json configuration for the timed region (c2 256^3 @ 1024^2, c3 512^3 @ 1920x1080, c4 = the default
-headline, c5 2048^3 uint16 @ 4096^2); at N = 1 the default run also reports c2 / c3 / c5, the linear layout on the headline workload,
-the reference's own host-buffer timed region and the N-rank load-balance model under `extras` / `scale_model`.
+headline, c5 2048^3 uint16 @ 4096^2).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the JSON line (`value`, `ms_per_step`, the
+roofline of the timed launches).  --full adds everything else, after the timed region: the frame check and the one-frame latency, the
+per-view kernel times, the min/max feeder, and at N = 1 c2 / c3 / c5, the linear layout on the headline workload, the reference's own
+host-buffer timed region, the N-rank load-balance model (`extras` / `scale_model`) and the CPU baselines.
+
+--dump-outputs DIR writes the frame the last timed step assembled (what a caller of the timed path receives) as float32 .npy files:
+DIR/frame.npy [H, W, 4] when it is at most 32 MiB as float32, else a fixed sample of 2^20 pixels (seed 0) as DIR/frame_sample.npy
+[2^20, 4] with their row-major pixel indices in DIR/frame_sample_index.npy (float64).  Inputs are seeded: the same arguments give the
+same frame.
 
 With N > 1 and no torch.distributed environment the script starts N ranks of itself (one per GPU) through
 `python -m torch.distributed.run` and relays rank 0's JSON line; launched under torch.distributed.run directly
@@ -21,7 +30,7 @@ algorithmic bytes are view independent (260 B/ray) — in TRILINEAR
 heavier mode).  The reference-pinned NEAREST sampling, the reference's default mode (ESL + ERT) and its ERT-only mode
 (VolR.cpp:288-290) are timed as extras, the latter two with a roofline over the bytes their sample sets touch.
 
-Rank 0 prints ONE JSON line.  With --gpus 1 it also times the reference's own CPURenderer (oracle/_ref, built from the
+Rank 0 prints ONE JSON line.  With --gpus 1 --full it also times the reference's own CPURenderer (oracle/_ref, built from the
 reference sources in the build container) on a bounded sample of the same workload on one host core, and the OpenMP
 leg of the CPU restatement on all host cores.
 
@@ -66,6 +75,9 @@ def parse():
     ap.add_argument("--cpu-band-rows", type=int, default=96, help="rows per view of the 1-core CPU-baseline sample")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo rehearsal of the multi-rank plumbing, nothing is rendered")
     ap.add_argument("--force-launcher", action="store_true", help="start the ranks as child processes even for --gpus 1")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the checks and every other measurement "
+                                                        "(frame check, latency, per-view times, extras, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step as float32 .npy files into DIR")
     return ap.parse_args()
 
 
@@ -268,7 +280,7 @@ def run_rank(a):
         t_setup = time.perf_counter()
         r.generate_volume("shell", n, seed=1, bytes_per_voxel=bpv)
         minmax = r.volume_minmax()[0]
-        minmax_ms = r.volume_minmax()[3]                        # second run: warm clocks
+        minmax_ms = r.volume_minmax()[3] if a.full else None    # second run: warm clocks
         scene = vr.Scene().set_volume(dims=(n, n, n), minmax=minmax)
         set_mode(scene, a.mode)
         r.set_transfer_fn(scene.tf, scene.esl)
@@ -390,17 +402,27 @@ def run_rank(a):
             fence()
         return (time.perf_counter() - t0) / frames
 
+    def dump_last_frame():
+        """The frame the last timed step assembled (slot of step K - 1, retired by the final fence), on rank 0."""
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, final[(a.steps - 1) % slots])
+
+    frame_check, latency = None, 0.0
     if stream_ctx is not None:
         with stream_ctx:
             elapsed = timed_region()
             tm = r.timing()
-            frame_check = check_frame()
-            latency = latency_region()
+            dump_last_frame()
+            if a.full:
+                frame_check = check_frame()
+                latency = latency_region()
     else:
         elapsed = timed_region()
         tm = None
-        frame_check = check_frame()
-        latency = latency_region()
+        dump_last_frame()
+        if a.full:
+            frame_check = check_frame()
+            latency = latency_region()
 
     per_rank_kernel_ms = [tm.kernel_ms_sum / max(1, tm.launches)] if tm is not None else [0.0]
     kernel_ms_max = float(tm.kernel_ms_max) if tm is not None else 0.0       # the longest single launch (Profiler.cpp:69-72 keeps sum and max)
@@ -426,14 +448,16 @@ def run_rank(a):
                       "Mrays/s (W*H / t_frame), 1024^3 volume @ 2048^2 viewport", "value": round(mrays, 2), "unit": "Mrays/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "frame_check": frame_check,
+            "frames_in_flight": slots,
+        }
+        if a.full:
             # north_star asks for "Mrays/s + ms/frame": `value` / `ms_per_step` are THROUGHPUT with `frames_in_flight` frames of a rank in
             # flight (a renderer that feeds an encoder); `ms_per_frame_latency` is ONE frame through the same path with nothing else in
             # flight (an interactive viewer), measured over 16 synchronous frames after the timed region.  At N = 1 both are the kernel.
-            "frames_in_flight": slots, "ms_per_frame_latency": round(latency * 1e3, 4), "Mrays_per_s_latency": round(W * H / latency / 1e6, 2) if latency > 0 else None,
-        }
-        if frame_check != "ok":
-            rc = 4
+            out.update({"frame_check": frame_check, "ms_per_frame_latency": round(latency * 1e3, 4),
+                        "Mrays_per_s_latency": round(W * H / latency / 1e6, 2) if latency > 0 else None})
+            if frame_check != "ok":
+                rc = 4
         if a.dry_run:
             out.update({"dry_run": True, "value": 0.0,
                         "config": {"workload": "DRY RUN: no rendering, row-pattern bands through the real split / gather / launcher code",
@@ -479,10 +503,11 @@ def run_rank(a):
                 "note": "the lit march is bound by vector-instruction issue as much as by memory (valu_busy_per_view 0.5 - 0.9; the column-window views stream 5.7 GB of copy per frame at 4.3 TB/s "
                         "when unlit), the run-brick views also by the gather rate of the L1 (SURVEY §8d 'honest ceiling'); every voxel is still fetched — the "
                         "exact per-wave shortcuts (transparent samples, rays whose accumulated alpha is exactly 1) skip arithmetic only"}
-            out["minmax_feeder"] = {"kernel": "vr::minmax_kernel", "kernel_ms": round(minmax_ms, 4),
-                                    "achieved_GBs": round(n ** 3 / (minmax_ms * 1e-3) / 1e9, 1),
-                                    "frac_of_hbm_peak": round(n ** 3 / (minmax_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-            if world == 1:
+            if a.full:
+                out["minmax_feeder"] = {"kernel": "vr::minmax_kernel", "kernel_ms": round(minmax_ms, 4),
+                                        "achieved_GBs": round(n ** 3 / (minmax_ms * 1e-3) / 1e9, 1),
+                                        "frac_of_hbm_peak": round(n ** 3 / (minmax_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            if world == 1 and a.full:
                 # one launch per benchmark view, outside the timed region: the per-view kernel times behind the mean above
                 per_view = []
                 for v in views:
@@ -504,7 +529,7 @@ def run_rank(a):
                                      "hbm_bytes": int(info.linear_bytes + info.bricked_bytes),
                                      "note": "brick copies are built by the first frame that reads them (vr_hip_prepare builds them ahead of time): "
                                              "what is listed is what this run's views and modes asked for so far"}
-            legs = set() if a.no_extras or world != 1 else set(x for x in a.extras.split(",") if x)
+            legs = set() if not a.full or a.no_extras or world != 1 else set(x for x in a.extras.split(",") if x)
             if legs:
                 out["extras"] = extras(vr, r, scene, views, split, local[0], stream, render_stream, n, W, H, bpv) if "modes" in legs else {}
                 set_mode(scene, a.mode)
@@ -551,7 +576,7 @@ def run_rank(a):
                         out["set_volume"]["builders"] = cbp.probe(vr, r2, n, bpv, reps=2)
                     finally:
                         r2.close()
-            if world == 1 and not a.no_cpu_baseline and bpv == 1:
+            if a.full and world == 1 and not a.no_cpu_baseline and bpv == 1:
                 out["cpu_baseline"] = cpu_baseline(vr, r, scene, views, n, W, H, a.cpu_band_rows)
                 # the comparison north_star asks for, labelled — vs_baseline itself stays null (BASELINE.md has no published number)
                 out["vs_cpu_baseline"] = {"ratio": round(mrays / out["cpu_baseline"]["value"], 1),
@@ -566,6 +591,21 @@ def run_rank(a):
     if r is not None:
         r.close()
     return rc
+
+
+def dump_outputs(directory, frame, sample=1 << 20, whole_max_bytes=32 << 20):
+    """Writes an assembled RGBA8 frame [H, W, 4] as float32: whole when that is at most `whole_max_bytes`, else a fixed sample of
+    `sample` pixels (seed 0, sorted row-major indices, saved beside it in float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    img = frame.cpu().numpy()
+    if img.size * 4 <= whole_max_bytes:
+        np.save(os.path.join(directory, "frame.npy"), img.astype(np.float32))
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=min(sample, flat.shape[0]), replace=False))
+    np.save(os.path.join(directory, "frame_sample.npy"), flat[idx].astype(np.float32))
+    np.save(os.path.join(directory, "frame_sample_index.npy"), idx.astype(np.float64))
 
 
 def set_mode(scene, mode):

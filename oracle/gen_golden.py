@@ -205,10 +205,16 @@ def main():
         assert fnv1a32(fr) == SURVEY_SHELL256["noopt"][i], fnv1a32(fr)
     print("shell 256^3 @ 1024^2 reference hashes equal SURVEY §8(c)")
 
-    np.savez_compressed(os.path.join(OUT, "golden.npz"), **arrays)
+    # inputs in golden.npz, frames split by case id parity (tests/helpers.py GOLDEN_SHARDS): every file stays under 1 MiB
+    frame_of = lambda k: k.startswith("case") and k.endswith("_frame")
+    shards = {"golden.npz": {k: v for k, v in arrays.items() if not frame_of(k)}}
+    for p in (0, 1):
+        shards[f"golden_frames{p}.npz"] = {k: v for k, v in arrays.items() if frame_of(k) and int(k[4:-6]) % 2 == p}
+    for name, part in shards.items():
+        np.savez_compressed(os.path.join(OUT, name), **part)
     with open(os.path.join(OUT, "golden.json"), "w") as f:
         json.dump(index, f, indent=1)
-    print("wrote", len(index["cases"]), "cases;", os.path.getsize(os.path.join(OUT, "golden.npz")) // 1024, "KiB")
+    print("wrote", len(index["cases"]), "cases;", {name: os.path.getsize(os.path.join(OUT, name)) // 1024 for name in shards}, "KiB")
 
 
 if __name__ == "__main__":

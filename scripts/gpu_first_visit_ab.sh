@@ -6,7 +6,7 @@ O=gpurun_out/fv; mkdir -p $O
 timeout -k 10 300 python -m pytest tests/test_gpu_parity.py tests/test_gpu_random.py -m gpu -x -q -k "tile_scheduling or orders_and_recordings or random" > $O/tests.log 2>&1 || { tail -25 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for e in 0 1; do
-  VR_TILE_ESTIMATE=$e timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench_$e.json 2> $O/bench_$e.err || { tail -5 $O/bench_$e.err; exit 1; }
+  VR_TILE_ESTIMATE=$e timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench_$e.json 2> $O/bench_$e.err || { tail -5 $O/bench_$e.err; exit 1; }
   python - $O/bench_$e.json $e <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -20,7 +20,7 @@ rows.sort()
 ms = [(e - s) / 1e6 for s, e, _ in rows]
 timed = ms[setup + warmup: setup + warmup + steps]
 names = [("col" if "colmarch" in n else "ray") + n.split("march_kernel")[1].split(">")[0] + ">" for _, _, n in rows[setup + warmup: setup + warmup + steps]]
-print(json.dumps({"command": f"rocprofv3 --kernel-trace --stats -- python bench.py --steps {steps} --warmup {warmup} --no-cpu-baseline --no-extras",
+print(json.dumps({"command": f"rocprofv3 --kernel-trace --stats -- python bench.py --steps {steps} --warmup {warmup} --full --no-cpu-baseline --no-extras",
                   "raymarch_launches": len(ms), "first_launch_ms": round(ms[0], 3) if ms else None,
                   "timed_steps_ms": [round(x, 4) for x in timed], "timed_instantiations": names,
                   "timed_mean_ms": round(sum(timed) / max(1, len(timed)), 4), "timed_max_ms": round(max(timed), 4) if timed else None,

@@ -40,6 +40,6 @@ json.dump({"nooptims_trilinear_1024_2048_n1": entry,
            "_source": f"profiles/{rnd}_bench_pmc_summary.txt: mean over the 16 TIMED raymarch launches of rocprofv3 --pmc FETCH_SIZE "
                       f"({vals['FETCH_SIZE']:.6g} KB, x2: gfx950 tallies 128-B requests at 64 B, calibrated on minmax_kernel which reads "
                       f"exactly 1 GiB and reports 524312 KB) + WRITE_SIZE ({vals['WRITE_SIZE']:.6g} KB, exact), separate passes",
-           "_command": "python bench.py --steps 16 --warmup 8 --no-cpu-baseline --no-extras"},
+           "_command": "python bench.py --steps 16 --warmup 8 --full --no-cpu-baseline --no-extras"},
           open(os.path.join(dst, f"{rnd}_traffic.json"), "w"), indent=1)
 print(f"traffic {traffic / 1e9:.3f} GB per launch at commit {commit}; TCC hit rate {vals['TCC_HIT_sum'] / (vals['TCC_HIT_sum'] + vals['TCC_MISS_sum']):.2f}")

@@ -107,11 +107,26 @@ class Oracle:
         return tf, esl, bd, bs, self.default_ray_step((x, y, z))
 
 
+# golden.npz holds the inputs, the frames are split by case id over two more files (each stays well under 1 MiB)
+GOLDEN_SHARDS = ("golden.npz", "golden_frames0.npz", "golden_frames1.npz")
+
+
+class _Arrays(dict):
+    """name -> array over every shard, with the `.files` list of an np.load() archive."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 class Golden:
-    """tests/golden/golden.{npz,json}: inputs + frames rendered by the reference's own CPURenderer (oracle/gen_golden.py)."""
+    """tests/golden/golden.json + GOLDEN_SHARDS: inputs + frames rendered by the reference's own CPURenderer (oracle/gen_golden.py)."""
 
     def __init__(self):
-        self.arrays = np.load(os.path.join(GOLDEN_DIR, "golden.npz"), allow_pickle=False)
+        self.arrays = _Arrays()
+        for shard in GOLDEN_SHARDS:
+            with np.load(os.path.join(GOLDEN_DIR, shard), allow_pickle=False) as z:
+                self.arrays.update((k, z[k]) for k in z.files)
         with open(os.path.join(GOLDEN_DIR, "golden.json")) as f:
             self.index = json.load(f)
         self._vox = {}
