@@ -157,6 +157,12 @@ int vr_hip_set_wide_addressing(vr_ctx *ctx, uint32_t force);
  * those views).  Speed only; testing and tuning aid.  No reference counterpart. */
 int vr_hip_set_brick_plane(vr_ctx *ctx, int32_t plane);
 
+/* Which copy the TRILINEAR frames that take the column march read: 0 = the windows of 16 plain voxels (VR_COPY_COLV_*, 1 byte per
+ * voxel) wherever the host can bound the cell columns of every 8x8-pixel wave to 64 (default; the quad-element windows otherwise);
+ * 1 = always the quad-element windows (VR_COPY_COL_*, 16/3 bytes per voxel; the round-4 march).  Speed only; A/B and testing aid.
+ * No reference counterpart. */
+int vr_hip_set_column_copy(vr_ctx *ctx, uint32_t mode);
+
 /* Which pixels of a 4x4-pixel block share a lane quad, and where the tile grid starts: speed only, images are identical.
  * lane_map -1 = chosen per frame from the view (default); else (lane order) + 4 * (wave shape): order 0 = 4 pixels along screen x,
  * 1 = along screen y, 2 = 2x2-pixel blocks; wave shape 0 = 8x8 pixels per wavefront, 1 = 16 wide x 4 high, 2 = 4 wide x 16 high;
@@ -194,7 +200,7 @@ int vr_hip_render_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, v
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {
 	uint32_t layout;        /* 0 linear array, 1 quad bricks, 2 / 3 run bricks along z / y, 4 voxel bricks, 5 oct bricks, 6 both run copies (per tile),
-	                           7 column windows (brick_plane then holds the march axis 0 x, 1 y, 2 z) */
+	                           7 column windows (brick_plane then holds the march axis 0 x, 1 y, 2 z; column_voxels says which copy) */
 	uint32_t brick_plane;   /* chunk plane of a quad copy: 0 (x,y), 1 (x,z), 2 (y,z) */
 	uint32_t lane_map;      /* (lane order) + 4 * (wave shape), as in vr_hip_set_tile_mapping */
 	uint32_t phase_x, phase_y;
@@ -202,6 +208,8 @@ typedef struct vr_launch_info {
 	uint32_t tiles_x, tiles_y;
 	uint32_t ordered;       /* 1: the frame ran in a measured-cost tile order */
 	uint32_t straddle_permille;   /* orthogonal views along an axis: lane groups that still straddle cells under the chosen phase */
+	uint32_t column_voxels; /* layout 7 with TRILINEAR: 1 = the march read the windows of 16 plain voxels (VR_COPY_COLV_*), 0 = the
+	                           quad-element windows (VR_COPY_COL_*); vr_hip_set_column_copy */
 } vr_launch_info;
 int vr_hip_last_launch(vr_ctx *ctx, vr_launch_info *out);
 
@@ -286,7 +294,7 @@ uint32_t vr_hip_multi_default_band_rows(uint32_t height, uint32_t n);
 #define VR_COPY_COL_Y    (1u << 8)   /* elements along the axis in ONE aligned 16-byte word; what TRILINEAR reads for full-march frames of */
 #define VR_COPY_COL_Z    (1u << 9)   /* ORTHOGONAL views along that axis: one gather and one transparency test per ~3 samples (vr_device.h) */
 #define VR_COPY_COLV_X   (1u << 10)  /* the same for NEAREST: 16 consecutive VOXELS of a cell column in one aligned 16-byte word (1 byte per voxel): */
-#define VR_COPY_COLV_Y   (1u << 11)  /* one gather and one transparency test per sixteen samples */
+#define VR_COPY_COLV_Y   (1u << 11)  /* one gather and one transparency test per sixteen samples; TRILINEAR reads them too (vr_hip_set_column_copy) */
 #define VR_COPY_COLV_Z   (1u << 12)
 #define VR_COPY_ALL      0x1fffu
 #define VR_COPY_KINDS    13

@@ -62,7 +62,7 @@ class VrTiming(C.Structure):
 
 class VrLaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("layout", "brick_plane", "lane_map", "phase_x", "phase_y", "clamp_fetch", "tiles_x", "tiles_y",
-                                          "ordered", "straddle_permille")]
+                                          "ordered", "straddle_permille", "column_voxels")]
 
 
 def library_path():
@@ -103,6 +103,7 @@ def lib():
         "vr_hip_set_wide_addressing": (C.c_int, [vp, u32]),
         "vr_hip_set_tile_mapping": (C.c_int, [vp, C.c_int32, u32, u32]),
         "vr_hip_set_brick_plane": (C.c_int, [vp, C.c_int32]),
+        "vr_hip_set_column_copy": (C.c_int, [vp, u32]),
         "vr_hip_set_tile_scheduling": (C.c_int, [vp, u32]),
         "vr_hip_last_launch": (C.c_int, [vp, P(VrLaunchInfo)]),
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),

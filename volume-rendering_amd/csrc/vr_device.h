@@ -177,7 +177,12 @@ struct TileSchedule { const uint32_t *order = nullptr; uint32_t *cost = nullptr;
 //                   block's windows follow each other along m: address = ((bv * nbu + bu) * nw + w) * 256 + (v & 3) * 64 + (u & 3) * 16.
 //                   One 16-byte gather serves the ~3 samples of a window, its transparency test is done once for the window, and the
 //                   address chain of a sample shrinks to the wave-uniform cell along m (colmarch_kernel).  16/3 bytes per voxel.
-enum : uint32_t { kLayoutLinear = 0, kLayoutBricked = 1, kLayoutRun = 2, kLayoutRunY = 3, kLayoutVoxel = 4, kLayoutOct = 5, kLayoutRunDual = 6, kLayoutColumn = 7 };
+//   kLayoutVoxCol : the column-march views and the TRILINEAR arithmetic of kLayoutColumn, read from the NEAREST windows of 16 plain voxels
+//                   (kCopyColVox*, 1 byte per voxel): a wave gathers the rectangle of cell columns its lanes sample, one column per
+//                   lane, and hands every lane its 2x2 corner columns by cross-lane permutes (voxcol_tri_kernel).  Taken where the host
+//                   can bound that rectangle to 64 columns (vr_hip_api.cpp), kLayoutColumn otherwise.
+enum : uint32_t { kLayoutLinear = 0, kLayoutBricked = 1, kLayoutRun = 2, kLayoutRunY = 3, kLayoutVoxel = 4, kLayoutOct = 5, kLayoutRunDual = 6, kLayoutColumn = 7,
+                  kLayoutVoxCol = 8 };
 __host__ __device__ constexpr bool is_run_layout(int layout) { return layout == (int) kLayoutRun || layout == (int) kLayoutRunY || layout == (int) kLayoutRunDual; }
 constexpr uint32_t kDualWords = 32;
 constexpr uint32_t kTileAltBit = 0x80000000u;       // kLayoutRunDual: set in a launch-order entry = this tile reads the copy with runs along y

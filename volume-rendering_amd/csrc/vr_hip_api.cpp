@@ -53,6 +53,7 @@ struct vr_ctx {
 	float copy_build_ms[kCopyKinds] = {};
 	bool copy_failed[kCopyKinds] = {};
 	int32_t column_force = 0;               // vr_hip_set_brick_plane: 0 = per view (views along a volume axis), 1 (plane 8) = every orthogonal full-march frame, -1 (plane 9) = never
+	uint32_t column_copy = 0;               // vr_hip_set_column_copy: 0 = TRILINEAR column frames read the voxel windows where a wave's columns fit, 1 = the quad-element windows
 	float upload_ms = 0;                    // host -> HBM copy (or generation) of the linear array in the last set_volume
 	int32_t brick_plane_force = -1;         // -1 = per view (plane perpendicular to the dominant view axis; run bricks for oblique views),
 	                                        // 0..2 = that chunk plane, 3 = the run bricks (testing)
@@ -534,10 +535,18 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		for (int i = 0; i < 3; i++) if ((std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i] > 1.0f) take = false;
 		if (c->column_force == 0)                                          // per view: along the axis — 4 > 2 sqrt(3), the longest segment in k
 			for (int i = 0; i < 3; i++) if (i != m && d[i] * 4.0f >= 0.45f) take = false;
-		if (take && copy_possible(c, (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + (uint32_t) m)) {
-			a.layout = kLayoutColumn; a.col_axis = (uint32_t) m; a.brick_plane = (uint32_t) m;
+		// TRILINEAR reads the voxel windows (kLayoutVoxCol, voxcol_tri_kernel) where every wave's rectangle of cell columns fits in its 64
+		// lanes: along a lateral axis i the 8x8 pixels of a wave span 7 pixel steps, i.e. at most floor(7 * cells per step) + 2 cells, + 1
+		// for the +1 neighbours of a trilinear sample and + 1 for a column flip.  The quad-element windows (colmarch_kernel) otherwise.
+		const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
+		bool voxcol = false;
+		if (!nearest && c->column_copy == 0 && col_copy_bytes(c->dim, (uint32_t) m, true) < (1ull << 32)) {      // (the kernel's explicit fetches use 32-bit offsets)
+			auto span = [&](int i) { return (int) std::floor(7.0f * (std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i]) + 4; };
+			voxcol = span(m == 0 ? 1 : 0) * span(m == 2 ? 1 : 2) <= 64;
+		}
+		if (take && copy_possible(c, (nearest || voxcol ? kCopyColVoxX : kCopyColX) + (uint32_t) m)) {
+			a.layout = voxcol ? kLayoutVoxCol : kLayoutColumn; a.col_axis = (uint32_t) m; a.brick_plane = (uint32_t) m;
 			// the dense path's constants, grouped for one scalar load each (vr_device.h); the products are the device's own fp32 products
-			const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
 			a.col_sample.ax = p->view.direction[0] * a.half_x; a.col_sample.ay = p->view.direction[1] * a.half_y; a.col_sample.az = p->view.direction[2] * a.half_z;
 			a.col_sample.tf_scale = a.tf_scale; a.col_sample.tf_zero_below = a.tf_zero_below;
 			a.col_sample.max_x = a.max_x; a.col_sample.max_y = a.max_y; a.col_sample.max_z = a.max_z;
@@ -547,7 +556,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			a.col_shade.kd_scaled = a.kd_scaled;
 			for (int i = 0; i < 3; i++) a.col_shade.dim[i] = c->dim[i];
 			a.col_shade.nbu = col_blocks(c->dim[m == 0 ? 1 : 0]);
-			a.col_shade.nw = col_windows(c->dim[m], nearest ? kColVoxCells : kColCells);
+			a.col_shade.nw = col_windows(c->dim[m], nearest || voxcol ? kColVoxCells : kColCells);
 			dual_analytic = false; dual_stage = -1;
 		}
 	}
@@ -561,7 +570,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	}
 	if (a.layout != kLayoutLinear && brick_copy == nullptr) {
 		const uint32_t want = a.layout == kLayoutRun ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
-		                      a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : kCopyQuadXY + a.brick_plane;
+		                      a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane;
 		brick_copy = copy_for(c, want);
 		if (brick_copy == nullptr && want != kCopyQuadXY) {
 			a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
@@ -652,7 +661,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		// No order at all — the first frame under this policy key (a new view: the reference's benchmark renders every view once): predict
 		// the tile costs from the ESL bit volume (tile_estimate_kernel) and order by them, on this stream, in front of the frame
 		static const bool estimate = [] { const char *e = getenv("VR_TILE_ESTIMATE"); return e == nullptr || atoi(e) != 0; }();      // VR_TILE_ESTIMATE=0: A/B
-		if (read_slot == nullptr && estimate && p->esl && a.layout != kLayoutColumn) {
+		if (read_slot == nullptr && estimate && p->esl && a.layout != kLayoutColumn && a.layout != kLayoutVoxCol) {
 			vr_ctx::SchedSlot *est = nullptr;
 			for (auto &sl : oe->slot) {
 				if (sl.last_seq > c->completed_seq) continue;                                          // a frame that may still run reads or records it
@@ -745,18 +754,21 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		c->cost_map_tiles_x = plan.tiles_x; c->cost_map_tiles_y = plan.tiles_y;
 	}
 
-	c->last_launch = vr_launch_info{ a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch, plan.tiles_x, plan.tiles_y,
-	                                 sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u };
+	// (the TRILINEAR column march over the voxel windows reports layout 7, the column march, and column_voxels = 1)
+	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
+	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u,
+	                                 a.layout == kLayoutVoxCol ? 1u : 0u };
 
 #ifdef VR_BOUNDS_CHECK
 	{   // debug build: what the frame's gathers must stay inside, and where the first violation is recorded
 		if (c->bc_fault == nullptr) { VR_TRY(c, hipMalloc((void **) &c->bc_fault, 8 * sizeof(uint32_t))); VR_TRY(c, hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t))); }
 		const void *array = plan.reads_linear ? c->vol : brick_copy;
-		a.bc_base = (uint64_t) (uintptr_t) array - (a.layout == kLayoutColumn ? kColPadBytes : 0u);
+		const bool column = a.layout == kLayoutColumn || a.layout == kLayoutVoxCol;
+		a.bc_base = (uint64_t) (uintptr_t) array - (column ? kColPadBytes : 0u);
 		a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
 		             copy_bytes(c, a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
-		                           a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : kCopyQuadXY + a.brick_plane);
-		if (a.layout == kLayoutColumn) a.bc_bytes += 2ull * kColPadBytes;
+		                           a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane);
+		if (column) a.bc_bytes += 2ull * kColPadBytes;
 		a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, kCopyRunY) : 0;
 		a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
 		// self-test of the net itself: VR_BC_SELFTEST=1 halves the size the checks hold the gathers against — a full-march frame must then fail
@@ -1089,6 +1101,13 @@ int vr_hip_set_brick_plane(vr_ctx *c, int32_t plane) {
 	c->oct_always = plane == (int32_t) kPlanes + 2;
 	c->brick_plane_force = c->oct_always ? -1 : plane;
 	c->map_cached = 0; c->map_next = 0;          // cached lane orders were chosen for another plane
+	return VR_OK;
+}
+
+int vr_hip_set_column_copy(vr_ctx *c, uint32_t mode) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (mode > 1u) return fail(c, VR_ERR_INVALID, "column copy must be 0 (voxel windows where a wave's columns fit, else quad-element windows) or 1 (quad-element windows)");
+	c->column_copy = mode;
 	return VR_OK;
 }
 

@@ -1943,6 +1943,374 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 	if (out_index != 0xffffffffu) ((ConstKernelArguments) dense_args())->out[out_index] = rgba;
 }
 
+// ---- the TRILINEAR column march over the 1-byte voxel windows (voxcol_tri_kernel) ---------------------------------------------------
+//
+// colmarch_kernel's views, colmarch_kernel's arithmetic, colmarch_nearest_kernel's copy (kCopyColVox*: 16 consecutive voxels of a column
+// per 16-byte window, 1 byte per voxel instead of the 16/3 of the quad-element windows).  On these views every lane of a wave samples the
+// same cell along m at every step and stays in one cell column (but for at most one flip per lateral axis), so a wave needs only the
+// RECTANGLE of columns its lanes sample: their own, their +1 neighbours and the columns they flip to (at most 7 x 7 at 0.5 cells per
+// pixel; the host admits a frame only when its 8 x 8-pixel waves fit in 64 columns, the kernel re-checks per wave).  Lane j gathers the
+// window of column j of that rectangle (ONE managed 16-byte gather per lane and 16 cells); a sample's eight corners come from the four
+// lanes that own its 2 x 2 columns — each owner aligns the two slices of the wave-uniform cell into one dword, four ds_bpermute and four
+// v_perm rebuild the quad-element pair (w0, w1) that colmarch_kernel reads from its copy, and from there on the sample is colmarch_kernel's,
+// expression by expression.  A flip is a switch of the lane's owner index at the first k of its second column (bisection once per ray),
+// exact per sample: no event windows.  The transparency test is ONE per window and wave: the slices 16w .. 16w + 16 of every column of
+// the rectangle (the 16 cells of window w need the first slice of window w + 1 too).  Waves that cannot share the k sequence or the
+// rectangle march per lane with explicit byte loads from the same copy; the shading sample is an explicit fetch of its 2 x 2 x 2 corners.
+// prefetch depth in windows of 16 cells (the window after the one consumed has landed too: it holds the last cell's second slice)
+#ifndef VR_VOXCOL_DEPTH
+#define VR_VOXCOL_DEPTH 3
+#endif
+constexpr int kVoxColDepth = VR_VOXCOL_DEPTH, kVoxColSlots = kVoxColDepth + 1;
+static_assert(kVoxColDepth >= 2 && 2 * kVoxColSlots + kVoxColDepth + 4 <= 64, "kColPadBytes");
+
+template <int SAMPLING, int M, bool FLIPS>
+#ifndef VR_VOXCOL_WAVES
+#define VR_VOXCOL_WAVES VR_COL_WAVES
+#endif
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(VR_VOXCOL_WAVES, 8)))       // 64 VGPRs, 80 SGPRs, no spills: tests/test_voxcol_march.py
+void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, const float *__restrict__ tf_g, uint32_t *__restrict__ out) {
+	constexpr bool kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;
+	constexpr int U = M == 0 ? 1 : 0, V = M == 2 ? 1 : 2;
+	constexpr int kCells = (int) kColVoxCells;
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	__shared__ f4 tf_l[VR_TF_SIZE + 1], dtf_l[VR_TF_SIZE + 1];
+	__shared__ f4 org_l[512];
+	{
+		const uint32_t t = threadIdx.x;
+		if (t <= VR_TF_SIZE) {
+			const f4 *tf4 = (const f4 *) tf_g;
+			const uint32_t i0 = t < VR_TF_SIZE ? t : VR_TF_SIZE - 1, i1 = t + 1 < VR_TF_SIZE ? t + 1 : VR_TF_SIZE - 1;
+			const f4 c0 = tf4[i0], c1 = tf4[i1];
+			tf_l[t] = c0;
+			f4 d; d.x = c1.x - c0.x; d.y = c1.y - c0.y; d.z = c1.z - c0.z; d.w = c1.w - c0.w;
+			dtf_l[t] = d;
+		}
+	}
+	__syncthreads();
+	uint32_t tile_x, tile_y;
+	tile_to_xy<VR_COL_XCD_MODE>(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, qd = lane >> 4;
+	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;
+	const uint32_t order = a.lane_map & 3u;
+	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
+	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
+	const uint32_t wx = (qd & 1u) * 4u + gu, wy = (qd >> 1) * 4u + gv, ox = (wave & 3u) * 8u, oy = (wave >> 2) * 8u;
+	const uint32_t lx = tile_x * 32u + ox + wx - a.phase_x, ly = tile_y * 16u + oy + wy - a.phase_y;
+	const bool in_frame = lx < a.p.out_width && ly < a.p.out_rows;
+	const uint32_t band = ly / a.p.band_rows;
+	const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
+	const uint32_t gx = a.p.x0 + lx;
+	uint32_t out_index = in_frame ? ly * a.p.out_width + lx : 0xffffffffu;
+
+	bool alive = in_frame && gx < a.p.view.width && gy < a.p.view.height;
+	const f3 dir = ld3(a.p.view.direction);
+	f3 origin;                                                          // kept in the thread's LDS slot for the samples that are shaded (see colmarch_kernel)
+	{
+		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u)), fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
+		const f3 o = mk3(a.p.view.origin[0] + a.p.view.right_plane[0] * fx, a.p.view.origin[1] + a.p.view.right_plane[1] * fx, a.p.view.origin[2] + a.p.view.right_plane[2] * fx);
+		origin = mk3(o.x + a.p.view.up_plane[0] * fy, o.y + a.p.view.up_plane[1] * fy, o.z + a.p.view.up_plane[2] * fy);
+	}
+	uint32_t org_slot = threadIdx.x * (uint32_t) sizeof(f4);
+	{ f4 o4; o4.x = origin.x; o4.y = origin.y; o4.z = origin.z; o4.w = 0.0f; org_l[threadIdx.x] = o4; }
+	auto origin_again = [&]() { pin(org_slot); const f4 o4 = *(const f4 *) ((const char *) org_l + org_slot); return mk3(o4.x, o4.y, o4.z); };
+	float kx = 0, ky = 0;
+	alive = alive && intersect(origin, dir, kx, ky);
+	const float step = a.p.ray_step;
+	alive = alive && (ky + step > ky);
+	ky = flmin(ky, kx + step * (float) kMaxRaySteps);
+	const uint64_t alive_mask = __builtin_amdgcn_ballot_w64(alive);
+	if (alive_mask == 0ull) { if (in_frame) out[out_index] = 0u; return; }
+	if (!alive) ky = -1.0f;
+
+	auto uni = [](float v) { return __uint_as_float(rfl(__float_as_uint(v))); };
+	const f3 A = mk3(uni(dir.x * a.half_x), uni(dir.y * a.half_y), uni(dir.z * a.half_z));
+	const f3 B = mk3(VR_FMA(origin.x, a.half_x, a.off_x), VR_FMA(origin.y, a.half_y, a.off_y), VR_FMA(origin.z, a.half_z, a.off_z));
+	const float Am = comp3<M>(A), Au = comp3<U>(A), Av = comp3<V>(A);
+	const float Bm = comp3<M>(B), Bu = comp3<U>(B), Bv = comp3<V>(B);
+	const uint32_t dim_u = U == 0 ? a.dim_x : a.dim_y, dim_v = V == 1 ? a.dim_y : a.dim_z, dim_m = M == 0 ? a.dim_x : (M == 1 ? a.dim_y : a.dim_z);
+	const float max_u = U == 0 ? a.max_x : a.max_y, max_v = V == 1 ? a.max_y : a.max_z;
+	const uint32_t nbu = col_blocks(dim_u), nw = col_windows(dim_m, kColVoxCells);
+	const uint64_t stride_u = (uint64_t) nw * kColBlockBytes, stride_v = (uint64_t) nbu * stride_u;
+	auto f_u = [&](int c) { return (uint64_t) ((uint32_t) c >> kColEdgeLog2) * stride_u + ((uint32_t) c & kColEdgeMask) * kColWindowBytes; };
+	auto f_v = [&](int c) { return (uint64_t) ((uint32_t) c >> kColEdgeLog2) * stride_v + ((uint32_t) c & kColEdgeMask) * kColRowBytes; };
+
+	f4 acc; acc.x = acc.y = acc.z = acc.w = 0.0f;
+	uint64_t live = alive_mask;
+	float k = kx;
+
+	auto dense_args = []() { ConstArgs q = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(q)); return q; };
+	struct KernelArguments { RayKernelArgs a; const uint8_t *copy; const float *tf_g; uint32_t *out; };
+	typedef const KernelArguments __attribute__((address_space(4))) *ConstKernelArguments;
+	// the eight corner voxels of a texel-space position as the quad-element pair (march index i, i + 1), by explicit byte loads from the
+	// voxel windows; every index clamped (at the upper faces like the quad copy: the weight there is exactly 0): any position is in bounds
+	auto corners_at = [&](const uint8_t *copy_p, float mx, float my, float mz, uint32_t blocks_u, uint32_t windows, float xb, float yb, float zb,
+	                      uint32_t &w0, uint32_t &w1) {
+		const uint32_t ix = (uint32_t) (int) __builtin_amdgcn_fmed3f(xb, 0.0f, mx), iy = (uint32_t) (int) __builtin_amdgcn_fmed3f(yb, 0.0f, my),
+		               iz = (uint32_t) (int) __builtin_amdgcn_fmed3f(zb, 0.0f, mz);
+		const float fu = U == 0 ? mx : my, fv = V == 1 ? my : mz, fm = M == 0 ? mx : (M == 1 ? my : mz);
+		const uint32_t iu = U == 0 ? ix : iy, iv = V == 1 ? iy : iz, im = M == 0 ? ix : (M == 1 ? iy : iz);
+		const uint32_t iu1 = iu + ((float) iu < fu ? 1u : 0u), iv1 = iv + ((float) iv < fv ? 1u : 0u), im1 = im + ((float) im < fm ? 1u : 0u);
+		// 32-bit byte offsets from the copy's start (the host takes this kernel only for copies below 4 GiB): one VGPR per address
+		auto lat = [&](uint32_t u, uint32_t v) {
+			return ((v >> kColEdgeLog2) * blocks_u + (u >> kColEdgeLog2)) * windows * kColBlockBytes + (v & kColEdgeMask) * kColRowBytes + (u & kColEdgeMask) * kColWindowBytes;
+		};
+		auto along = [](uint32_t m) { return (m >> 4) * kColBlockBytes + (m & 15u); };
+		auto ld = [&](uint32_t off) { return (uint32_t) *VR_BC_POINTER(a, const uint8_t *, copy_p + off, 1u); };
+		const uint32_t l00 = lat(iu, iv), l10 = lat(iu1, iv), l01 = lat(iu, iv1), l11 = lat(iu1, iv1), m0 = along(im), m1 = along(im1);
+		w0 = ld(l00 + m0) | (ld(l10 + m0) << 8) | (ld(l01 + m0) << 16) | (ld(l11 + m0) << 24);
+		w1 = ld(l00 + m1) | (ld(l10 + m1) << 8) | (ld(l01 + m1) << 16) | (ld(l11 + m1) << 24);
+	};
+	auto fetch_at = [&](float kk, uint32_t &w0, uint32_t &w1) {         // the corners of the sample at kk, from each lane's true column
+		ConstArgs q = dense_args();
+		const float xb = VR_FMA(kk, q->col_sample.ax, B.x), yb = VR_FMA(kk, q->col_sample.ay, B.y), zb = VR_FMA(kk, q->col_sample.az, B.z);
+		corners_at(((ConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb, w0, w1);
+	};
+	// one sample at `k` whose element pair is (w0, w1): colmarch_kernel's body, but for where the shading sample's corners come from
+	auto sample = [&](uint32_t w0, uint32_t w1) {
+		if ((__builtin_amdgcn_uicmp((w0 | w1) & a.skip_mask, a.skip_cmp, kIcmpNE) & live) != 0ull && VR_OPEN_LANES(acc.w, live) != 0ull) {
+			ConstArgs q = dense_args();
+			RayKernelArgs::ColDenseSample ds;
+			ds.ax = q->col_sample.ax; ds.ay = q->col_sample.ay; ds.az = q->col_sample.az; ds.tf_scale = q->col_sample.tf_scale;
+			ds.max_x = q->col_sample.max_x; ds.max_y = q->col_sample.max_y; ds.max_z = q->col_sample.max_z; ds.tf_zero_below = q->col_sample.tf_zero_below;
+			ds.light_kd = q->col_sample.light_kd; ds.ray_threshold = q->col_sample.ray_threshold;
+			hold_scalars(ds.ax, ds.ay, ds.az, ds.tf_scale, ds.max_x, ds.max_y, ds.max_z, ds.tf_zero_below, ds.light_kd, ds.ray_threshold);
+			live &= __builtin_amdgcn_fcmpf(k, ky, kFcmpOLE);
+			const float xb = VR_FMA(k, ds.ax, B.x), yb = VR_FMA(k, ds.ay, B.y), zb = VR_FMA(k, ds.az, B.z);
+			const float raw = col_resolve<M, kQ8>(w0, w1, ds.max_x, ds.max_y, ds.max_z, xb, yb, zb);     // GPURenderer4.cu:76
+			const float tb = __builtin_amdgcn_fmed3f(VR_FMA(raw, ds.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
+			if ((__builtin_amdgcn_fcmpf(tb, ds.tf_zero_below, kFcmpOGE) & live) != 0ull) {
+				f4 c;
+				{
+					const uint32_t i = (uint32_t) (int) tb;
+					const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
+					const f4 c0 = tf_l[i], dc = dtf_l[i];
+					c.x = VR_FMA(w, dc.x, c0.x); c.y = VR_FMA(w, dc.y, c0.y); c.z = VR_FMA(w, dc.z, c0.z); c.w = VR_FMA(w, dc.w, c0.w);
+				}
+				const uint64_t shaded = ds.light_kd > 0.01f ? (__builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live) : 0ull;   // GPURenderer4.cu:78
+				if (shaded != 0ull) {                                                                  // GPURenderer4.cu:41-51 shade_texture
+					const f3 org = origin_again();
+					RayKernelArgs::ColDenseShade dh;
+					for (int i = 0; i < 3; i++) { dh.dir[i] = q->col_shade.dir[i]; dh.light[i] = q->col_shade.light[i]; dh.lh[i] = q->col_shade.lh[i]; }
+					dh.kd_scaled = q->col_shade.kd_scaled; dh.nbu = q->col_shade.nbu; dh.nw = q->col_shade.nw;
+					const uint8_t *const copy_p = ((ConstKernelArguments) q)->copy;
+					hold_scalars(dh.dir[0], dh.dir[1], dh.dir[2], dh.kd_scaled, dh.light[0], dh.light[1], dh.light[2], dh.lh[0], dh.lh[1], dh.lh[2]);
+					hold_scalars(dh.nbu, dh.nw, (uint64_t) (uintptr_t) copy_p);
+					const f3 p3 = march_point<SAMPLING>(org, mk3(dh.dir[0], dh.dir[1], dh.dir[2]), k);
+					const f3 d = mk3(dh.light[0] - p3.x, dh.light[1] - p3.y, dh.light[2] - p3.z);
+					const float inv = rsqrt_nr(VR_FMA(d.z, d.z, VR_FMA(d.y, d.y, d.x * d.x)));
+					const float sx = VR_FMA(d.x * inv, dh.lh[0], xb), sy = VR_FMA(d.y * inv, dh.lh[1], yb), sz = VR_FMA(d.z * inv, dh.lh[2], zb);
+					uint32_t l0, l1;
+					corners_at(copy_p, ds.max_x, ds.max_y, ds.max_z, dh.nbu, dh.nw, sx, sy, sz, l0, l1);
+					const float raw_l = col_resolve<M, kQ8>(l0, l1, ds.max_x, ds.max_y, ds.max_z, sx, sy, sz);
+					const float diffuse = select_lanes(shaded, (raw_l - raw) * dh.kd_scaled);
+					c.x += diffuse; c.y += diffuse; c.z += diffuse;
+				}
+				const float t = select_lanes(live, 1 - acc.w);
+				acc.x = VR_FMA(c.x, t, acc.x); acc.y = VR_FMA(c.y, t, acc.y); acc.z = VR_FMA(c.z, t, acc.z); acc.w = VR_FMA(c.w, t, acc.w);
+				live &= ~__builtin_amdgcn_fcmpf(acc.w, ds.ray_threshold, kFcmpOGT);                    // ERT (CPURenderer.cpp:35-36)
+			}
+		}
+	};
+
+	// -- can this wave take the column path?  (colmarch_kernel's conditions, and a column rectangle of at most 64 columns)
+	const int leader = __builtin_ctzll(alive_mask);
+	const float kx_l = rlane(kx, leader), Bm_l = rlane(Bm, leader);
+	bool ok = __builtin_amdgcn_ballot_w64(alive && (__float_as_uint(kx) != __float_as_uint(kx_l) || __float_as_uint(Bm) != __float_as_uint(Bm_l))) == 0ull;
+	const float advance = __builtin_fabsf(Am) * step;
+	ok = ok && __builtin_amdgcn_ballot_w64(!(advance >= (1.0f / 64.0f) && advance <= 1.0f)) == 0ull;
+	auto cell = [&](float kk, float Ac, float Bc, float maxc) { return (int) __builtin_amdgcn_fmed3f(VR_FMA(kk, Ac, Bc), 0.0f, maxc); };
+	int cu0 = cell(kx, Au, Bu, max_u), cv0 = cell(kx, Av, Bv, max_v);
+	int cu1 = cell(ky, Au, Bu, max_u), cv1 = cell(ky, Av, Bv, max_v);
+	{
+		const int lu = __builtin_amdgcn_readlane(cu0, leader), lv = __builtin_amdgcn_readlane(cv0, leader);
+		if (!alive) { cu0 = cu1 = lu; cv0 = cv1 = lv; ky = -1.0f; }
+	}
+	const uint64_t flips = __builtin_amdgcn_ballot_w64(cu0 != cu1 || cv0 != cv1);
+	ok = ok && __builtin_amdgcn_ballot_w64((cu1 - cu0) * (cu1 - cu0) > 1 || (cv1 - cv0) * (cv1 - cv0) > 1) == 0ull;
+	ok = ok && (FLIPS || flips == 0ull);
+	// the rectangle [ru0, ru1] x [rv0, rv1]: every column a lane samples, with its +1 neighbours
+	int ru0 = cu0 < cu1 ? cu0 : cu1, ru1 = (cu0 > cu1 ? cu0 : cu1) + 1, rv0 = cv0 < cv1 ? cv0 : cv1, rv1 = (cv0 > cv1 ? cv0 : cv1) + 1;
+	#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		const int a0 = __shfl_xor(ru0, d, 64), a1 = __shfl_xor(ru1, d, 64), a2 = __shfl_xor(rv0, d, 64), a3 = __shfl_xor(rv1, d, 64);
+		ru0 = a0 < ru0 ? a0 : ru0; ru1 = a1 > ru1 ? a1 : ru1; rv0 = a2 < rv0 ? a2 : rv0; rv1 = a3 > rv1 ? a3 : rv1;
+	}
+	ru0 = (int) rfl((uint32_t) ru0); ru1 = (int) rfl((uint32_t) ru1); rv0 = (int) rfl((uint32_t) rv0); rv1 = (int) rfl((uint32_t) rv1);
+	const int rw = ru1 - ru0 + 1, nrect = rw * (rv1 - rv0 + 1);
+	ok = ok && nrect <= 64;
+	// the column this lane OWNS (gathers for the wave): column j of the rectangle, row by row; lanes beyond it repeat the last one; indices
+	// clamped at the upper faces.  Offsets relative to the rectangle's first column, biased by 2^30 (colmarch_kernel)
+	const uint32_t lane_i = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+	int own_u, own_v;
+	{
+		const int j = (int) lane_i < nrect ? (int) lane_i : nrect - 1;
+		const int jv = j / rw;
+		own_u = ru0 + (j - jv * rw); own_v = rv0 + jv;
+		own_u = own_u < (int) dim_u - 1 ? own_u : (int) dim_u - 1; own_v = own_v < (int) dim_v - 1 ? own_v : (int) dim_v - 1;
+	}
+	const int64_t ref = (int64_t) (f_u(ru0) + f_v(rv0));
+	const int64_t rel = (int64_t) (f_u(own_u) + f_v(own_v)) - ref;
+	ok = ok && __builtin_amdgcn_ballot_w64(rel < 0 || rel >= (1ll << 28)) == 0ull;
+
+	auto per_lane_march = [&]() {                                        // exact, unpipelined: waves that straddle two kx values, or too many columns
+		while (live != 0ull) {
+			uint32_t w0, w1;
+			fetch_at(k, w0, w1);
+			sample(w0, w1);
+			k += step;
+			live &= __builtin_amdgcn_fcmpf(k, ky, kFcmpOLE);
+		}
+	};
+	if (ok) {
+		const uint32_t voff = (uint32_t) (rel + (1ll << 30));
+		uint64_t s_base;
+		{
+			const uint64_t b = (uint64_t) (uintptr_t) copy + (uint64_t) ref - (1ull << 30);
+			s_base = ((uint64_t) rfl((uint32_t) (b >> 32)) << 32) | rfl((uint32_t) b);
+		}
+		const int dsign = (__float_as_uint(comp3<M>(dir)) >> 31) != 0u ? -1 : 1;
+		const bool forward = dsign > 0;
+		// where this lane reads its corners: the byte address (ds_bpermute) of the owner of its (u, v) column; the owners of (u+1, v), (u, v+1)
+		// and (u+1, v+1) follow at +4, +4 rw, +4 rw + 4.  A lane whose column flips switches at the smallest float t in (kx, ky] with
+		// cell(t) != cell(kx) (bisection over the positive float bit patterns, once per ray; the cell is monotone in k): samples with
+		// k >= t read the second column — exact per sample
+		const uint32_t rw4 = (uint32_t) rw * 4u;
+		const uint32_t own0 = (uint32_t) ((cu0 - ru0) + (cv0 - rv0) * rw) * 4u;
+		float t_u = __builtin_inff(), t_v = __builtin_inff();
+		uint32_t step_u = 0u, step_v = 0u;
+		if (FLIPS && flips != 0ull) {
+			auto bisect = [&](bool flipping, int c0, float Ac, float Bc, float maxc) {
+				uint32_t lo = __float_as_uint(kx), hi = __float_as_uint(ky);
+				if (!flipping) hi = lo;
+				for (int it = 0; it < 34 && __builtin_amdgcn_ballot_w64(hi - lo > 1u) != 0ull; it++) {
+					const uint32_t mid = lo + ((hi - lo) >> 1);
+					const bool same = cell(__uint_as_float(mid), Ac, Bc, maxc) == c0;
+					if (hi - lo > 1u) { if (same) lo = mid; else hi = mid; }
+				}
+				return flipping ? __uint_as_float(hi) : __builtin_inff();
+			};
+			t_u = bisect(cu0 != cu1, cu0, Au, Bu, max_u);
+			t_v = bisect(cv0 != cv1, cv0, Av, Bv, max_v);
+			step_u = (uint32_t) (cu1 - cu0) * 4u; step_v = (uint32_t) (cv1 - cv0) * rw4;      // (two's complement: the sums wrap back into range)
+		}
+		// the wave-uniform sample sequence, 64 samples at a time (colmarch_kernel: exact arithmetic progression inside a binade)
+		auto window_of = [](int lc) { return lc >> 4; };
+		float kvec = 0.0f, knext = kx_l;
+		int wvec = 0;
+		auto refill = [&]() {
+			const float kbase = knext;
+			const float k1 = kbase + step, delta = k1 - kbase, low = step - delta;
+			const uint32_t e = __float_as_uint(kbase) >> 23;
+			const float half_ulp = __uint_as_float((e > 24u ? e - 24u : 1u) << 23);
+			const float kend = VR_FMA(64.0f, delta, kbase);
+			const bool fast = rfl((e > 24u && (__float_as_uint(kend) >> 23) == e && __builtin_fabsf(low) != half_ulp && delta > 0.0f) ? 1u : 0u) != 0u;
+			if (fast) { kvec = VR_FMA((float) lane_i, delta, kbase); knext = uni(kend); }
+			else {
+				float kc = kbase;
+				#pragma nounroll
+				for (uint32_t j = 0; j < 64u; j++) { kvec = lane_i == j ? kc : kvec; kc = kc + step; }
+				knext = uni(kc);
+			}
+			wvec = window_of((int) VR_FMA(kvec, Am, Bm_l));               // (cell by truncation, as colmarch_kernel; may leave 0 .. Nm-1 past the exit)
+		};
+		refill();
+		int pos = 0;
+		int cur = __builtin_amdgcn_readlane(wvec, 0);
+		cur = cur < 0 ? 0 : (cur > (int) nw - 1 ? (int) nw - 1 : cur);
+		// hang / bounds guard as in colmarch_kernel; what lies beyond a column's windows is a neighbouring block's or the zeroed padding
+		int guard = (dsign > 0 ? (int) nw - cur : cur + 1) + 2 * kVoxColSlots;
+		int woff = cur * (int) kColBlockBytes;
+		auto issue = [&](u32x4 &dst) {
+			const uint32_t lane_offset = voff + (uint32_t) woff;
+#if defined(VR_BOUNDS_CHECK)
+			managed_load128(dst, VR_BC_ADDRESS(a, s_base + lane_offset, 16u));
+#else
+			managed_load128_s(dst, lane_offset, s_base);
+#endif
+			woff += dsign * (int) kColBlockBytes;
+		};
+		// the first slice of window cur + 1 — the last cell of window cur needs it: marching up it is the next window's (in a slot), marching
+		// down the previous one's, kept in `carry` (for the first window: one extra gather, oldest of the pipeline)
+		uint32_t carry;
+		{
+			const uint32_t lane_offset = voff + (uint32_t) ((cur + 1) * (int) kColBlockBytes);
+#if defined(VR_BOUNDS_CHECK)
+			asm volatile("global_load_dword %0, %1, off" : "=&v"(carry) : "v"(VR_BC_ADDRESS(a, s_base + lane_offset, 4u)));
+#else
+			managed_load32(carry, lane_offset, (const void *) (uintptr_t) s_base);
+#endif
+		}
+		u32x4 slot[kVoxColSlots];
+		slot[kVoxColSlots - 1] = (u32x4) (0u);
+		static_for<0, kVoxColDepth>([&](auto j) { issue(slot[j.value]); });
+		auto window_step = [&](auto jc) {
+			constexpr int c = decltype(jc)::value, n = (c + kVoxColDepth) % kVoxColSlots, c1 = (c + 1) % kVoxColSlots;
+			issue(slot[n]);
+			__builtin_amdgcn_sched_barrier(0);
+			pin(slot[c]); pin(slot[c1]); pin(carry); managed_wait<kVoxColDepth - 1>(); pin(slot[c]); pin(slot[c1]); pin(carry);
+			const u32x4 o = slot[c];
+			const uint32_t nx = forward ? slot[c1].x : carry;
+			// (held as scalars: left to the compiler, their copies at the window's branch go through a vector register, and such a copy may
+			// name a gather still in flight — tests/test_voxcol_march.py walks the built code)
+			pos = (int) rfl((uint32_t) pos); cur = (int) rfl((uint32_t) cur);
+			if (c == 0) live &= __builtin_amdgcn_fcmpf(rlane(kvec, pos), ky, kFcmpOLE);
+			const uint32_t all17 = (o.x | o.y | o.z | o.w | (nx & 0xffu)) & a.skip_mask;
+			// dense: some column of the rectangle holds a voxel at or above the skip threshold in slices 16 cur .. 16 cur + 16, and a lane is open
+			const bool dense = (__builtin_amdgcn_ballot_w64(lane_i < (uint32_t) nrect && all17 != a.skip_cmp) != 0ull) & (VR_OPEN_LANES(acc.w, live) != 0ull);
+			if (!dense) {
+				for (int batches = 0; batches < kCells + 2; batches++) {
+					pos += __builtin_popcountll(__builtin_amdgcn_ballot_w64(wvec == cur));
+					if (pos < 64) break;
+					refill(); pos = 0;
+				}
+				pos = pos < 64 ? pos : 63;
+			} else {
+				const int first = cur * kCells;
+				for (int batches = 0; batches < kCells + 2; batches++) {
+					const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(wvec == cur));
+					for (int i = pos; i < pos + cnt; i++) {
+						k = rlane(kvec, i);
+						const uint32_t sub = (uint32_t) ((int) rfl((uint32_t) (int) VR_FMA(k, Am, Bm_l)) - first) & 15u;      // the sample's cell inside the window (uniform)
+						// the owner's two slices of that cell in one dword (byte 0: slice sub, byte 1: slice sub + 1)
+						const uint32_t qw = sub >> 2;
+						const uint32_t lo = qw == 0u ? o.x : (qw == 1u ? o.y : (qw == 2u ? o.z : o.w));
+						const uint32_t hi = qw == 0u ? o.y : (qw == 1u ? o.z : (qw == 2u ? o.w : nx));
+						const int pair = (int) __builtin_amdgcn_alignbyte(hi, lo, sub & 3u);
+						uint32_t at = own0;
+						if (FLIPS) at += (k >= t_u ? step_u : 0u) + (k >= t_v ? step_v : 0u);
+						const uint32_t p00 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) at, pair), p10 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + 4u), pair);
+						const uint32_t p01 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4), pair), p11 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4 + 4u), pair);
+						// (u,v) (u+1,v) (u,v+1) (u+1,v+1) of slice sub -> w0, of slice sub + 1 -> w1
+						const uint32_t t0 = __builtin_amdgcn_perm(p10, p00, 0x05010400u), t1 = __builtin_amdgcn_perm(p11, p01, 0x05010400u);
+						sample(__builtin_amdgcn_perm(t1, t0, 0x05040100u), __builtin_amdgcn_perm(t1, t0, 0x07060302u));
+					}
+					pos += cnt;
+					if (pos < 64) break;
+					refill(); pos = 0;
+				}
+				pos = pos < 64 ? pos : 63;
+			}
+			carry = o.x;
+			cur += dsign;
+		};
+		while (live != 0ull && guard > 0) {
+			static_for<0, kVoxColSlots>(window_step);
+			guard -= kVoxColSlots;
+		}
+		static_for<0, kVoxColSlots>([&](auto j) { pin(slot[j.value]); });
+		pin(carry);
+		managed_wait<0>();
+		static_for<0, kVoxColSlots>([&](auto j) { pin(slot[j.value]); });
+		pin(carry);
+	} else per_lane_march();
+	uint32_t ky_bits = __float_as_uint(ky);
+	pin(ky_bits, out_index);
+	uint32_t rgba = 0;
+	if (__uint_as_float(ky_bits) > 0.0f) rgba = map_float_int(acc.x, 256) | (map_float_int(acc.y, 256) << 8) | (map_float_int(acc.z, 256) << 16) | (map_float_int(acc.w, 256) << 24);
+	if (out_index != 0xffffffffu) ((ConstKernelArguments) dense_args())->out[out_index] = rgba;
+}
+
 // Which instantiation a frame runs: ONE selector, visited by the launcher and by the host's questions about the launch (does it read
 // the linear array?  how many workgroup tiles?), so the answers cannot drift from what is launched.  `visit` is called with four
 // std::integral_constant tags <SAMPLING, BPV, ADDR, LAYOUT> and a bool: true = the variant reads `linear`, false = the brick copy.
@@ -2006,7 +2374,7 @@ template <int ADDR, int LAYOUT> constexpr uint32_t variant_threads() { return Lu
 
 // what launch_raymarch will do with these arguments (launch_frame asks before it launches)
 RaymarchPlan plan_raymarch(const RayKernelArgs &a, bool have_bricked, uint32_t bpv) {
-	if (have_bricked && a.layout == kLayoutColumn) {                     // colmarch_kernel: 512 threads = 32x16 pixels
+	if (have_bricked && (a.layout == kLayoutColumn || a.layout == kLayoutVoxCol)) {      // the column kernels: 512 threads = 32x16 pixels
 		RaymarchPlan plan;
 		plan.reads_linear = false;
 		plan.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u; plan.tiles_y = (a.p.out_rows + a.phase_y + 15u) / 16u;
@@ -2025,7 +2393,7 @@ RaymarchPlan plan_raymarch(const RayKernelArgs &a, bool have_bricked, uint32_t b
 
 hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
                            const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
-	if (bricked != nullptr && args.layout == kLayoutColumn) {            // orthogonal view along args.col_axis, full march, TRILINEAR, 1-byte voxels (launch_frame)
+	if (bricked != nullptr && (args.layout == kLayoutColumn || args.layout == kLayoutVoxCol)) {      // orthogonal view along args.col_axis, full march, 1-byte voxels (launch_frame)
 		RayKernelArgs a = args;
 		a.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u; a.tiles_y = (a.p.out_rows + a.phase_y + 15u) / 16u;
 		const dim3 grid(a.tiles_x * a.tiles_y), block(512);
@@ -2040,9 +2408,11 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
 			else { if (flips) go(colmarch_nearest_kernel<2, true>); else go(colmarch_nearest_kernel<2, false>); }
 			return hipGetLastError();
 		}
+		const bool voxels = a.layout == kLayoutVoxCol;                      // voxel windows (kCopyColVoxX ..): voxcol_tri_kernel
 		auto pick = [&](auto sampling, auto axis) {
 			constexpr int S = decltype(sampling)::value, AX = decltype(axis)::value;
-			if (flips) go(colmarch_kernel<S, AX, true>); else go(colmarch_kernel<S, AX, false>);
+			if (voxels) { if (flips) go(voxcol_tri_kernel<S, AX, true>); else go(voxcol_tri_kernel<S, AX, false>); }
+			else if (flips) go(colmarch_kernel<S, AX, true>); else go(colmarch_kernel<S, AX, false>);
 		};
 		auto pick_axis = [&](auto sampling) {
 			if (m == 0u) pick(sampling, std::integral_constant<int, 0>()); else if (m == 1u) pick(sampling, std::integral_constant<int, 1>()); else pick(sampling, std::integral_constant<int, 2>());
