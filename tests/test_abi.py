@@ -61,6 +61,19 @@ def test_product_never_imports_the_oracle():
                 assert "vr_oracle" not in text.replace("oracle/vr_oracle.c", "") and "libvolr_ref" not in text, os.path.join(dirpath, f)
 
 
+def _no_spill_kernels(resource_log_text, kernel_pattern):
+    """The kernels of the build's -Rpass-analysis log whose mangled name matches `kernel_pattern`, each held against what 8 waves per
+    SIMD without spilling mean: <= 80 SGPRs, <= 64 VGPRs, no scratch, no SGPR or VGPR spilled.  Returns the set of their names."""
+    found = set()
+    for m in re.finditer(r"Function Name: (\S*" + kernel_pattern + r"\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+                         r"SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", resource_log_text, flags=re.S):
+        sgprs, vgprs, scratch, sspill, vspill = (int(g) for g in m.groups()[-5:])
+        found.add(m.group(1))
+        assert scratch == 0 and sspill == 0 and vspill == 0, (m.group(1), "spills", scratch, sspill, vspill)
+        assert sgprs <= 80 and vgprs <= 64, (m.group(1), sgprs, vgprs)
+    return found
+
+
 def test_hot_kernels_keep_eight_waves_per_simd(vr):
     """The ray-march variants the product launches by default (bricked layout, table addressing) must stay within 80 SGPRs and
     64 VGPRs: on gfx950 a SIMD then holds 8 of their waves; 81-96 SGPRs silently drop that to 7, i.e. from 4 to 3 resident
@@ -86,14 +99,8 @@ def test_hot_kernels_keep_eight_waves_per_simd(vr):
     # the column march (colmarch_kernel<SAMPLING, axis, FLIPS>): {TRILINEAR, Q8} x {x, y, z} x {with, without the flip logic} = 12 kernels, none
     # may spill — a spilled scalar or vector register is reloaded inside the window loop behind an s_waitcnt that drains the prefetch
     # pipeline, and a build that was FORCED to 8 waves by spilling faulted on the GPU (round 4)
-    found = 0
-    for m in re.finditer(r"Function Name: (\S*colmarch_(?:nearest_kernelILi\d|kernelILi\dELi\d)ELb[01]E\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", text, flags=re.S):
-        sgprs, vgprs, scratch, sspill, vspill = (int(m.group(i)) for i in (2, 3, 4, 5, 6))
-        found += 1
-        assert scratch == 0 and sspill == 0 and vspill == 0, (m.group(1), "spills", scratch, sspill, vspill)
-        assert sgprs <= 80 and vgprs <= 64, (m.group(1), sgprs, vgprs)
-    assert found == 12 + 6, found                   # + colmarch_nearest_kernel<axis, FLIPS>
+    found = _no_spill_kernels(text, r"colmarch_(?:nearest_kernelILi\d|kernelILi\dELi\d)ELb[01]E")
+    assert len(found) == 12 + 6, sorted(found)                # + colmarch_nearest_kernel<axis, FLIPS>
 
 
 def _disassemble_gfx950(lib_path, tmp_path):
@@ -131,6 +138,40 @@ def _vgprs(operand_text):
     return regs
 
 
+def _walk_gathers_in_flight(name, lines, sinks, min_loads, min_waits):
+    """One function's instruction lines in program order: every vector-memory load enters a queue with its destination registers,
+    `s_waitcnt vmcnt(N)` retires all but the N youngest, and no other instruction may name a register (but the `sinks`) of a load
+    still in the queue.  The function must hold at least `min_loads` such loads and `min_waits` such waits."""
+    inflight, loads, waits = [], 0, 0
+    for ins in lines:
+        parts = ins.split(None, 1)
+        op, rest = parts[0], (parts[1] if len(parts) > 1 else "")
+        if op == "s_waitcnt":
+            w = re.search(r"vmcnt\((\d+)\)", rest)
+            if w:
+                n = int(w.group(1))
+                inflight = inflight[len(inflight) - n:] if n < len(inflight) else inflight
+                if n == 0:
+                    inflight = []
+                waits += 1
+            continue
+        if op in ("s_branch", "s_endpgm", "s_setpc_b64"):
+            # what follows is not reached by falling through: a block the compiler moved out of line (the dense path of a window step sits
+            # behind the loop in the binary, i.e. AFTER the next step's gather in program order, but executes before it).  Its
+            # predecessors are unknown to this walk: start it with an empty queue rather than with a false alarm.
+            inflight = []
+            continue
+        regs = _vgprs(rest) - sinks
+        busy = set().union(*inflight) if inflight else set()
+        assert not (regs & busy), f"{name}: `{ins}` names v{sorted(regs & busy)} while a load into it is in flight"
+        if re.match(r"(global|flat|buffer|scratch)_load", op):
+            inflight.append(_vgprs(rest.split(",")[0]))
+            loads += 1
+        elif re.match(r"(global|flat|buffer|scratch)_(store|atomic)", op):
+            inflight.append(set())                      # shares the counter; has no destination to protect
+    assert loads >= min_loads and waits >= min_waits, (name, loads, waits)
+
+
 def test_no_instruction_touches_a_gather_in_flight(vr, tmp_path):
     """the software-pipelined march issues its gathers through inline asm and waits with hand-counted
     `s_waitcnt vmcnt(N)`; that is only correct while the compiler never reads, copies or overwrites a destination register between
@@ -161,32 +202,5 @@ def test_no_instruction_touches_a_gather_in_flight(vr, tmp_path):
                 elsewhere |= _vgprs(",".join(rest.split(",")[1:]))     # everything but the destination
         sinks = load_dst - elsewhere
         assert len(sinks) <= 1, (name, sinks)
-        inflight, loads, waits = [], 0, 0
-        for ins in lines:
-            parts = ins.split(None, 1)
-            op, rest = parts[0], (parts[1] if len(parts) > 1 else "")
-            if op == "s_waitcnt":
-                w = re.search(r"vmcnt\((\d+)\)", rest)
-                if w:
-                    n = int(w.group(1))
-                    inflight = inflight[len(inflight) - n:] if n < len(inflight) else inflight
-                    if n == 0:
-                        inflight = []
-                    waits += 1
-                continue
-            if op in ("s_branch", "s_endpgm", "s_setpc_b64"):
-                # what follows is not reached by falling through: a block the compiler moved out of line (the dense path of a window step sits
-                # behind the loop in the binary, i.e. AFTER the next step's gather in program order, but executes before it).  Its
-                # predecessors are unknown to this walk: start it with an empty queue rather than with a false alarm.
-                inflight = []
-                continue
-            regs = _vgprs(rest) - sinks
-            busy = set().union(*inflight) if inflight else set()
-            assert not (regs & busy), f"{name}: `{ins}` names v{sorted(regs & busy)} while a load into it is in flight"
-            if re.match(r"(global|flat|buffer|scratch)_load", op):
-                inflight.append(_vgprs(rest.split(",")[0]))
-                loads += 1
-            elif re.match(r"(global|flat|buffer|scratch)_(store|atomic)", op):
-                inflight.append(set())                      # shares the counter; has no destination to protect
-        assert (loads >= 20 or column and loads >= 8) and waits >= 10, (name, loads, waits)
+        _walk_gathers_in_flight(name, lines, sinks, 8 if column else 20, 10)
     assert checked >= 10 + 12 + 6, checked

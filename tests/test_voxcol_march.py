@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from test_abi import _disassemble_gfx950, _vgprs
+from test_abi import _disassemble_gfx950, _no_spill_kernels, _walk_gathers_in_flight
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = r"voxcol_tri_kernelILi(\d)ELi(\d)ELb([01])E"
@@ -21,49 +21,20 @@ def test_voxcol_kernels_keep_eight_waves_without_spills(vr):
     log = os.path.join(csrc, "resource_usage.log")
     if not os.path.exists(log):
         subprocess.check_call(["make", "-B", "-C", csrc])
-    text = open(log).read()
-    found = set()
-    for m in re.finditer(r"Function Name: (\S*" + KERNEL + r"\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", text, flags=re.S):
-        sgprs, vgprs, scratch, sspill, vspill = (int(m.group(i)) for i in (5, 6, 7, 8, 9))
-        found.add(m.group(1))
-        assert scratch == 0 and sspill == 0 and vspill == 0, (m.group(1), "spills", scratch, sspill, vspill)
-        assert sgprs <= 80 and vgprs <= 64, (m.group(1), sgprs, vgprs)
+    found = _no_spill_kernels(open(log).read(), KERNEL)
     assert len(found) == 12, sorted(found)
 
 
 def test_voxcol_gathers_in_flight_are_untouched(vr, tmp_path):
-    """tests/test_abi.py's walk over the disassembly, for the new kernel: no instruction names a register of a managed gather that
-    the hand-counted s_waitcnt vmcnt(N) has not retired yet."""
+    """tests/test_abi.py's walk over the disassembly, for this kernel (no sink registers): no instruction names a register of a managed
+    gather that the hand-counted s_waitcnt vmcnt(N) has not retired yet."""
     funcs = _disassemble_gfx950(vr.library_path(), tmp_path)
     checked = 0
     for name, lines in funcs.items():
         if re.search(KERNEL, name) is None:
             continue
         checked += 1
-        inflight, loads, waits = [], 0, 0
-        for ins in lines:
-            parts = ins.split(None, 1)
-            op, rest = parts[0], (parts[1] if len(parts) > 1 else "")
-            if op == "s_waitcnt":
-                w = re.search(r"vmcnt\((\d+)\)", rest)
-                if w:
-                    n = int(w.group(1))
-                    inflight = [] if n == 0 else (inflight[len(inflight) - n:] if n < len(inflight) else inflight)
-                    waits += 1
-                continue
-            if op in ("s_branch", "s_endpgm", "s_setpc_b64"):
-                inflight = []          # an out-of-line block: unknown predecessors (as in test_abi.py)
-                continue
-            regs = _vgprs(rest)
-            busy = set().union(*inflight) if inflight else set()
-            assert not (regs & busy), f"{name}: `{ins}` names v{sorted(regs & busy)} while a load into it is in flight"
-            if re.match(r"(global|flat|buffer|scratch)_load", op):
-                inflight.append(_vgprs(rest.split(",")[0]))
-                loads += 1
-            elif re.match(r"(global|flat|buffer|scratch)_(store|atomic)", op):
-                inflight.append(set())
-        assert loads >= 8 and waits >= 4, (name, loads, waits)
+        _walk_gathers_in_flight(name, lines, set(), 8, 4)
     assert checked == 12, checked
 
 

@@ -230,6 +230,20 @@ __host__ __device__ constexpr uint32_t col_blocks(uint32_t n) { return (n + kCol
 __host__ __device__ constexpr uint32_t col_axis_u(uint32_t m) { return m == 0u ? 1u : 0u; }
 __host__ __device__ constexpr uint32_t col_axis_v(uint32_t m) { return m == 2u ? 1u : 2u; }
 __host__ __device__ inline uint32_t col_windows(uint32_t nm, uint32_t cells = kColCells) { return (nm + cells - 1u) / cells; }
+// Where cell column (u, v) lies in a window copy — the one statement of the layout for everything that reads it (column_build_kernel
+// writes in copy order and never forms a column's address).  The lateral blocks follow each other along u, then v, each a run of
+// `windows` windows of kColBlockBytes along m; inside every window of its block the column's 16 bytes sit at row v, place u.
+__host__ __device__ constexpr uint32_t col_lateral_block(uint32_t u, uint32_t v, uint32_t blocks_u) { return (v >> kColEdgeLog2) * blocks_u + (u >> kColEdgeLog2); }
+__host__ __device__ constexpr uint32_t col_in_block(uint32_t u, uint32_t v) { return (v & kColEdgeMask) * kColRowBytes + (u & kColEdgeMask) * kColWindowBytes; }
+// byte offset of the column's first window: 32-bit (copies below 4 GiB), and 64-bit from the byte strides between lateral blocks
+// (stride_u = windows * kColBlockBytes, stride_v = blocks_u * stride_u), one axis at a time (in_block: kColWindowBytes along u, kColRowBytes along v) or both
+__host__ __device__ constexpr uint32_t col_lateral_offset(uint32_t u, uint32_t v, uint32_t blocks_u, uint32_t windows) {
+	return col_lateral_block(u, v, blocks_u) * windows * kColBlockBytes + col_in_block(u, v);
+}
+__host__ __device__ constexpr uint64_t col_axis_offset64(uint32_t c, uint64_t block_stride, uint32_t in_block) { return (uint64_t) (c >> kColEdgeLog2) * block_stride + (c & kColEdgeMask) * in_block; }
+__host__ __device__ constexpr uint64_t col_lateral_offset64(uint32_t u, uint32_t v, uint64_t stride_u, uint64_t stride_v) {
+	return col_axis_offset64(u, stride_u, kColWindowBytes) + col_axis_offset64(v, stride_v, kColRowBytes);
+}
 // The march prefetches windows past a ray's exit and addresses them by a running pointer without clamping the window index: inside
 // the copy that reads a neighbouring block's windows (never used: those samples lie outside every segment), at its two ends it reads
 // this much zeroed padding (64 windows).  The kernel bounds its window count by the windows left in march direction + kColSlots + 2 (colmarch_kernel).
