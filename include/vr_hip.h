@@ -196,6 +196,34 @@ int vr_hip_read_tile_costs(vr_ctx *ctx, uint32_t *host_out, uint32_t capacity, u
 int vr_hip_render(vr_ctx *ctx, const vr_params *params, uint8_t *host_rgba);
 int vr_hip_render_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
 
+/* ---- maximum-intensity projection (MIP): the second projection next to the front-to-back composite above.  No reference counterpart. ----
+ * Per pixel:
+ *  1. the ray is View::get_ray + Raycaster::intersect exactly as in vr_hip_render; a miss leaves the pixel cleared (0,0,0,0);
+ *  2. the samples are those of the march with leaping off: `while (kx <= ky) { sample at kx; kx += ray_step; }` — kx, ky from intersect,
+ *     kx accumulated by repeated addition, the position formed from kx for every sample.  Nothing below changes this sequence;
+ *  3. VR_SAMPLE_NEAREST: m = the integer maximum of the raw voxels Model::sample_data returns (its unfused arithmetic); the colour is
+ *     transfer_fn[s8 / VR_TF_RATIO] with s8 = m for 1-byte voxels and m >> 8 for 2-byte voxels;
+ *  4. VR_SAMPLE_TRILINEAR / _Q8: m = the float maximum of the interpolated RAW value (texel coordinates fma(k, A, B), the lerps of the
+ *     TRILINEAR mode, Q8 with rounded weights), starting at 0; the colour is the linearly filtered transfer-function lookup of m with the
+ *     arithmetic of a composited sample's lookup (Q8: rounded weight);
+ *  5. the pixel is write_color(colour): the premultiplied entry as it is stored.  No shading, no compositing: ray_threshold, light_kd and
+ *     light_pos are ignored;
+ *  6. x0, out_width, out_rows and band_* partition the frame as in vr_hip_render.
+ * params.esl selects EXACT acceleration.  0: every sample is fetched, no ray stops early.  Otherwise the kernel may skip the fetch of a
+ * sample whose value provably cannot exceed the ray's current m — by the maximum of the sample's ESL block (NEAREST) or of the 3x3x3
+ * blocks around it (TRILINEAR: a sample's cell can lie one voxel outside its block), in the block grid vr_hip_volume_minmax reports for
+ * the resident volume (params.esl_block_* and the ESL bits of vr_hip_set_transfer_fn are not used) — and may stop a ray whose m has
+ * reached the maximum of the volume.  Only fetches are skipped; kx += ray_step runs for every sample up to the point where the ray
+ * stops, so images with esl on and off are identical byte for byte.  The block maxima are derived on the device from the min/max scan
+ * by the first such frame after a set_volume* / generate_volume and kept until the next; vr_hip_release_linear_copy derives them
+ * before it frees the array they are scanned from.
+ * Return values, NULL conventions and VR_ERR_NOT_READY as for vr_hip_render / vr_hip_render_device (the transfer function must be set);
+ * the brick copy a frame reads (voxel bricks for NEAREST, quad or oct bricks for TRILINEAR, the linear array under VR_LAYOUT_LINEAR) is
+ * built on first use; vr_hip_set_wide_addressing and vr_hip_set_tile_mapping apply; frames are counted by vr_hip_timing and described
+ * by vr_hip_last_launch.  vr_hip_render_mip is one launch and one copy to the host. */
+int vr_hip_render_mip(vr_ctx *ctx, const vr_params *params, uint8_t *host_rgba);
+int vr_hip_render_mip_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

@@ -109,6 +109,8 @@ def lib():
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
         "vr_hip_render": (C.c_int, [vp, P(VrParams), vp]),
         "vr_hip_render_device": (C.c_int, [vp, P(VrParams), vp, vp]),
+        "vr_hip_render_mip": (C.c_int, [vp, P(VrParams), vp]),
+        "vr_hip_render_mip_device": (C.c_int, [vp, P(VrParams), vp, vp]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

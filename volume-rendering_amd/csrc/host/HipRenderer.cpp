@@ -32,14 +32,14 @@ void HipRenderer::to_params(const Raycaster &r, vr_sampling sampling, vr_params 
 }
 
 HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), mirror_error_(nullptr) {
 	create_status_ = vr_hip_create(device, &ctx_);
 	if (create_status_ == 0)
 		prime(r);
 }
 
 HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), mirror_error_(nullptr) {
 	create_status_ = vr_hip_multi_create(n_devices, devices, &multi_);
 	if (create_status_ == 0)
 		prime(r);
@@ -61,6 +61,8 @@ HipRenderer::~HipRenderer() {
 }
 
 const char *HipRenderer::last_error() const {
+	if (mirror_error_ != nullptr)
+		return mirror_error_;
 	if (multi_ != nullptr)
 		return vr_hip_multi_last_error(multi_);
 	if (ctx_ == nullptr)
@@ -96,7 +98,13 @@ int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 	vr_params p;
 	to_params(r, sampling_, &p);
 	int rc;
-	if (multi_) rc = device_buffer_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_multi_render(multi_, &p, (uint8_t *) buffer);
+	mirror_error_ = nullptr;
+	if (mip_ && multi_) {
+		mirror_error_ = "the maximum-intensity projection renders on a single device (vr_hip_render_mip): construct the renderer without a device list";
+		return 1;
+	}
+	if (mip_) rc = device_buffer_ ? vr_hip_render_mip_device(ctx_, &p, buffer, nullptr) : vr_hip_render_mip(ctx_, &p, (uint8_t *) buffer);
+	else if (multi_) rc = device_buffer_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_multi_render(multi_, &p, (uint8_t *) buffer);
 	else rc = device_buffer_ ? vr_hip_render_device(ctx_, &p, buffer, nullptr) : vr_hip_render(ctx_, &p, (uint8_t *) buffer);
 	return rc == 0 ? 0 : 1;
 }

@@ -85,6 +85,10 @@ class HipRenderer : public Renderer {
 		vr_ctx *context() { return multi_ ? vr_hip_multi_context(multi_, 0) : ctx_; }
 		vr_multi *multi() { return multi_; }
 		void set_sampling(vr_sampling s) { sampling_ = s; }
+		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
+		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
+		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
+		void set_mip(bool mip) { mip_ = mip; }
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:
@@ -96,6 +100,8 @@ class HipRenderer : public Renderer {
 		int create_status_;
 		vr_sampling sampling_;
 		bool device_buffer_;
+		bool mip_;
+		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
 };
 
 }  // namespace volr

@@ -3,7 +3,7 @@
 // summary table (VolR.cpp:200-223) and, for eyeballing, a PPM writer for single frames.  There is no interactive mode.
 //
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
-//              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-o <frame.ppm>]
+//              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +38,7 @@ void print_usage() {
 	       "  -r <id> : renderer, 0 = HIP nearest (CPURenderer semantics), 1 = HIP trilinear (GPURenderer4 semantics)\n"
 	       "  -s <width> <height> : viewport, 128..2048 like the reference\n  -d <device> : GPU index\n"
 	       "  -devices <a,b,...> : split every frame over these GPUs (interleaved bands gathered on the first one over xGMI)\n"
+	       "  -mip : maximum-intensity projection instead of the composite (single device)\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -237,7 +238,7 @@ int write_ppm(const char *path) {
 
 int main(int argc, char **argv) {
 	std::string file_name, out_ppm;
-	bool benchmark_mode = false, persp = false, have_pose = false;
+	bool benchmark_mode = false, persp = false, have_pose = false, mip = false;
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
 	ViewBase::reset();
 	for (int i = 1; i < argc; i++) {
@@ -274,6 +275,7 @@ int main(int argc, char **argv) {
 		}
 		else if (strcmp(arg, "-bg") == 0 || strcmp(arg, "-b") == 0) benchmark_mode = true;
 		else if (strcmp(arg, "-persp") == 0) persp = true;
+		else if (strcmp(arg, "-mip") == 0) mip = true;
 		else if (strcmp(arg, "-pose") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) pose[k] = (float) atof(argv[++i]); have_pose = true; } }
 		else if (strcmp(arg, "-o") == 0) { if (need(1)) out_ppm = argv[++i]; }
 		else printf("Warning: unknown argument: %s\n", arg);
@@ -299,6 +301,11 @@ int main(int argc, char **argv) {
 	}
 	for (int i = 0; i < PROFILER_RENDERERS; i++)
 		if (!renderers[i]->ok()) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }
+	if (mip) {
+		if (!device_list.empty()) { printf("Error: -mip renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		for (int i = 0; i < PROFILER_RENDERERS; i++) renderers[i]->set_mip(true);
+		printf("Maximum-intensity projection\n");
+	}
 
 	int rc = EXIT_SUCCESS;
 	if (benchmark_mode) {

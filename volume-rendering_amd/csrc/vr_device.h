@@ -313,6 +313,22 @@ hipError_t launch_tile_choice(const uint32_t *cost_z, const uint32_t *cost_y, ui
 hipError_t launch_minmax(const void *volume, uint32_t bytes_per_voxel, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z,
                          uint32_t esl_block_dims, uint8_t *minmax_dev /* 32768 x {min,max} */, hipStream_t stream);
 
+// ---- maximum-intensity projection (include/vr_hip.h vr_hip_render_mip) ----
+// The bounds a MIP frame skips fetches by, derived from the min/max scan: kMipBoundEntries bytes for NEAREST (entry = the block's
+// maximum), the same again for TRILINEAR (entry = the maximum over the 3x3x3 neighbouring blocks: a sample's cell may lie one voxel
+// outside its block on each side), then one 32-bit word, the volume's maximum.  Entry index z*1024 + y*32 + x like the scan; 2-byte
+// volumes hold the HIGH byte everywhere (the kernel pads it with 0xff: rounding a bound up only loses skips).  The probe build
+// (`make EXTRA=-DVR_MIP_STATS`, scripts/mip_probe.py; not the product) keeps two 64-bit counters behind them, at kMipStatsAt: samples
+// of the frames that skipped, and fetches they issued.
+constexpr uint32_t kMipBoundEntries = VR_ESL_VOLUME_DIMS * VR_ESL_VOLUME_DIMS * VR_ESL_VOLUME_DIMS;
+constexpr uint32_t kMipStatsAt = 2u * kMipBoundEntries + 16u, kMipBoundBytes = kMipStatsAt + 16u;
+hipError_t launch_mip_bounds(const uint8_t *minmax_dev /* launch_minmax */, uint8_t *bounds_dev /* kMipBoundBytes */, hipStream_t stream);
+// One MIP frame.  `a` as for launch_raymarch with layout one of kLayoutLinear / kLayoutBricked / kLayoutVoxel / kLayoutOct (what
+// plan_raymarch answers for `a` holds for this launch too: same selector, same tile grid); a.p.esl != 0 = skip and stop by `bounds`
+// (then not NULL) with the block grid of a.esl_div_*, which the caller takes from the VOLUME (vr_hip_volume_minmax), not from a.p.
+hipError_t launch_mip(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                      const uint8_t *bounds, void *out_rgba, hipStream_t stream);
+
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);
 

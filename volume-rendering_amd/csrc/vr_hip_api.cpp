@@ -93,6 +93,11 @@ struct vr_ctx {
 	bool oct_always = false;                // vr_hip_set_brick_plane(5): 2-byte voxels read the oct bricks for every view (testing)
 	// feeders scratch
 	uint8_t *minmax = nullptr; unsigned long long *hist = nullptr;
+	// maximum-intensity projection: the bounds its frames skip fetches by (vr_device.h kMipBoundBytes), built from the min/max scan by the
+	// first frame that skips, kept until the volume changes; and the tile mappings chosen for its last few views
+	uint8_t *mip_bounds = nullptr; bool mip_bounds_ready = false;
+	struct MipMap { vr_params p; uint32_t dim[3], layout, brick_plane, lane_map, phase_x, phase_y, straddle_permille; };
+	MipMap mip_map[16]; uint32_t mip_mapped = 0, mip_map_next = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -349,8 +354,8 @@ void dual_choice_bits(RayKernelArgs &a, const RaymarchPlan &plan, bool default_a
 	a.dual_analytic = 1u; a.dual_shift = shift;
 }
 
-int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
-	RayKernelArgs a;
+// the part of the kernel argument that only restates the frame parameters and the geometry of the resident volume
+void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 	memset(&a, 0, sizeof a);
 	a.p = *p;
 	a.dim_x = c->dim[0]; a.dim_y = c->dim[1]; a.dim_z = c->dim[2];
@@ -362,6 +367,68 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	a.tf_scale = c->bpv == 1 ? (float) VR_TF_SIZE / 255.0f : (float) VR_TF_SIZE / 65535.0f;
 	a.kd_scaled = p->light_kd * (c->bpv == 1 ? (1.0f / 255.0f) : (1.0f / 65535.0f));
 	a.tf_zero_below = c->tf_zero_below;
+	a.nbx = (c->dim[0] + kBrickEdge - 1) / kBrickEdge; a.nby = (c->dim[1] + kBrickEdge - 1) / kBrickEdge;
+	a.nbz = (c->dim[2] + kBrickEdge - 1) / kBrickEdge;
+}
+
+// index / block edge of the ESL grid, prepared as shift or multiply-high (RaycasterBase.h:59-63)
+void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
+	const uint32_t bd = block_dims ? block_dims : 1u;
+	if ((bd & (bd - 1)) == 0) { a.esl_div_magic = 0; a.esl_div_shift = (uint32_t) __builtin_ctz(bd); }
+	else { a.esl_div_magic = (uint32_t) ((1ull << 32) / bd + 1); a.esl_div_shift = 0; }
+}
+
+// the event pair and the sequence number of the frame about to be launched (only blocks if kEventRing launches are still in flight)
+EventPair &next_frame_events(vr_ctx *c, uint64_t &frame_seq) {
+	EventPair &ev = c->ring[c->ring_head];
+	frame_seq = c->seq_next++;
+	c->ring_seq[c->ring_head] = frame_seq;
+	c->ring_head = (c->ring_head + 1) % kEventRing;
+	harvest(c, ev);
+	return ev;
+}
+
+#ifdef VR_BOUNDS_CHECK
+// debug build: what the frame's gathers must stay inside, and where the first violation is recorded
+hipError_t bounds_check_arm(vr_ctx *c, RayKernelArgs &a, const vr_params *p, const RaymarchPlan &plan, const void *brick_copy, uint32_t ntiles) {
+	if (c->bc_fault == nullptr) {
+		hipError_t e = hipMalloc((void **) &c->bc_fault, 8 * sizeof(uint32_t));
+		if (e == hipSuccess) e = hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t));
+		if (e != hipSuccess) return e;
+	}
+	const void *array = plan.reads_linear ? c->vol : brick_copy;
+	const bool column = a.layout == kLayoutColumn || a.layout == kLayoutVoxCol;
+	a.bc_base = (uint64_t) (uintptr_t) array - (column ? kColPadBytes : 0u);
+	a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
+	             copy_bytes(c, a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
+	                           a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane);
+	if (column) a.bc_bytes += 2ull * kColPadBytes;
+	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, kCopyRunY) : 0;
+	a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
+	// self-test of the net itself: VR_BC_SELFTEST=1 halves the size the checks hold the gathers against — a full-march frame must then fail
+	if (const char *e = getenv("VR_BC_SELFTEST")) if (atoi(e) == 1) a.bc_bytes /= 2;
+	return hipSuccess;
+}
+
+// ... and what the frame recorded: waits for it
+int bounds_check_verdict(vr_ctx *c, hipStream_t stream, uint32_t layout) {
+	uint32_t fault[6] = { 0, 0, 0, 0, 0, 0 };
+	VR_TRY(c, hipStreamSynchronize(stream));
+	VR_TRY(c, hipMemcpy(fault, c->bc_fault, sizeof fault, hipMemcpyDeviceToHost));
+	if (fault[0] != 0u) {
+		char msg[256];
+		snprintf(msg, sizeof msg, "bounds check: code %u (1 table index [axis << 8], 2 offset, 3 address, 4 cost slot) workgroup %u thread %u value 0x%08x%08x limit %u, layout %u",
+		         fault[0], fault[1], fault[2], fault[4], fault[3], fault[5], layout);
+		(void) hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t));
+		return fail(c, VR_ERR_HIP, msg);
+	}
+	return VR_OK;
+}
+#endif
+
+int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	RayKernelArgs a;
+	volume_args(c, p, a);
 	{   // largest power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below: raw < P implies a transparent sample
 		uint32_t below = 0;
 		const uint32_t top = c->bpv == 1 ? 256u : 65536u;
@@ -459,13 +526,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			if ((std::fabs(p->view.right_plane[ax]) + std::fabs(p->view.up_plane[ax])) * half[ax] > 1.0f) dense = false;
 		if (dense || c->oct_always) a.layout = kLayoutOct;
 	}
-	a.nbx = (c->dim[0] + kBrickEdge - 1) / kBrickEdge; a.nby = (c->dim[1] + kBrickEdge - 1) / kBrickEdge;
-	a.nbz = (c->dim[2] + kBrickEdge - 1) / kBrickEdge;
-	{   // RaycasterBase.h:59-63: index / esl_block_dims, prepared as shift or multiply-high
-		const uint32_t bd = p->esl_block_dims ? p->esl_block_dims : 1u;
-		if ((bd & (bd - 1)) == 0) { a.esl_div_magic = 0; a.esl_div_shift = (uint32_t) __builtin_ctz(bd); }
-		else { a.esl_div_magic = (uint32_t) ((1ull << 32) / bd + 1); a.esl_div_shift = 0; }
-	}
+	esl_divisor(a, p->esl_block_dims);
 
 	vr_ctx::MapEntry *hit = nullptr;
 	if (c->tile_lane_map >= 0) { a.lane_map = (uint32_t) c->tile_lane_map; a.phase_x = c->tile_phase_x; a.phase_y = c->tile_phase_y; }
@@ -760,43 +821,16 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	                                 a.layout == kLayoutVoxCol ? 1u : 0u };
 
 #ifdef VR_BOUNDS_CHECK
-	{   // debug build: what the frame's gathers must stay inside, and where the first violation is recorded
-		if (c->bc_fault == nullptr) { VR_TRY(c, hipMalloc((void **) &c->bc_fault, 8 * sizeof(uint32_t))); VR_TRY(c, hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t))); }
-		const void *array = plan.reads_linear ? c->vol : brick_copy;
-		const bool column = a.layout == kLayoutColumn || a.layout == kLayoutVoxCol;
-		a.bc_base = (uint64_t) (uintptr_t) array - (column ? kColPadBytes : 0u);
-		a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
-		             copy_bytes(c, a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
-		                           a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane);
-		if (column) a.bc_bytes += 2ull * kColPadBytes;
-		a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, kCopyRunY) : 0;
-		a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
-		// self-test of the net itself: VR_BC_SELFTEST=1 halves the size the checks hold the gathers against — a full-march frame must then fail
-		if (const char *e = getenv("VR_BC_SELFTEST")) if (atoi(e) == 1) a.bc_bytes /= 2;
-	}
+	VR_TRY(c, bounds_check_arm(c, a, p, plan, brick_copy, ntiles));
 #endif
-	EventPair &ev = c->ring[c->ring_head];
-	const uint64_t frame_seq = c->seq_next++;
-	c->ring_seq[c->ring_head] = frame_seq;
-	c->ring_head = (c->ring_head + 1) % kEventRing;
-	harvest(c, ev);                              // only blocks if 256 launches are still in flight
+	uint64_t frame_seq = 0;
+	EventPair &ev = next_frame_events(c, frame_seq);
 	VR_TRY(c, hipEventRecord(ev.start, stream));
 	VR_TRY(c, launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream));
 	VR_TRY(c, hipEventRecord(ev.stop, stream));
 	ev.pending = true;
 #ifdef VR_BOUNDS_CHECK
-	{
-		uint32_t fault[6] = { 0, 0, 0, 0, 0, 0 };
-		VR_TRY(c, hipStreamSynchronize(stream));
-		VR_TRY(c, hipMemcpy(fault, c->bc_fault, sizeof fault, hipMemcpyDeviceToHost));
-		if (fault[0] != 0u) {
-			char msg[256];
-			snprintf(msg, sizeof msg, "bounds check: code %u (1 table index [axis << 8], 2 offset, 3 address, 4 cost slot) workgroup %u thread %u value 0x%08x%08x limit %u, layout %u",
-			         fault[0], fault[1], fault[2], fault[4], fault[3], fault[5], a.layout);
-			(void) hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t));
-			return fail(c, VR_ERR_HIP, msg);
-		}
-	}
+	{ const int bc = bounds_check_verdict(c, stream, a.layout); if (bc) return bc; }
 #endif
 	if (dual_advance) {                          // behind the frame, on its stream
 		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
@@ -917,12 +951,123 @@ int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	if (c->vol) { (void) hipFree(c->vol); c->vol = nullptr; }
 	free_bricks(c);
 	c->map_cached = 0; c->map_next = 0;          // cached tile mappings belong to the previous volume
+	c->mip_mapped = 0; c->mip_map_next = 0; c->mip_bounds_ready = false;       // ... and so do the block maxima of the MIP frames
 	c->dim[0] = c->dim[1] = c->dim[2] = 0;
 	const uint64_t elems = (uint64_t) x * y * z;
 	const uint64_t slack = volume_tail_slack(x, y);
 	VR_TRY(c, hipMalloc(&c->vol, (elems + slack) * bpv));
 	VR_TRY(c, hipMemsetAsync((uint8_t *) c->vol + elems * bpv, 0, slack * bpv, c->stream));
 	c->vol_elems = elems; c->dim[0] = x; c->dim[1] = y; c->dim[2] = z; c->bpv = bpv;
+	return VR_OK;
+}
+
+// voxels per edge of an ESL block of the resident volume (RaycasterBase.cpp:97-99)
+uint32_t volume_block_dims(const vr_ctx *c) {
+	const uint32_t bd = (max_dim_of(c) + VR_ESL_VOLUME_DIMS - 1) / VR_ESL_VOLUME_DIMS;
+	return bd < VR_ESL_MIN_BLOCK ? VR_ESL_MIN_BLOCK : bd;
+}
+
+// The bounds a MIP frame skips by (vr_device.h): the min/max scan of the linear array and the small kernel behind it, on the
+// context's stream, synchronous like a brick copy's first use.  Kept until the volume changes.
+int build_mip_bounds(vr_ctx *c) {
+	if (c->mip_bounds_ready) return VR_OK;
+	if (c->vol == nullptr)
+		return fail(c, VR_ERR_NOT_READY, "the block maxima of a MIP frame with esl on are built from the linear array, which was released before the first such frame");
+	if (c->mip_bounds == nullptr) VR_TRY(c, hipMalloc((void **) &c->mip_bounds, kMipBoundBytes));
+	VR_TRY(c, launch_minmax(c->vol, c->bpv, c->dim[0], c->dim[1], c->dim[2], volume_block_dims(c), c->minmax, c->stream));
+	VR_TRY(c, launch_mip_bounds(c->minmax, c->mip_bounds, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	c->mip_bounds_ready = true;
+	return VR_OK;
+}
+
+// One MIP frame (include/vr_hip.h vr_hip_render_mip): the copy it reads — voxel bricks for NEAREST, quad bricks of the plane across the
+// view (oct bricks for 2-byte voxels where a DVR frame takes them) for TRILINEAR, the linear array under VR_LAYOUT_LINEAR —, the tile
+// mapping of a DVR frame of the same view, one launch, one event pair.
+int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	RayKernelArgs a;
+	volume_args(c, p, a);
+	a.force_wide = c->force_wide;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, nearest = p->sampling == VR_SAMPLE_NEAREST;
+	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
+	a.brick_plane = kPlaneXY;
+	if (bricked && nearest && copy_possible(c, kCopyVoxel) && c->force_wide != 1 && !(c->brick_plane_force >= 0 && c->brick_plane_force < (int32_t) kPlanes))
+		a.layout = kLayoutVoxel;
+	if (bricked && !nearest && !c->force_wide) {
+		uint32_t plane = kPlaneXY;
+		if (c->brick_plane_force >= 0 && c->brick_plane_force < (int32_t) kPlanes) plane = (uint32_t) c->brick_plane_force;
+		else if (c->brick_plane_force < 0) {             // along a volume axis: the chunk plane across it (launch_frame)
+			const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y), dz = std::fabs(p->view.direction[2] * a.half_z);
+			if (std::fmax(dx, std::fmax(dy, dz)) > 0.98f * std::sqrt(dx * dx + dy * dy + dz * dz)) plane = dz >= dx && dz >= dy ? kPlaneXY : (dy >= dx ? kPlaneXZ : kPlaneYZ);
+		}
+		if (copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
+	}
+	if (bricked && !nearest && c->bpv == 2 && copy_possible(c, kCopyOct) && c->brick_plane_force < 0 && c->force_wide != 1 && (!p->view.perspective || c->oct_always)) {
+		bool dense = true;               // at most one cell per pixel (launch_frame)
+		const float half[3] = { a.half_x, a.half_y, a.half_z };
+		for (int ax = 0; ax < 3; ax++)
+			if ((std::fabs(p->view.right_plane[ax]) + std::fabs(p->view.up_plane[ax])) * half[ax] > 1.0f) dense = false;
+		if (dense || c->oct_always) a.layout = kLayoutOct;
+	}
+	const void *brick_copy = nullptr;
+	if (a.layout != kLayoutLinear) {
+		brick_copy = copy_for(c, a.layout == kLayoutVoxel ? kCopyVoxel : a.layout == kLayoutOct ? kCopyOct : kCopyQuadXY + a.brick_plane);
+		if (brick_copy == nullptr) {                     // refused or not buildable any more: the first quad copy, then whatever is resident
+			a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
+			brick_copy = copy_for(c, kCopyQuadXY);
+		}
+		if (brick_copy == nullptr) {
+			if (nearest && c->copy[kCopyVoxel] && c->force_wide != 1) { a.layout = kLayoutVoxel; brick_copy = c->copy[kCopyVoxel]; }
+			else if (!nearest && c->bpv == 2 && c->force_wide != 1 && c->copy[kCopyOct]) { a.layout = kLayoutOct; brick_copy = c->copy[kCopyOct]; }
+			else a.layout = kLayoutLinear;
+		}
+	}
+	// Skipping and stopping by block maxima.  The grid is the volume's own (vr_hip_volume_minmax), whatever params.esl_block_* say.  Not
+	// for views so far away that fp32 sample coordinates are not exact to a small fraction of a cell (the condition under which DVR
+	// frames clamp every fetch, launch_frame): the TRILINEAR bound covers one voxel around the block of the sample's position.
+	esl_divisor(a, volume_block_dims(c));
+	if (p->esl) {
+		const float omax = std::fmax(std::fabs(p->view.origin[0]), std::fmax(std::fabs(p->view.origin[1]), std::fabs(p->view.origin[2])));
+		if (!((1.0f + 2.0f * omax) * (float) max_dim_of(c) < 1048576.0f)) a.p.esl = 0u;
+	}
+	if (a.p.esl) { const int rc = build_mip_bounds(c); if (rc) return rc; }
+
+	uint32_t straddle = 1000u;
+	if (c->tile_lane_map >= 0) { a.lane_map = (uint32_t) c->tile_lane_map; a.phase_x = c->tile_phase_x; a.phase_y = c->tile_phase_y; }
+	else {
+		vr_ctx::MipMap *hit = nullptr;
+		for (uint32_t i = 0; i < c->mip_mapped && hit == nullptr; i++) {
+			vr_ctx::MipMap &e = c->mip_map[i];
+			if (memcmp(&e.p, p, sizeof *p) == 0 && memcmp(e.dim, c->dim, sizeof c->dim) == 0 && e.layout == a.layout && e.brick_plane == a.brick_plane) hit = &e;
+		}
+		if (hit == nullptr) {
+			constexpr uint32_t kMaps = sizeof c->mip_map / sizeof c->mip_map[0];
+			hit = &c->mip_map[c->mip_map_next];
+			c->mip_map_next = (c->mip_map_next + 1) % kMaps;
+			if (c->mip_mapped < kMaps) c->mip_mapped++;
+			hit->straddle_permille = choose_tile_mapping(a);
+			hit->p = *p; memcpy(hit->dim, c->dim, sizeof c->dim); hit->layout = a.layout; hit->brick_plane = a.brick_plane;
+			hit->lane_map = a.lane_map; hit->phase_x = a.phase_x; hit->phase_y = a.phase_y;
+		}
+		a.lane_map = hit->lane_map; a.phase_x = hit->phase_x; a.phase_y = hit->phase_y; straddle = hit->straddle_permille;
+	}
+	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
+	if (plan.reads_linear && c->vol == nullptr)
+		return fail(c, VR_ERR_NOT_READY, "this MIP frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
+		                                 "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again");
+	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u };
+#ifdef VR_BOUNDS_CHECK
+	VR_TRY(c, bounds_check_arm(c, a, p, plan, brick_copy, plan.tiles_x * plan.tiles_y));
+#endif
+	uint64_t frame_seq = 0;
+	EventPair &ev = next_frame_events(c, frame_seq);
+	VR_TRY(c, hipEventRecord(ev.start, stream));
+	VR_TRY(c, launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, a.p.esl ? c->mip_bounds : nullptr, dev_rgba, stream));
+	VR_TRY(c, hipEventRecord(ev.stop, stream));
+	ev.pending = true;
+#ifdef VR_BOUNDS_CHECK
+	{ const int bc = bounds_check_verdict(c, stream, a.layout); if (bc) return bc; }
+#endif
 	return VR_OK;
 }
 
@@ -986,6 +1131,7 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->vol) (void) hipFree(c->vol);
 	free_bricks(c);
 	if (c->minmax) (void) hipFree(c->minmax);
+	if (c->mip_bounds) (void) hipFree(c->mip_bounds);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
 	if (c->stream) (void) hipStreamDestroy(c->stream);
@@ -1211,6 +1357,52 @@ int vr_hip_render(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 	return VR_OK;
 }
 
+int vr_hip_render_mip_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (dev_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");
+	int rc = validate_params(c, p);
+	if (rc) return rc;
+	rc = ready(c);
+	if (rc) return rc;
+	VR_TRY(c, hipSetDevice(c->device));
+	return launch_mip_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_mip(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (host_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");
+	int rc = validate_params(c, p);
+	if (rc) return rc;
+	rc = ready(c);
+	if (rc) return rc;
+	const size_t bytes = (size_t) p->out_width * p->out_rows * 4;
+	if (c->fb == nullptr || bytes > c->fb_bytes)
+		return fail(c, VR_ERR_NOT_READY, "output larger than the window buffer: call vr_hip_set_window first");
+	VR_TRY(c, hipSetDevice(c->device));
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_mip_frame(c, p, c->fb, c->stream);
+	if (rc) return rc;
+	VR_TRY(c, hipMemcpyAsync(host_rgba, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	c->last_total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if (c->last_total_ms > c->total_ms_max) c->total_ms_max = c->last_total_ms;
+	return VR_OK;
+}
+
+#ifdef VR_MIP_STATS
+// probe build only (scripts/mip_probe.py): { samples, fetches issued } of the MIP frames that skipped since the last call
+int vr_hip_debug_mip_stats(vr_ctx *c, uint64_t *out2) {
+	if (c == nullptr || out2 == nullptr) return VR_ERR_INVALID;
+	out2[0] = out2[1] = 0;
+	if (!c->mip_bounds_ready) return VR_OK;
+	VR_TRY(c, hipSetDevice(c->device));
+	VR_TRY(c, drain(c));
+	VR_TRY(c, hipMemcpy(out2, c->mip_bounds + kMipStatsAt, 16, hipMemcpyDeviceToHost));
+	VR_TRY(c, hipMemset(c->mip_bounds + kMipStatsAt, 0, 16));
+	return VR_OK;
+}
+#endif
+
 int vr_hip_timing(vr_ctx *c, vr_timing *out) {
 	if (c == nullptr || out == nullptr) return VR_ERR_INVALID;
 	(void) hipSetDevice(c->device);
@@ -1238,11 +1430,7 @@ int vr_hip_volume_minmax(vr_ctx *c, uint8_t *minmax_out, uint32_t *bd_out, float
 	if (minmax_out == nullptr) return fail(c, VR_ERR_INVALID, "minmax_out is NULL");
 	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, c->dim[0] ? "the linear copy was released (vr_hip_release_linear_copy): set the volume again" : "minmax before set_volume");
 	VR_TRY(c, hipSetDevice(c->device));
-	// RaycasterBase.cpp:97-99
-	uint32_t max_dim = c->dim[0] > c->dim[1] ? c->dim[0] : c->dim[1];
-	if (c->dim[2] > max_dim) max_dim = c->dim[2];
-	uint32_t bd = (max_dim + VR_ESL_VOLUME_DIMS - 1) / VR_ESL_VOLUME_DIMS;
-	if (bd < VR_ESL_MIN_BLOCK) bd = VR_ESL_MIN_BLOCK;
+	const uint32_t bd = volume_block_dims(c);
 	VR_TRY(c, hipEventRecord(c->aux_start, c->stream));
 	VR_TRY(c, launch_minmax(c->vol, c->bpv, c->dim[0], c->dim[1], c->dim[2], bd, c->minmax, c->stream));
 	VR_TRY(c, hipEventRecord(c->aux_stop, c->stream));
@@ -1365,6 +1553,8 @@ int vr_hip_release_linear_copy(vr_ctx *c) {
 		return fail(c, VR_ERR_INVALID, "the index-arithmetic path (vr_hip_set_wide_addressing 1) reads the linear array");
 	VR_TRY(c, hipSetDevice(c->device));
 	VR_TRY(c, drain(c));
+	const int rc = build_mip_bounds(c);          // MIP frames with esl on need the scan of the linear array: taken now (64 KiB)
+	if (rc) return rc;
 	(void) hipFree(c->vol);
 	c->vol = nullptr;
 	return VR_OK;

@@ -2087,6 +2087,298 @@ void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, 
 	col_store(ray, acc);
 }
 
+// ---- maximum-intensity projection (vr_hip_render_mip) ---------------------------------------------------------
+//
+// Per pixel: the ray of raymarch_kernel (get_ray, intersect), the sample sequence of its march with leaping off — k starts at kx, is
+// accumulated by repeated addition of ray_step, every position is formed from k — and instead of a composite the running MAXIMUM m
+// of the raw samples: NEAREST the integer voxel of Model::sample_data's unfused arithmetic, TRILINEAR the interpolated raw value
+// (coordinates fma(k, A, B), the lerps of tri_resolve, Q8 weights rounded), m starting at 0.  The pixel is write_color of ONE
+// transfer-function lookup of m (NEAREST transfer_fn[s8 / TF_RATIO], TRILINEAR the filtered lookup of a DVR sample), read from
+// global memory once per ray: no table of it in LDS, no shading, no composite, no termination threshold.
+//
+// A sample is the march and the fetch.  kMipBatch samples are issued back to back before the first of them is consumed, so their
+// gathers are in flight together (compiler-scheduled waits; every fetch clamps its cell like the reference, so any lane's address
+// is in bounds whatever its k).  A lane fetches only while it is live AND needs the sample; a sample no lane needs issues nothing;
+// the wave leaves when no lane is live.
+//
+// Exact acceleration (a.p.esl != 0).  m only grows, so a sample whose value cannot exceed m changes nothing:
+//  * skipping: the bound of a sample is read from LDS by its ESL block index (block_index of the sample position: the grid of the
+//    min/max scan).  NEAREST: the sample IS a voxel of that block, the bound is the block's maximum.  TRILINEAR: with v the voxel index
+//    block_index forms per axis, the cell of the sample is floor(v - 1/2 +- rounding), i.e. v - 1 or v, its neighbour one more: the
+//    eight corners lie within one voxel of the block, inside the 3x3x3 neighbouring blocks (edge >= 8 voxels) whose maximum is the
+//    bound (the host keeps the frame out of this path when fp32 coordinates are not exact to a fraction of a cell: far-away views).
+//    A lerp fma(t, b - a, a) with 0 <= t < 1 never leaves [min(a, b), max(a, b)], rounding included, so the interpolated value obeys
+//    the bound too.  Q8 weights can round to exactly 1: the first two lerp levels are then still exact (1-byte voxels: all three —
+//    every operand has at most 24 significant bits), the third may end one ulp above its larger operand for 2-byte voxels, which is
+//    why that case compares against the next multiple of 256 (2-byte bounds are high bytes, padded with 0xff otherwise);
+//  * stopping: once m has reached the volume's maximum the ray is finished (same bound, same argument).
+// Both only skip fetches: k is advanced for every sample up to the point where the ray stops, so the image does not depend on them.
+#ifndef VR_MIP_BATCH
+#define VR_MIP_BATCH 4
+#endif
+constexpr int kMipBatch = VR_MIP_BATCH;
+extern __shared__ __attribute__((aligned(16))) uint8_t mip_bound_lds[];      // kMipBoundEntries bytes of dynamic LDS, only for frames that skip
+
+// the address tables of the quad / voxel / oct bricks into LDS, as raymarch_kernel stages them for these layouts; no barrier
+template <int BPV, int ADDR, int LAYOUT>
+__device__ __forceinline__ void stage_brick_tables(const RayKernelArgs &a, uint32_t *lut) {
+	typedef LutCfg<ADDR> L;
+	constexpr uint32_t kThreads = L::threads;
+	const uint32_t t = threadIdx.x;
+	auto cell_of = [](uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); };
+	const uint32_t nx = a.dim_x, ny = a.dim_y, nz = a.dim_z;
+	const uint32_t elem = LAYOUT == kLayoutVoxel ? BPV : (LAYOUT == kLayoutOct ? 8u * BPV : 4u * BPV);
+#ifdef VR_BOUNDS_CHECK
+	if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = ny + 2 * kLutPad; bc_table_entries[2] = nz + 2 * kLutPad; }
+#endif
+	const uint32_t row = a.nbx * kBrickPitch;
+	const uint64_t slab = (uint64_t) a.nby * row;
+	for (uint32_t jj = t; jj < nz + 2 * kLutPad; jj += kThreads) {
+		const uint32_t i = cell_of(jj, nz);
+		const uint32_t j = i + 1 < nz ? i + 1 : i;
+		const uint64_t z0 = ((i >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, i & 7u)) * elem;
+		const uint64_t z1 = ((j >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, j & 7u)) * elem;
+		if (ADDR == kAddr32) {
+			lut[2 * jj] = (uint32_t) z0; lut[2 * jj + 1] = (uint32_t) z1;
+		} else {
+			lut[4 * jj] = (uint32_t) z0; lut[4 * jj + 1] = (uint32_t) (z0 >> 32);
+			lut[4 * jj + 2] = (uint32_t) z1; lut[4 * jj + 3] = (uint32_t) (z1 >> 32);
+		}
+	}
+	for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, nx); lut[L::x_at + j] = ((i >> 3) * kBrickPitch + brick_spread(BPV, a.brick_plane, 0, i & 7u)) * elem; }
+	for (uint32_t j = t; j < ny + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, ny); lut[L::y_at + j] = ((i >> 3) * row + brick_spread(BPV, a.brick_plane, 1, i & 7u)) * elem; }
+}
+
+template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
+__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
+void mip_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
+                uint32_t *__restrict__ out) {
+	typedef LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)> L;
+	constexpr uint32_t kThreads = L::threads;
+	constexpr bool kNearest = SAMPLING == VR_SAMPLE_NEAREST, kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;
+	__shared__ __attribute__((aligned(16))) uint32_t lut[L::words];
+	const bool skipping = a.p.esl != 0u;                            // wave-uniform: a kernel argument
+	uint32_t volume_max = 0u;
+	if constexpr (L::max_dim != 0) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);
+	if (skipping) {
+		// (32-bit copies: static LDS in front of the dynamic region may leave its base at any multiple of 4)
+		const uint32_t *src = (const uint32_t *) (bounds_g + (kNearest ? 0u : kMipBoundEntries));
+		uint32_t *dst = (uint32_t *) mip_bound_lds;
+		for (uint32_t i = threadIdx.x; i < kMipBoundEntries / 4u; i += kThreads) dst[i] = src[i];
+		volume_max = *(const uint32_t *) (bounds_g + 2u * kMipBoundEntries);
+	}
+	__syncthreads();
+
+	// -- workgroup -> tile -> pixel, as raymarch_kernel (tile = workgroup id: every ray of a MIP frame without skipping is a full march)
+	uint32_t tile_x, tile_y;
+	tile_to_xy(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint32_t qd = lane >> 4;
+	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;
+	const uint32_t order = a.lane_map & 3u, shape = kThreads == 512u ? (a.lane_map >> 2) : 0u;
+	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
+	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
+	uint32_t wx, wy, ox, oy;
+	if (shape == 1u) { wx = qd * 4u + gu; wy = gv; ox = (wave & 1u) * 16u; oy = (wave >> 1) * 4u; }
+	else if (shape == 2u) { wx = gu; wy = qd * 4u + gv; ox = wave * 4u; oy = 0u; }
+	else { wx = (qd & 1u) * 4u + gu; wy = (qd >> 1) * 4u + gv; ox = (wave & 3u) * 8u; oy = (wave >> 2) * 8u; }
+	const uint32_t lx = tile_x * 32u + ox + wx - a.phase_x;
+	const uint32_t ly = tile_y * (kThreads / 32u) + oy + wy - a.phase_y;
+	if (lx >= a.p.out_width || ly >= a.p.out_rows)
+		return;                                     // no barrier below this point
+	const uint32_t band = ly / a.p.band_rows;
+	const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
+	const uint32_t gx = a.p.x0 + lx;
+	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
+
+	// -- View::get_ray (ViewBase.h:23-35) and Raycaster::intersect, as raymarch_kernel
+	f3 origin, dir;
+	bool alive = gx < a.p.view.width && gy < a.p.view.height;
+	{
+		const f3 vo = ld3(a.p.view.origin), vd = ld3(a.p.view.direction);
+		const f3 vr_ = ld3(a.p.view.right_plane), vu = ld3(a.p.view.up_plane);
+		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u));
+		const float fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
+		if (a.p.view.perspective) {
+			origin = vo;
+			dir = mk3(vd.x + vr_.x * fx, vd.y + vr_.y * fx, vd.z + vr_.z * fx);
+			dir = mk3(dir.x + vu.x * fy, dir.y + vu.y * fy, dir.z + vu.z * fy);
+		} else {
+			dir = vd;
+			origin = mk3(vo.x + vr_.x * fx, vo.y + vr_.y * fx, vo.z + vr_.z * fx);
+			origin = mk3(origin.x + vu.x * fy, origin.y + vu.y * fy, origin.z + vu.z * fy);
+		}
+	}
+	float kx = 0, ky = 0;
+	alive = alive && intersect(origin, dir, kx, ky);
+	const float step = a.p.ray_step;
+	alive = alive && (ky + step > ky);              // the termination guard of raymarch_kernel
+	ky = flmin(ky, kx + step * (float) kMaxRaySteps);
+	const bool hit = alive;
+	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a segment: position 0, never live
+
+	// -- the march: kMipBatch samples issued, then consumed.  With skipping, `need` is decided against the m of the batch's start: a
+	//    smaller m only keeps a fetch that a later one would have made unnecessary.
+	float k = kx;
+	bool live = alive;
+#ifdef VR_MIP_STATS
+	uint32_t stat_samples = 0u, stat_fetches = 0u;
+#define VR_MIP_COUNT(is_live, is_needed) do { stat_samples += (is_live) ? 1u : 0u; stat_fetches += (is_needed) ? 1u : 0u; } while (0)
+#define VR_MIP_COUNT_REST() do { if (live && k <= ky) stat_samples += (uint32_t) ((ky - k) / step) + 1u; } while (0)      /* what a stopped ray leaves out (approximate) */
+#else
+#define VR_MIP_COUNT(is_live, is_needed) do { } while (0)
+#define VR_MIP_COUNT_REST() do { } while (0)
+#endif
+	f4 colour; colour.x = colour.y = colour.z = colour.w = 0.0f;
+	const f4 *tf4 = (const f4 *) tf_g;
+	auto bound_index = [&](f3 pos) { const BlockIdx b = block_index(a, pos); return (b.z * VR_ESL_VOLUME_DIMS + b.y) * VR_ESL_VOLUME_DIMS + b.x; };
+	// Two instantiations of each loop, like the clamp tags of raymarch_kernel.  Without skipping the batch is straight-line code: every
+	// lane fetches — a finished lane where its k stopped, the same cell again — and only the maximum looks at liveness.  With skipping a
+	// fetch sits behind the wave's vote and the lane's own need; what it loaded is consumed behind the same vote after the whole batch
+	// was issued, so the compiler cannot pull the consumer (and the wait in front of it) up to the load.
+	if constexpr (kNearest) {
+		auto widen = [](uint32_t high) { return BPV == 1 ? high : ((high << 8) | 0xffu); };
+		const uint32_t stop_at = widen(volume_max);
+		uint32_t m = 0u;
+		auto march = [&](auto skip_tag) {
+			constexpr bool kSkip = decltype(skip_tag)::value;
+			while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+				uint32_t word[kMipBatch];
+				uint64_t fetched[kMipBatch];
+				bool counts[kMipBatch];
+				#pragma unroll
+				for (int u = 0; u < kMipBatch; u++) {
+					const f3 pos = march_point<SAMPLING>(origin, dir, k);
+					counts[u] = live;
+					if constexpr (kSkip) {
+						const bool need = live && widen(mip_bound_lds[bound_index(pos)]) > m;
+						fetched[u] = __builtin_amdgcn_ballot_w64(need);
+						word[u] = 0u;
+						VR_MIP_COUNT(live, need);
+						if (fetched[u] != 0ull) {
+							if (need) word[u] = sample_nearest<BPV, ADDR, LAYOUT>(vol, a, lut, pos);
+						}
+						k += step;
+					} else {
+						fetched[u] = ~0ull;
+						word[u] = sample_nearest<BPV, ADDR, LAYOUT>(vol, a, lut, pos);
+						k += live ? step : 0.0f;
+					}
+					live = live && k <= ky;
+				}
+				__builtin_amdgcn_sched_barrier(0);
+				#pragma unroll
+				for (int u = 0; u < kMipBatch; u++) {
+					if (!kSkip || fetched[u] != 0ull) {     // (lanes that did not fetch hold 0)
+						uint32_t s = voxel_of<BPV, LAYOUT>(word[u]);
+						if (!kSkip) s = counts[u] ? s : 0u;
+						m = s > m ? s : m;
+					}
+				}
+				if (kSkip && m >= stop_at) { VR_MIP_COUNT_REST(); live = false; }
+			}
+		};
+		if (skipping) march(std::true_type()); else march(std::false_type());
+		colour = tf4[(BPV == 1 ? m : (m >> 8)) / VR_TF_RATIO];
+	} else {
+		const f3 A = mk3(dir.x * a.half_x, dir.y * a.half_y, dir.z * a.half_z);
+		const f3 B = mk3(VR_FMA(origin.x, a.half_x, a.off_x), VR_FMA(origin.y, a.half_y, a.off_y), VR_FMA(origin.z, a.half_z, a.off_z));
+		auto widen = [](uint32_t high) { return BPV == 1 ? (float) high : (kQ8 ? (float) ((high + 1u) << 8) : (float) ((high << 8) | 0xffu)); };
+		const float stop_at = widen(volume_max);
+		float m = 0.0f;
+		auto march = [&](auto skip_tag) {
+			constexpr bool kSkip = decltype(skip_tag)::value;
+			while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+				TriFetch<BPV, LAYOUT> f[kMipBatch];
+				float ks[kMipBatch];
+				uint64_t fetched[kMipBatch];
+				bool counts[kMipBatch];
+				#pragma unroll
+				for (int u = 0; u < kMipBatch; u++) {
+					ks[u] = k;
+					counts[u] = live;
+					if constexpr (kSkip) {
+						const bool need = live && widen(mip_bound_lds[bound_index(march_point<SAMPLING>(origin, dir, k))]) > m;
+						f[u].w0 = f[u].w1 = f[u].w2 = f[u].w3 = 0u; f[u].q = 0ull; f[u].q2 = 0ull; f[u].o = (u32x4) (0u);
+						fetched[u] = __builtin_amdgcn_ballot_w64(need);
+						VR_MIP_COUNT(live, need);
+						if (fetched[u] != 0ull) {
+							if (need) f[u] = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z), true);
+						}
+						k += step;
+					} else {
+						fetched[u] = ~0ull;
+						f[u] = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z), true);
+						k += live ? step : 0.0f;
+					}
+					live = live && k <= ky;
+				}
+				__builtin_amdgcn_sched_barrier(0);
+				#pragma unroll
+				for (int u = 0; u < kMipBatch; u++) {
+					if (!kSkip || fetched[u] != 0ull) {     // (lanes that did not fetch resolve zeros to 0: m >= 0 keeps them unchanged)
+						const float raw = tri_resolve<BPV, LAYOUT, kQ8>(f[u], a, VR_FMA(ks[u], A.x, B.x), VR_FMA(ks[u], A.y, B.y), VR_FMA(ks[u], A.z, B.z));
+						m = ((kSkip || counts[u]) && raw > m) ? raw : m;
+					}
+				}
+				if (kSkip && m >= stop_at) { VR_MIP_COUNT_REST(); live = false; }
+			}
+		};
+		if (skipping) march(std::true_type()); else march(std::false_type());
+		// the filtered lookup of a DVR sample (raymarch_kernel; GPURenderer4.cu:77): entries floor(tb) and floor(tb) + 1, clamp addressing
+		const float tb = __builtin_amdgcn_fmed3f(VR_FMA(m, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
+		const uint32_t i = (uint32_t) (int) tb, i1 = i + 1u < VR_TF_SIZE ? i + 1u : i;
+		const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
+		const f4 c0 = tf4[i], c1 = tf4[i1];
+		colour.x = VR_FMA(w, c1.x - c0.x, c0.x); colour.y = VR_FMA(w, c1.y - c0.y, c0.y);
+		colour.z = VR_FMA(w, c1.z - c0.z, c0.z); colour.w = VR_FMA(w, c1.w - c0.w, c0.w);
+	}
+
+	// -- RaycasterBase.h:44-50 write_color of the entry as it is stored (+ the fused clear: misses store 0)
+	uint32_t rgba = 0;
+	if (hit) {
+		rgba = map_float_int(colour.x, 256) | (map_float_int(colour.y, 256) << 8) |
+		       (map_float_int(colour.z, 256) << 16) | (map_float_int(colour.w, 256) << 24);
+	}
+	*out_px = rgba;
+#ifdef VR_MIP_STATS
+	if (skipping) {
+		atomicAdd((unsigned long long *) (bounds_g + kMipStatsAt), (unsigned long long) stat_samples);
+		atomicAdd((unsigned long long *) (bounds_g + kMipStatsAt + 8u), (unsigned long long) stat_fetches);
+	}
+#endif
+#undef VR_MIP_COUNT
+#undef VR_MIP_COUNT_REST
+}
+
+// block maxima of the min/max scan -> the MIP bounds (vr_device.h): one thread per block of the 32^3 grid
+__global__ __launch_bounds__(256)
+void mip_bounds_kernel(const uint8_t *__restrict__ minmax, uint8_t *__restrict__ bounds) {
+	const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+	constexpr int D = VR_ESL_VOLUME_DIMS;
+	const int x = (int) (e % D), y = (int) ((e / D) % D), z = (int) (e / (D * D));
+	uint32_t around = 0u;
+	for (int dz = -1; dz <= 1; dz++)
+		for (int dy = -1; dy <= 1; dy++)
+			for (int dx = -1; dx <= 1; dx++) {
+				const int nx = x + dx, ny = y + dy, nz = z + dz;
+				if (nx < 0 || ny < 0 || nz < 0 || nx >= D || ny >= D || nz >= D) continue;
+				const uint32_t v = minmax[2 * ((nz * D + ny) * D + nx) + 1];      // unused blocks hold 0 (minmax_init_kernel)
+				around = v > around ? v : around;
+			}
+	const uint32_t own = minmax[2 * e + 1];
+	bounds[e] = (uint8_t) own;
+	bounds[kMipBoundEntries + e] = (uint8_t) around;
+	if (own != 0u) atomicMax((uint32_t *) (bounds + 2u * kMipBoundEntries), own);
+}
+
+hipError_t launch_mip_bounds(const uint8_t *minmax_dev, uint8_t *bounds_dev, hipStream_t stream) {
+	hipError_t e = hipMemsetAsync(bounds_dev + 2u * kMipBoundEntries, 0, kMipBoundBytes - 2u * kMipBoundEntries, stream);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(mip_bounds_kernel, dim3(kMipBoundEntries / 256u), dim3(256), 0, stream, minmax_dev, bounds_dev);
+	return hipGetLastError();
+}
+
 // Which instantiation a frame runs: ONE selector, visited by the launcher and by the host's questions about the launch (does it read
 // the linear array?  how many workgroup tiles?), so the answers cannot drift from what is launched.  `visit` is called with four
 // std::integral_constant tags <SAMPLING, BPV, ADDR, LAYOUT> and a bool: true = the variant reads `linear`, false = the brick copy.
@@ -2218,6 +2510,26 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
 		hipLaunchKernelGGL((raymarch_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
 		                   a, reads_linear ? linear : bricked, tf, esl, (uint32_t *) out, sched.order, sched.cost);
 		return hipGetLastError();
+	});
+}
+
+hipError_t launch_mip(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf, const uint8_t *bounds,
+                      void *out, hipStream_t stream) {
+	if (args.p.esl != 0u && bounds == nullptr) return hipErrorInvalidValue;
+	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
+		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
+		if constexpr (is_run_layout(LAYOUT)) return hipErrorInvalidValue;       // a MIP frame never reads the run bricks (the caller does not ask for them)
+		else {
+			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
+			RayKernelArgs a = args;
+			a.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u;
+			a.tiles_y = (a.p.out_rows + a.phase_y + threads / 32u - 1u) / (threads / 32u);
+			// the bound table is dynamic LDS, so that frames which do not skip keep every resident workgroup the address tables allow
+			const uint32_t dynamic_lds = a.p.esl != 0u ? kMipBoundEntries : 0u;
+			hipLaunchKernelGGL((mip_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
+			                   a, reads_linear ? linear : bricked, tf, bounds, (uint32_t *) out);
+			return hipGetLastError();
+		}
 	});
 }
 

@@ -129,6 +129,18 @@ class HipRenderer:
         self._check(self._L.vr_hip_render_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
                                                  C.c_void_p(stream) if stream else None), "render_volume_device")
 
+    # -- maximum-intensity projection (vr_hip_render_mip: the maximum sample of every ray through one transfer-function lookup)
+    def render_mip(self, params):
+        """Host-buffer flavour: returns an (out_rows, out_width, 4) uint8 array.  params.esl != 0 = exact fetch skipping by block maxima."""
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        self._check(self._L.vr_hip_render_mip(self._ctx, C.byref(params), out.ctypes.data), "render_mip")
+        return out
+
+    def render_mip_device(self, params, dev_ptr, stream=None):
+        """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
+        self._check(self._L.vr_hip_render_mip_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
+                                                     C.c_void_p(stream) if stream else None), "render_mip_device")
+
     # -- timing (Profiler.cpp:46-67)
     def timing(self):
         t = VrTiming()
