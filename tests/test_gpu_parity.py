@@ -219,11 +219,16 @@ def test_column_march_matches_oracle(vr, gpu, golden, oracle):
             p.esl, p.ray_threshold = 0, 1.0
             want = oracle.render(p, golden.voxels(name), st["tf"], st["esl"])
             gpu.set_brick_plane(-1)
-            for lane_map in (0, 1, 2):
+            # 5 and 10 add the 16x4 / 4x16 wave-shape bits, which the column kernels must ignore (their waves are 8x8); both kernels' marches
+            pn = p.copy()
+            pn.sampling = vr.SAMPLE_NEAREST
+            want_nearest = oracle.render(pn, golden.voxels(name), st["tf"], st["esl"])
+            for lane_map in (0, 1, 2, 5, 10):
                 for ph in ((0, 0), (3, 5), (7, 1)):
                     gpu.set_tile_mapping(lane_map, *ph)
-                    assert np.array_equal(gpu.render_volume(p), want), (name, lane_map, ph)
-                    assert gpu.last_launch()["layout"] == 7
+                    for q, expected in ((p, want), (pn, want_nearest)) if lane_map > 2 else ((p, want),):
+                        assert np.array_equal(gpu.render_volume(q), expected), (name, lane_map, ph, q.sampling)
+                        assert gpu.last_launch()["layout"] == 7
             gpu.set_tile_mapping(-1)
             rows = []
             for rank in range(3):

@@ -134,6 +134,8 @@ uint64_t copy_bytes(const vr_ctx *c, uint32_t kind);
 hipError_t drain(vr_ctx *c);
 const void *copy_for(vr_ctx *c, uint32_t kind);
 
+uint32_t max_dim_of(const vr_ctx *c) { return std::max(c->dim[0], std::max(c->dim[1], c->dim[2])); }
+
 bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // folds one finished event pair into the statistics
@@ -378,6 +380,92 @@ void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
 	else { a.esl_div_magic = (uint32_t) ((1ull << 32) / bd + 1); a.esl_div_shift = 0; }
 }
 
+// ---- what launch_frame and launch_mip_frame (further down) decide the same way ----------------------------------------------------
+
+// the copy a frame of this layout reads (not asked for kLayoutLinear)
+uint32_t copy_kind_of(const RayKernelArgs &a, uint32_t sampling) {
+	return a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
+	       a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis :
+	       a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane;
+}
+
+// d = |direction * half| (cells per unit of k along every volume axis), its major axis — ties go to the higher axis — and whether the
+// view, or in perspective its central direction, runs along that axis
+struct ViewAxis { float d[3]; int major; bool along; };
+ViewAxis view_axis(const vr_params *p, const float *half) {
+	ViewAxis v;
+	for (int i = 0; i < 3; i++) v.d[i] = std::fabs(p->view.direction[i] * half[i]);
+	const float dx = v.d[0], dy = v.d[1], dz = v.d[2];
+	v.major = dz >= dx && dz >= dy ? 2 : (dy >= dx ? 1 : 0);
+	v.along = std::fmax(dx, std::fmax(dy, dz)) > 0.98f * std::sqrt(dx * dx + dy * dy + dz * dz);
+	return v;
+}
+// the chunk plane across a volume axis
+uint32_t plane_across(int axis) { return axis == 2 ? kPlaneXY : (axis == 1 ? kPlaneXZ : kPlaneYZ); }
+
+// neighbouring pixels are at most one cell apart along every volume axis
+bool one_cell_per_pixel(const vr_params *p, const float *half) {
+	for (int ax = 0; ax < 3; ax++)
+		if ((std::fabs(p->view.right_plane[ax]) + std::fabs(p->view.up_plane[ax])) * half[ax] > 1.0f) return false;
+	return true;
+}
+
+// TRILINEAR with 2-byte voxels: the oct bricks (one 16-byte gather per sample instead of two 8-byte ones) for ORTHOGONAL views
+// with at most one cell per pixel — there the pixels of a lane quad share their elements and the halved gather count wins
+// (1024^3: 4.0 / 5.8 / 4.0 / 4.2 ms against 5.1 / 6.0 / 5.9 / 5.6 with the quad bricks; 2048^3: 28-44 against 40-48 ms); the
+// rays of a perspective view diverge to more than a cell per pixel, every lane then pulls 16 bytes it uses once, and the doubled
+// traffic loses (4.2-5.5 against 3.5-4.4 ms): those keep the quad bricks.  Not when a quad copy is forced (testing) or the
+// index-arithmetic path is.
+bool takes_oct_bricks(const vr_ctx *c, const vr_params *p, const float *half) {
+	if (p->sampling == VR_SAMPLE_NEAREST || c->bpv != 2 || c->layout != VR_LAYOUT_BRICKED || !copy_possible(c, kCopyOct) || c->brick_plane_force >= 0 || c->force_wide == 1 ||
+	    (p->view.perspective && !c->oct_always))
+		return false;
+	return c->oct_always || one_cell_per_pixel(p, half);
+}
+
+// No copy could be built: any resident copy this sampling mode can read (the run copies only for a caller whose kernel reads them), else
+// the linear array.  Sets the layout and returns the copy.
+const void *resident_fallback(const vr_ctx *c, uint32_t sampling, bool run_copies, uint32_t &layout) {
+	const bool nearest = sampling == VR_SAMPLE_NEAREST;
+	if (nearest && c->copy[kCopyVoxel] && c->force_wide != 1) { layout = kLayoutVoxel; return c->copy[kCopyVoxel]; }
+	if (run_copies && !nearest && !c->force_wide && c->copy[kCopyRunZ]) { layout = kLayoutRun; return c->copy[kCopyRunZ]; }
+	if (run_copies && !nearest && !c->force_wide && c->copy[kCopyRunY]) { layout = kLayoutRunY; return c->copy[kCopyRunY]; }
+	if (!nearest && c->bpv == 2 && c->force_wide != 1 && c->copy[kCopyOct]) { layout = kLayoutOct; return c->copy[kCopyOct]; }
+	layout = kLayoutLinear;
+	return nullptr;
+}
+
+// In-cube sample coordinates are exact to ~2^-23 * (1 + 2 max|origin|) * N/2 texels; the unclamped fetch (vr_kernels.hip)
+// needs them inside (-1, N), i.e. an error below 1/2.  True with a factor-4 margin.
+float max_abs_origin(const vr_params *p) { return std::fmax(std::fabs(p->view.origin[0]), std::fmax(std::fabs(p->view.origin[1]), std::fabs(p->view.origin[2]))); }
+bool fetch_coordinates_exact(const vr_ctx *c, const vr_params *p) { return (1.0f + 2.0f * max_abs_origin(p)) * (float) max_dim_of(c) < 1048576.0f; }
+
+// cost[ntiles] and order[ntiles * order_words_per_tile] for at least `ntiles` tiles.  Buffers that are too small are freed (nothing of them
+// may be in flight) and allocated anew; false, with none left, if that fails.
+bool ensure_tile_buffers(uint32_t *&cost, uint32_t *&order, uint32_t &capacity, uint32_t ntiles, uint32_t order_words_per_tile) {
+	if (capacity >= ntiles) return true;
+	if (cost) { (void) hipFree(cost); (void) hipFree(order); cost = order = nullptr; capacity = 0; }
+	if (hipMalloc((void **) &cost, (size_t) ntiles * 4) == hipSuccess && hipMalloc((void **) &order, (size_t) ntiles * 4 * order_words_per_tile) == hipSuccess) { capacity = ntiles; return true; }
+	(void) hipGetLastError();
+	if (cost) (void) hipFree(cost);
+	cost = order = nullptr;
+	return false;
+}
+
+// cached lane orders / tile phases were chosen for another volume, copy or plane
+void forget_tile_mappings(vr_ctx *c) { c->map_cached = 0; c->map_next = 0; }
+// recorded tile orders describe other ray lengths or another scheduling mode (buffers and last-use marks stay: recycled only when free)
+void forget_recorded_orders(vr_ctx *c) {
+	for (auto &e : c->map_cache) { e.dual_state = 0; e.order_tiles = 0; }
+	for (auto &e : c->order_cache) { e.has_last = false; e.repeats = 0; for (auto &sl : e.slot) sl.valid = false; }
+}
+
+// refuses a call that needs the linear array once that was released; `remedy` ends the message
+int need_linear(vr_ctx *c, const char *remedy) {
+	if (c->vol != nullptr || c->dim[0] == 0) return VR_OK;
+	return fail(c, VR_ERR_NOT_READY, (std::string("the linear copy was released (vr_hip_release_linear_copy): ") + remedy).c_str());
+}
+
 // the event pair and the sequence number of the frame about to be launched (only blocks if kEventRing launches are still in flight)
 EventPair &next_frame_events(vr_ctx *c, uint64_t &frame_seq) {
 	EventPair &ev = c->ring[c->ring_head];
@@ -400,8 +488,7 @@ hipError_t bounds_check_arm(vr_ctx *c, RayKernelArgs &a, const vr_params *p, con
 	const bool column = a.layout == kLayoutColumn || a.layout == kLayoutVoxCol;
 	a.bc_base = (uint64_t) (uintptr_t) array - (column ? kColPadBytes : 0u);
 	a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
-	             copy_bytes(c, a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
-	                           a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane);
+	             copy_bytes(c, copy_kind_of(a, p->sampling));
 	if (column) a.bc_bytes += 2ull * kColPadBytes;
 	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, kCopyRunY) : 0;
 	a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
@@ -426,9 +513,29 @@ int bounds_check_verdict(vr_ctx *c, hipStream_t stream, uint32_t layout) {
 }
 #endif
 
+// One frame: `launch` between the start and stop events of the frame's pair, armed before and judged after in the bounds-checked build.
+// frame_seq = the frame's sequence number.
+template <class Launch>
+int launch_timed(vr_ctx *c, RayKernelArgs &a, const vr_params *p, const RaymarchPlan &plan, const void *brick_copy, hipStream_t stream, uint64_t &frame_seq, Launch &&launch) {
+#ifdef VR_BOUNDS_CHECK
+	VR_TRY(c, bounds_check_arm(c, a, p, plan, brick_copy, plan.tiles_x * plan.tiles_y));
+#endif
+	EventPair &ev = next_frame_events(c, frame_seq);
+	VR_TRY(c, hipEventRecord(ev.start, stream));
+	VR_TRY(c, launch());
+	VR_TRY(c, hipEventRecord(ev.stop, stream));
+	ev.pending = true;
+#ifdef VR_BOUNDS_CHECK
+	{ const int bc = bounds_check_verdict(c, stream, a.layout); if (bc) return bc; }
+#endif
+	return VR_OK;
+}
+
 int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
 	RayKernelArgs a;
 	volume_args(c, p, a);
+	const float half[3] = { a.half_x, a.half_y, a.half_z };
+	const ViewAxis va = view_axis(p, half);
 	{   // largest power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below: raw < P implies a transparent sample
 		uint32_t below = 0;
 		const uint32_t top = c->bpv == 1 ? 256u : 65536u;
@@ -439,11 +546,9 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		else if (c->bpv == 1) a.skip_mask = ((0xffu & ~(below - 1u)) * 0x01010101u);
 		else a.skip_mask = ((0xffffu & ~(below - 1u)) * 0x00010001u);
 	}
-	{   // In-cube sample coordinates are exact to ~2^-23 * (1 + 2 max|origin|) * N/2 texels; the unclamped fetch (vr_kernels.hip)
-		// needs them inside (-1, N), i.e. an error below 1/2.  Keep a factor-4 margin, else clamp every sample.
-		const float omax = std::fmax(std::fabs(p->view.origin[0]), std::fmax(std::fabs(p->view.origin[1]), std::fabs(p->view.origin[2])));
-		const float nmax = (float) std::max(c->dim[0], std::max(c->dim[1], c->dim[2]));
-		a.clamp_fetch = (1.0f + 2.0f * omax) * nmax < 1048576.0f ? 0u : 1u;
+	{   // fp32 sample coordinates that are not exact to a fraction of a cell: clamp every sample
+		const float omax = max_abs_origin(p), nmax = (float) max_dim_of(c);
+		a.clamp_fetch = fetch_coordinates_exact(c, p) ? 0u : 1u;
 		// intersect() replaces a direction component that is exactly 0 by 1e-5 (RaycasterBase.h:33-35): a ray whose origin lies
 		// up to ky * 1e-5 outside a face of the cube is then still reported as a hit and marches at that constant out-of-cube
 		// coordinate, ky * 1e-5 * N/2 texels beyond the face.  ky <= sqrt(3) * (omax + 1) for |direction| >= 1 (orthogonal: unit
@@ -454,7 +559,6 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		// A step moves a ray by ray_step * |direction component| * N/2 cells along an axis; perspective directions are not
 		// normalised (direction + right * fx + up * fy, ViewBase.h:29-31), so the bound is taken over the whole frame.
 		{
-			const float half[3] = { a.half_x, a.half_y, a.half_z };
 			float advance = 0.0f;
 			for (int i = 0; i < 3; i++) {
 				float d = std::fabs(p->view.direction[i]);
@@ -483,12 +587,9 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		else {
 			// only for views (or, in perspective, central directions) along a volume axis: measured on the oblique benchmark pose the
 			// (x,y) copy is as good as any (4.1 ms against 4.1 - 5.1 ms), along an axis the perpendicular plane wins by 8 - 16 %
-			const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y),
-			            dz = std::fabs(p->view.direction[2] * a.half_z);
-			const float dmax = std::fmax(dx, std::fmax(dy, dz));
-			if (dz >= dx && dz >= dy && copy_possible(c, kCopyRunY)) run_layout = kLayoutRunY;     // runs across the march, never along it
-			if (dmax > 0.98f * std::sqrt(dx * dx + dy * dy + dz * dz)) {
-				plane = dz >= dx && dz >= dy ? kPlaneXY : (dy >= dx ? kPlaneXZ : kPlaneYZ);
+			if (va.major == 2 && copy_possible(c, kCopyRunY)) run_layout = kLayoutRunY;     // runs across the march, never along it
+			if (va.along) {
+				plane = plane_across(va.major);
 				// Perspective along x or y: the pixel pitch grows from 0.4 to 1.1 cells along the march, most lane quads straddle
 				// chunks, and the run bricks — whose runs (along z) then lie across the march — are faster (measured 2.08 / 2.18 ms
 				// against 2.49 / 2.51 ms on the benchmark poses).  Along z the runs lie along the march and the quad copy wins
@@ -512,20 +613,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// NEAREST: the voxel bricks (one voxel per element) unless a quad copy is forced (testing) or a 64-bit path is
 	if (p->sampling == VR_SAMPLE_NEAREST && bricked && copy_possible(c, kCopyVoxel) && c->brick_plane_force < 0 && c->force_wide != 1)
 		a.layout = kLayoutVoxel;
-	// TRILINEAR with 2-byte voxels: the oct bricks (one 16-byte gather per sample instead of two 8-byte ones) for ORTHOGONAL views
-	// with at most one cell per pixel — there the pixels of a lane quad share their elements and the halved gather count wins
-	// (1024^3: 4.0 / 5.8 / 4.0 / 4.2 ms against 5.1 / 6.0 / 5.9 / 5.6 with the quad bricks; 2048^3: 28-44 against 40-48 ms); the
-	// rays of a perspective view diverge to more than a cell per pixel, every lane then pulls 16 bytes it uses once, and the doubled
-	// traffic loses (4.2-5.5 against 3.5-4.4 ms): those keep the quad bricks.  Not when a quad copy is forced (testing) or the
-	// index-arithmetic path is.
-	if (p->sampling != VR_SAMPLE_NEAREST && c->bpv == 2 && bricked && copy_possible(c, kCopyOct) && c->brick_plane_force < 0 && c->force_wide != 1 &&
-	    (!p->view.perspective || c->oct_always)) {
-		bool dense = true;
-		const float half[3] = { a.half_x, a.half_y, a.half_z };
-		for (int ax = 0; ax < 3; ax++)
-			if ((std::fabs(p->view.right_plane[ax]) + std::fabs(p->view.up_plane[ax])) * half[ax] > 1.0f) dense = false;
-		if (dense || c->oct_always) a.layout = kLayoutOct;
-	}
+	if (takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
 	esl_divisor(a, p->esl_block_dims);
 
 	vr_ctx::MapEntry *hit = nullptr;
@@ -587,13 +675,10 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	static const bool col_ert = [] { const char *e = getenv("VR_COL_ERT"); return e == nullptr || atoi(e) != 0; }();      // VR_COL_ERT=0: A/B
 	if (bricked && c->bpv == 1 && !c->force_wide && !p->view.perspective && !p->esl && (p->ray_threshold >= 1.0f || col_ert) &&
 	    !a.clamp_fetch && c->column_force >= 0 && (c->brick_plane_force < 0 || c->column_force > 0)) {
-		const float half[3] = { a.half_x, a.half_y, a.half_z };
-		float d[3];
-		for (int i = 0; i < 3; i++) d[i] = std::fabs(p->view.direction[i] * half[i]);
-		const int m = d[2] >= d[0] && d[2] >= d[1] ? 2 : (d[1] >= d[0] ? 1 : 0);
+		const float *d = va.d;
+		const int m = va.major;
 		const float advance = d[m] * p->ray_step;
-		bool take = advance >= 1.0f / 64.0f && advance <= 1.0f;
-		for (int i = 0; i < 3; i++) if ((std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i] > 1.0f) take = false;
+		bool take = advance >= 1.0f / 64.0f && advance <= 1.0f && one_cell_per_pixel(p, half);
 		if (c->column_force == 0)                                          // per view: along the axis — 4 > 2 sqrt(3), the longest segment in k
 			for (int i = 0; i < 3; i++) if (i != m && d[i] * 4.0f >= 0.45f) take = false;
 		// TRILINEAR reads the voxel windows (kLayoutVoxCol, voxcol_tri_kernel) where every wave's rectangle of cell columns fits in its 64
@@ -630,21 +715,14 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		if (brick_copy == nullptr || a.alt_copy == 0) { a.layout = run_layout; dual_stage = -1; dual_analytic = false; brick_copy = nullptr; }
 	}
 	if (a.layout != kLayoutLinear && brick_copy == nullptr) {
-		const uint32_t want = a.layout == kLayoutRun ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
-		                      a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (p->sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis : a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane;
+		const uint32_t want = copy_kind_of(a, p->sampling);
 		brick_copy = copy_for(c, want);
 		if (brick_copy == nullptr && want != kCopyQuadXY) {
 			a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
-			c->map_cached = 0; c->map_next = 0;              // lane orders were chosen for the copy that could not be had
+			forget_tile_mappings(c);                         // lane orders were chosen for the copy that could not be had
 			brick_copy = copy_for(c, kCopyQuadXY);
 		}
-		if (brick_copy == nullptr) {                         // no quad copy either: any resident copy this sampling mode can read
-			if (p->sampling == VR_SAMPLE_NEAREST && c->copy[kCopyVoxel] && c->force_wide != 1) { a.layout = kLayoutVoxel; brick_copy = c->copy[kCopyVoxel]; }
-			else if (p->sampling != VR_SAMPLE_NEAREST && !c->force_wide && c->copy[kCopyRunZ]) { a.layout = kLayoutRun; brick_copy = c->copy[kCopyRunZ]; }
-			else if (p->sampling != VR_SAMPLE_NEAREST && !c->force_wide && c->copy[kCopyRunY]) { a.layout = kLayoutRunY; brick_copy = c->copy[kCopyRunY]; }
-			else if (p->sampling != VR_SAMPLE_NEAREST && c->bpv == 2 && c->force_wide != 1 && c->copy[kCopyOct]) { a.layout = kLayoutOct; brick_copy = c->copy[kCopyOct]; }
-			else a.layout = kLayoutLinear;
-		}
+		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, true, a.layout);      // no quad copy either
 	}
 	// Shape of a wave's pixel tile (8x8, 16x4 or 4x16 inside the 32x16-pixel workgroup tile): a perspective view along a volume axis
 	// that reads run bricks gets its waves elongated along the screen direction the RUNS map to — the lanes of a wave then share the
@@ -652,8 +730,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// perspective poses: 2.07 -> 1.96 (along z, runs along y: tall), 2.04 -> 1.95 (along y, runs along z: tall), 2.05 -> 1.96 ms
 	// (along x, runs along z: wide); oblique views and orthogonal views lose 3-9 % with either elongated shape and keep 8x8.
 	if (c->tile_lane_map < 0 && is_run_layout(a.layout) && p->view.perspective && !p->esl) {       // (with leaping the rays are short: no difference measured)
-		const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y), dz = std::fabs(p->view.direction[2] * a.half_z);
-		if (std::fmax(dx, std::fmax(dy, dz)) > 0.98f * std::sqrt(dx * dx + dy * dy + dz * dz)) {
+		if (va.along) {
 			const int run_axis = a.layout == kLayoutRunY ? 1 : 2;
 			const float across = std::fabs(p->view.right_plane[run_axis]), down = std::fabs(p->view.up_plane[run_axis]);
 			a.lane_map = (a.lane_map & 3u) | ((down > across ? 2u : 1u) << 2);
@@ -663,8 +740,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// maps to z — four different slices, i.e. four different lines — not a 2x2-pixel block: byte gathers whose lanes fall into the same
 	// dwords serialise (measured on the benchmark poses: 1.44 -> 1.38 ms along y, 1.46 -> 1.38 ms along x; along z the blocks stay: 1.23).
 	if (c->tile_lane_map < 0 && a.layout == kLayoutVoxel && p->view.perspective && (a.lane_map & 3u) == kLaneBlocks) {
-		const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y), dz = std::fabs(p->view.direction[2] * a.half_z);
-		if (dz < dx || dz < dy) a.lane_map = std::fabs(p->view.up_plane[2]) > std::fabs(p->view.right_plane[2]) ? kLaneColumns : kLaneRows;
+		if (va.major != 2) a.lane_map = std::fabs(p->view.up_plane[2]) > std::fabs(p->view.right_plane[2]) ? kLaneColumns : kLaneRows;
 	}
 	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
 	if (plan.reads_linear && c->vol == nullptr)
@@ -684,8 +760,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		memset(&key, 0, sizeof key);
 		key.sampling = p->sampling; key.esl = p->esl ? 1u : 0u; key.ert = p->ray_threshold < 1.0f ? 1u : 0u; key.perspective = p->view.perspective ? 1u : 0u;
 		{
-			const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y), dz = std::fabs(p->view.direction[2] * a.half_z);
-			const int m = dz >= dx && dz >= dy ? 2 : (dy >= dx ? 1 : 0);
+			const int m = va.major;
 			key.major_axis = (uint32_t) m * 2u + (p->view.direction[m] < 0.0f ? 1u : 0u);
 			// ... and the direction itself in steps of 1/8 per component (views within a few degrees share their costs, different poses do not)
 			const float len = std::sqrt(p->view.direction[0] * p->view.direction[0] + p->view.direction[1] * p->view.direction[1] + p->view.direction[2] * p->view.direction[2]);
@@ -729,11 +804,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 				if (sl.ready != nullptr && sl.issue_seq != 0) { const hipError_t q = hipEventQuery(sl.ready); if (q != hipSuccess) { (void) hipGetLastError(); continue; } }
 				est = &sl; break;
 			}
-			if (est != nullptr && est->capacity < ntiles) {
-				if (est->cost) { (void) hipFree(est->cost); (void) hipFree(est->order); est->cost = est->order = nullptr; est->capacity = 0; }
-				if (hipMalloc((void **) &est->cost, (size_t) ntiles * 4) == hipSuccess && hipMalloc((void **) &est->order, (size_t) ntiles * 4) == hipSuccess) est->capacity = ntiles;
-				else { (void) hipGetLastError(); if (est->cost) (void) hipFree(est->cost); est->cost = est->order = nullptr; est = nullptr; }
-			}
+			if (est != nullptr && !ensure_tile_buffers(est->cost, est->order, est->capacity, ntiles, 1u)) est = nullptr;
 			if (est != nullptr) {
 				if (est->ready == nullptr) VR_TRY(c, hipEventCreateWithFlags(&est->ready, hipEventDisableTiming));
 				RayKernelArgs ea = a;
@@ -756,11 +827,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 				if (sl.ready != nullptr && sl.issue_seq != 0) { const hipError_t q = hipEventQuery(sl.ready); if (q != hipSuccess) { (void) hipGetLastError(); continue; } }   // its order kernel has not run yet
 				if (record_slot == nullptr || (!sl.valid && record_slot->valid) || (sl.valid == record_slot->valid && sl.issue_seq < record_slot->issue_seq)) record_slot = &sl;
 			}
-			if (record_slot != nullptr && record_slot->capacity < ntiles) {                        // (free: nothing of it is in flight)
-				if (record_slot->cost) { (void) hipFree(record_slot->cost); (void) hipFree(record_slot->order); record_slot->cost = record_slot->order = nullptr; record_slot->capacity = 0; }
-				if (hipMalloc((void **) &record_slot->cost, (size_t) ntiles * 4) == hipSuccess && hipMalloc((void **) &record_slot->order, (size_t) ntiles * 4) == hipSuccess) record_slot->capacity = ntiles;
-				else { (void) hipGetLastError(); if (record_slot->cost) (void) hipFree(record_slot->cost); record_slot->cost = record_slot->order = nullptr; record_slot = nullptr; }
-			}
+			if (record_slot != nullptr && !ensure_tile_buffers(record_slot->cost, record_slot->order, record_slot->capacity, ntiles, 1u)) record_slot = nullptr;      // (free: nothing of it is in flight)
 			if (record_slot != nullptr) {
 				if (record_slot->ready == nullptr) VR_TRY(c, hipEventCreateWithFlags(&record_slot->ready, hipEventDisableTiming));
 				record_slot->valid = false;
@@ -776,9 +843,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	if (dual_stage >= 0) {
 		if (ntiles < 2u || ntiles > (1u << 20)) dual_stage = -1;      // (a frame that keeps kLayoutRunDual without a choice reads the copy along z)
 		else if (hit->capacity < ntiles) {
-			if (hit->cost) { VR_TRY(c, drain(c)); (void) hipFree(hit->cost); (void) hipFree(hit->order); hit->cost = hit->order = nullptr; hit->capacity = 0; }
-			if (hipMalloc((void **) &hit->cost, (size_t) ntiles * 4) == hipSuccess && hipMalloc((void **) &hit->order, (size_t) ntiles * 8) == hipSuccess) hit->capacity = ntiles;
-			else { (void) hipGetLastError(); if (hit->cost) (void) hipFree(hit->cost); hit->cost = hit->order = nullptr; dual_stage = -1; }
+			if (hit->cost) VR_TRY(c, drain(c));
+			if (!ensure_tile_buffers(hit->cost, hit->order, hit->capacity, ntiles, 2u)) dual_stage = -1;      // (order: the choice, and behind it the second recording)
 			if (!dual_test) { hit->dual_state = 0; if (dual_stage > 0) dual_stage = -1; }      // (cannot happen: the grid of a parameter set does not change)
 		}
 	}
@@ -820,18 +886,9 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u,
 	                                 a.layout == kLayoutVoxCol ? 1u : 0u };
 
-#ifdef VR_BOUNDS_CHECK
-	VR_TRY(c, bounds_check_arm(c, a, p, plan, brick_copy, ntiles));
-#endif
 	uint64_t frame_seq = 0;
-	EventPair &ev = next_frame_events(c, frame_seq);
-	VR_TRY(c, hipEventRecord(ev.start, stream));
-	VR_TRY(c, launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream));
-	VR_TRY(c, hipEventRecord(ev.stop, stream));
-	ev.pending = true;
-#ifdef VR_BOUNDS_CHECK
-	{ const int bc = bounds_check_verdict(c, stream, a.layout); if (bc) return bc; }
-#endif
+	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
+	if (rc) return rc;
 	if (dual_advance) {                          // behind the frame, on its stream
 		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
 		VR_TRY(c, hipEventRecord(hit->order_ready, stream));
@@ -870,8 +927,6 @@ void free_bricks(vr_ctx *c) {
 		c->copy_build_ms[k] = 0; c->copy_failed[k] = false;
 	}
 }
-
-uint32_t max_dim_of(const vr_ctx *c) { return std::max(c->dim[0], std::max(c->dim[1], c->dim[2])); }
 
 uint64_t copy_bytes(const vr_ctx *c, uint32_t kind) {
 	if (kind <= kCopyQuadYZ) return bricked_elems(c->dim[0], c->dim[1], c->dim[2]) * 4 * c->bpv;
@@ -950,7 +1005,7 @@ int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	VR_TRY(c, drain(c));                         // frames still reading the volume we are about to free
 	if (c->vol) { (void) hipFree(c->vol); c->vol = nullptr; }
 	free_bricks(c);
-	c->map_cached = 0; c->map_next = 0;          // cached tile mappings belong to the previous volume
+	forget_tile_mappings(c);                     // cached tile mappings belong to the previous volume
 	c->mip_mapped = 0; c->mip_map_next = 0; c->mip_bounds_ready = false;       // ... and so do the block maxima of the MIP frames
 	c->dim[0] = c->dim[1] = c->dim[2] = 0;
 	const uint64_t elems = (uint64_t) x * y * z;
@@ -988,6 +1043,7 @@ int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t 
 	RayKernelArgs a;
 	volume_args(c, p, a);
 	a.force_wide = c->force_wide;
+	const float half[3] = { a.half_x, a.half_y, a.half_z };
 	const bool bricked = c->layout == VR_LAYOUT_BRICKED, nearest = p->sampling == VR_SAMPLE_NEAREST;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	a.brick_plane = kPlaneXY;
@@ -996,40 +1052,27 @@ int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t 
 	if (bricked && !nearest && !c->force_wide) {
 		uint32_t plane = kPlaneXY;
 		if (c->brick_plane_force >= 0 && c->brick_plane_force < (int32_t) kPlanes) plane = (uint32_t) c->brick_plane_force;
-		else if (c->brick_plane_force < 0) {             // along a volume axis: the chunk plane across it (launch_frame)
-			const float dx = std::fabs(p->view.direction[0] * a.half_x), dy = std::fabs(p->view.direction[1] * a.half_y), dz = std::fabs(p->view.direction[2] * a.half_z);
-			if (std::fmax(dx, std::fmax(dy, dz)) > 0.98f * std::sqrt(dx * dx + dy * dy + dz * dz)) plane = dz >= dx && dz >= dy ? kPlaneXY : (dy >= dx ? kPlaneXZ : kPlaneYZ);
+		else if (c->brick_plane_force < 0) {             // along a volume axis: the chunk plane across it
+			const ViewAxis va = view_axis(p, half);
+			if (va.along) plane = plane_across(va.major);
 		}
 		if (copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
 	}
-	if (bricked && !nearest && c->bpv == 2 && copy_possible(c, kCopyOct) && c->brick_plane_force < 0 && c->force_wide != 1 && (!p->view.perspective || c->oct_always)) {
-		bool dense = true;               // at most one cell per pixel (launch_frame)
-		const float half[3] = { a.half_x, a.half_y, a.half_z };
-		for (int ax = 0; ax < 3; ax++)
-			if ((std::fabs(p->view.right_plane[ax]) + std::fabs(p->view.up_plane[ax])) * half[ax] > 1.0f) dense = false;
-		if (dense || c->oct_always) a.layout = kLayoutOct;
-	}
+	if (takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
 	const void *brick_copy = nullptr;
 	if (a.layout != kLayoutLinear) {
-		brick_copy = copy_for(c, a.layout == kLayoutVoxel ? kCopyVoxel : a.layout == kLayoutOct ? kCopyOct : kCopyQuadXY + a.brick_plane);
+		brick_copy = copy_for(c, copy_kind_of(a, p->sampling));
 		if (brick_copy == nullptr) {                     // refused or not buildable any more: the first quad copy, then whatever is resident
 			a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
 			brick_copy = copy_for(c, kCopyQuadXY);
 		}
-		if (brick_copy == nullptr) {
-			if (nearest && c->copy[kCopyVoxel] && c->force_wide != 1) { a.layout = kLayoutVoxel; brick_copy = c->copy[kCopyVoxel]; }
-			else if (!nearest && c->bpv == 2 && c->force_wide != 1 && c->copy[kCopyOct]) { a.layout = kLayoutOct; brick_copy = c->copy[kCopyOct]; }
-			else a.layout = kLayoutLinear;
-		}
+		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, false, a.layout);      // (a MIP frame never reads the run copies)
 	}
 	// Skipping and stopping by block maxima.  The grid is the volume's own (vr_hip_volume_minmax), whatever params.esl_block_* say.  Not
 	// for views so far away that fp32 sample coordinates are not exact to a small fraction of a cell (the condition under which DVR
 	// frames clamp every fetch, launch_frame): the TRILINEAR bound covers one voxel around the block of the sample's position.
 	esl_divisor(a, volume_block_dims(c));
-	if (p->esl) {
-		const float omax = std::fmax(std::fabs(p->view.origin[0]), std::fmax(std::fabs(p->view.origin[1]), std::fabs(p->view.origin[2])));
-		if (!((1.0f + 2.0f * omax) * (float) max_dim_of(c) < 1048576.0f)) a.p.esl = 0u;
-	}
+	if (p->esl && !fetch_coordinates_exact(c, p)) a.p.esl = 0u;
 	if (a.p.esl) { const int rc = build_mip_bounds(c); if (rc) return rc; }
 
 	uint32_t straddle = 1000u;
@@ -1056,18 +1099,34 @@ int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t 
 		return fail(c, VR_ERR_NOT_READY, "this MIP frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                 "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again");
 	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u };
-#ifdef VR_BOUNDS_CHECK
-	VR_TRY(c, bounds_check_arm(c, a, p, plan, brick_copy, plan.tiles_x * plan.tiles_y));
-#endif
 	uint64_t frame_seq = 0;
-	EventPair &ev = next_frame_events(c, frame_seq);
-	VR_TRY(c, hipEventRecord(ev.start, stream));
-	VR_TRY(c, launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, a.p.esl ? c->mip_bounds : nullptr, dev_rgba, stream));
-	VR_TRY(c, hipEventRecord(ev.stop, stream));
-	ev.pending = true;
-#ifdef VR_BOUNDS_CHECK
-	{ const int bc = bounds_check_verdict(c, stream, a.layout); if (bc) return bc; }
-#endif
+	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, a.p.esl ? c->mip_bounds : nullptr, dev_rgba, stream); });
+}
+
+// what the four render entry points check first; host_frame: the frame goes through the window buffer to host memory
+int render_preamble(vr_ctx *c, const vr_params *p, const void *buffer, bool host_frame) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (buffer == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");      // GPURenderer1.cu:101-102
+	int rc = validate_params(c, p);
+	if (rc) return rc;
+	rc = ready(c);
+	if (rc) return rc;
+	if (host_frame && (c->fb == nullptr || (size_t) p->out_width * p->out_rows * 4 > c->fb_bytes))
+		return fail(c, VR_ERR_NOT_READY, "output larger than the window buffer: call vr_hip_set_window first");
+	VR_TRY(c, hipSetDevice(c->device));
+	return VR_OK;
+}
+
+// ... and what the two host-buffer ones end with: the frame in host memory (where the reference's timed region ends, GPURenderer1.cu:107-110)
+// and the time since t0
+void take_total_time(vr_ctx *c, std::chrono::steady_clock::time_point t0) {
+	c->last_total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if (c->last_total_ms > c->total_ms_max) c->total_ms_max = c->last_total_ms;
+}
+int frame_to_host(vr_ctx *c, uint8_t *host_rgba, size_t bytes, std::chrono::steady_clock::time_point t0) {
+	VR_TRY(c, hipMemcpyAsync(host_rgba, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	take_total_time(c, t0);
 	return VR_OK;
 }
 
@@ -1172,9 +1231,7 @@ int vr_hip_set_transfer_fn(vr_ctx *c, const float *tf, const uint32_t *esl) {
 		zero++;
 	c->tf_zero_below = (float) zero;
 	c->tf_set = true;
-	// tile orders recorded under the old transfer function describe other ray lengths (placement only; nothing is in flight here: drained above)
-	for (auto &e : c->map_cache) { e.dual_state = 0; e.order_tiles = 0; }
-	for (auto &e : c->order_cache) { e.has_last = false; e.repeats = 0; for (auto &sl : e.slot) sl.valid = false; }
+	forget_recorded_orders(c);                   // they describe ray lengths under the old transfer function (placement only; nothing is in flight here: drained above)
 	return VR_OK;
 }
 
@@ -1211,11 +1268,10 @@ int vr_hip_set_layout(vr_ctx *c, uint32_t layout) {
 	if (layout != VR_LAYOUT_LINEAR && layout != VR_LAYOUT_BRICKED) return fail(c, VR_ERR_INVALID, "unknown volume layout");
 	VR_TRY(c, hipSetDevice(c->device));
 	VR_TRY(c, drain(c));                         // a frame may still be reading the copies we are about to drop
-	if (c->vol == nullptr && c->dim[0] != 0)
-		return fail(c, VR_ERR_NOT_READY, "the linear copy was released (vr_hip_release_linear_copy): the brick copies cannot be rebuilt or dropped");
+	if (const int rc = need_linear(c, "the brick copies cannot be rebuilt or dropped")) return rc;
 	c->layout = layout;
 	free_bricks(c);
-	c->map_cached = 0; c->map_next = 0;
+	forget_tile_mappings(c);
 	return VR_OK;
 }
 
@@ -1223,8 +1279,7 @@ int vr_hip_set_wide_addressing(vr_ctx *c, uint32_t force) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	// The index-arithmetic path (1) reads the linear array for NEAREST: refused once that array was released (the frame
 	// would otherwise be launched with a NULL volume pointer).  launch_frame checks the same for every frame.
-	if ((force & 3u) == 1u && c->vol == nullptr && c->dim[0] != 0)
-		return fail(c, VR_ERR_NOT_READY, "the linear copy was released (vr_hip_release_linear_copy): the index-arithmetic path needs it");
+	if ((force & 3u) == 1u) if (const int rc = need_linear(c, "the index-arithmetic path needs it")) return rc;
 	c->force_wide = force & 3u;                  // 0 auto, 1 arithmetic 64-bit path, 2 table path with 64-bit z offsets
 	c->force_clamp_fetch = (force >> 2) & 3u;    // + 4: clamp the fetch coordinates of every sample (far-away views do that);
 	                                             // + 8: NEAREST never marches in the scaled domain (volumes with power-of-two edges do)
@@ -1236,7 +1291,7 @@ int vr_hip_set_brick_plane(vr_ctx *c, int32_t plane) {
 	if (plane == (int32_t) kPlanes + 5 || plane == (int32_t) kPlanes + 6) {      // 8 / 9: the column windows for every orthogonal full-march frame / never
 		c->column_force = plane == (int32_t) kPlanes + 5 ? 1 : -1;
 		c->oct_always = false; c->brick_plane_force = -1;
-		c->map_cached = 0; c->map_next = 0;
+		forget_tile_mappings(c);
 		return VR_OK;
 	}
 	c->column_force = 0;
@@ -1246,7 +1301,7 @@ int vr_hip_set_brick_plane(vr_ctx *c, int32_t plane) {
 		                               "8 (column windows for every orthogonal full-march frame) or 9 (never the column windows)");
 	c->oct_always = plane == (int32_t) kPlanes + 2;
 	c->brick_plane_force = c->oct_always ? -1 : plane;
-	c->map_cached = 0; c->map_next = 0;          // cached lane orders were chosen for another plane
+	forget_tile_mappings(c);                     // cached lane orders were chosen for another plane
 	return VR_OK;
 }
 
@@ -1261,8 +1316,7 @@ int vr_hip_set_tile_scheduling(vr_ctx *c, uint32_t mode) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (mode > 2u) return fail(c, VR_ERR_INVALID, "tile scheduling mode must be 0 (workgroup id), 1 (measured-cost order) or 2 (workgroup id + cost map)");
 	c->tile_scheduling = mode;
-	for (auto &e : c->map_cache) { e.dual_state = 0; e.order_tiles = 0; }
-	for (auto &e : c->order_cache) { e.has_last = false; e.repeats = 0; for (auto &sl : e.slot) sl.valid = false; }      // (buffers and last-use marks stay: recycled only when free)
+	forget_recorded_orders(c);
 	return VR_OK;
 }
 
@@ -1301,27 +1355,14 @@ int vr_hip_set_tile_mapping(vr_ctx *c, int32_t lane_map, uint32_t phase_x, uint3
 }
 
 int vr_hip_render_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
-	if (c == nullptr) return VR_ERR_INVALID;
-	if (dev_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");      // GPURenderer1.cu:101-102
-	int rc = validate_params(c, p);
-	if (rc) return rc;
-	rc = ready(c);
-	if (rc) return rc;
-	VR_TRY(c, hipSetDevice(c->device));
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
 	return launch_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
 }
 
 int vr_hip_render(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
-	if (c == nullptr) return VR_ERR_INVALID;
-	if (host_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");
-	int rc = validate_params(c, p);
-	if (rc) return rc;
-	rc = ready(c);
+	int rc = render_preamble(c, p, host_rgba, true);
 	if (rc) return rc;
 	const size_t bytes = (size_t) p->out_width * p->out_rows * 4;
-	if (c->fb == nullptr || bytes > c->fb_bytes)
-		return fail(c, VR_ERR_NOT_READY, "output larger than the window buffer: call vr_hip_set_window first");
-	VR_TRY(c, hipSetDevice(c->device));
 	const auto t0 = std::chrono::steady_clock::now();
 	// The reference's timed region ends with the frame in HOST memory (GPURenderer1.cu:107-110).  A frame of unpartitioned rows is
 	// rendered as TWO row slices: the first on a stream of the highest priority, so that its workgroups are dispatched ahead of the
@@ -1345,48 +1386,26 @@ int vr_hip_render(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 		VR_TRY(c, hipMemcpyAsync(host_rgba + first_bytes, (uint8_t *) c->fb + first_bytes, bytes - first_bytes, hipMemcpyDeviceToHost, c->stream));
 		VR_TRY(c, hipStreamSynchronize(c->stream_first));
 		VR_TRY(c, hipStreamSynchronize(c->stream));
-	} else {
-		rc = launch_frame(c, p, c->fb, c->stream);
-		if (rc) return rc;
-		VR_TRY(c, hipMemcpyAsync(host_rgba, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
-		VR_TRY(c, hipStreamSynchronize(c->stream));
+		take_total_time(c, t0);
+		return VR_OK;
 	}
-	const auto t1 = std::chrono::steady_clock::now();
-	c->last_total_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-	if (c->last_total_ms > c->total_ms_max) c->total_ms_max = c->last_total_ms;
-	return VR_OK;
+	rc = launch_frame(c, p, c->fb, c->stream);
+	if (rc) return rc;
+	return frame_to_host(c, host_rgba, bytes, t0);
 }
 
 int vr_hip_render_mip_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
-	if (c == nullptr) return VR_ERR_INVALID;
-	if (dev_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");
-	int rc = validate_params(c, p);
-	if (rc) return rc;
-	rc = ready(c);
-	if (rc) return rc;
-	VR_TRY(c, hipSetDevice(c->device));
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
 	return launch_mip_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
 }
 
 int vr_hip_render_mip(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
-	if (c == nullptr) return VR_ERR_INVALID;
-	if (host_rgba == nullptr) return fail(c, VR_ERR_INVALID, "buffer is NULL");
-	int rc = validate_params(c, p);
+	int rc = render_preamble(c, p, host_rgba, true);
 	if (rc) return rc;
-	rc = ready(c);
-	if (rc) return rc;
-	const size_t bytes = (size_t) p->out_width * p->out_rows * 4;
-	if (c->fb == nullptr || bytes > c->fb_bytes)
-		return fail(c, VR_ERR_NOT_READY, "output larger than the window buffer: call vr_hip_set_window first");
-	VR_TRY(c, hipSetDevice(c->device));
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = launch_mip_frame(c, p, c->fb, c->stream);
 	if (rc) return rc;
-	VR_TRY(c, hipMemcpyAsync(host_rgba, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
-	VR_TRY(c, hipStreamSynchronize(c->stream));
-	c->last_total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	if (c->last_total_ms > c->total_ms_max) c->total_ms_max = c->last_total_ms;
-	return VR_OK;
+	return frame_to_host(c, host_rgba, (size_t) p->out_width * p->out_rows * 4, t0);
 }
 
 #ifdef VR_MIP_STATS
@@ -1428,7 +1447,8 @@ int vr_hip_timing_reset(vr_ctx *c) {
 int vr_hip_volume_minmax(vr_ctx *c, uint8_t *minmax_out, uint32_t *bd_out, float *bs_out, float *kernel_ms_out) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (minmax_out == nullptr) return fail(c, VR_ERR_INVALID, "minmax_out is NULL");
-	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, c->dim[0] ? "the linear copy was released (vr_hip_release_linear_copy): set the volume again" : "minmax before set_volume");
+	if (const int rc = need_linear(c, "set the volume again")) return rc;
+	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, "minmax before set_volume");
 	VR_TRY(c, hipSetDevice(c->device));
 	const uint32_t bd = volume_block_dims(c);
 	VR_TRY(c, hipEventRecord(c->aux_start, c->stream));
@@ -1449,7 +1469,8 @@ int vr_hip_volume_minmax(vr_ctx *c, uint8_t *minmax_out, uint32_t *bd_out, float
 int vr_hip_volume_histogram(vr_ctx *c, uint64_t *hist_out, float *kernel_ms_out) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (hist_out == nullptr) return fail(c, VR_ERR_INVALID, "hist_out is NULL");
-	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, c->dim[0] ? "the linear copy was released (vr_hip_release_linear_copy): set the volume again" : "histogram before set_volume");
+	if (const int rc = need_linear(c, "set the volume again")) return rc;
+	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, "histogram before set_volume");
 	VR_TRY(c, hipSetDevice(c->device));
 	VR_TRY(c, hipEventRecord(c->aux_start, c->stream));
 	VR_TRY(c, launch_histogram(c->vol, c->bpv, c->vol_elems, c->hist, c->stream));
@@ -1476,7 +1497,8 @@ int vr_hip_generate_volume(vr_ctx *c, uint32_t kind, uint32_t n, uint32_t seed, 
 int vr_hip_download_volume(vr_ctx *c, void *host_out, uint64_t bytes) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (host_out == nullptr) return fail(c, VR_ERR_INVALID, "host_out is NULL");
-	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, c->dim[0] ? "the linear copy was released (vr_hip_release_linear_copy): set the volume again" : "download before set_volume");
+	if (const int rc = need_linear(c, "set the volume again")) return rc;
+	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, "download before set_volume");
 	if (bytes != c->vol_elems * c->bpv) return fail(c, VR_ERR_INVALID, "byte count does not match the resident volume");
 	VR_TRY(c, hipSetDevice(c->device));
 	VR_TRY(c, hipMemcpy(host_out, c->vol, bytes, hipMemcpyDeviceToHost));
@@ -1516,12 +1538,12 @@ int vr_hip_prepare(vr_ctx *c, uint32_t copies) {
 	int worst = VR_OK;
 	for (uint32_t k = 0; k < kCopyKinds; k++) {
 		if (!((copies >> k) & 1u) || c->copy[k] || !copy_in_policy(c, k)) continue;      // copies the policy does not have at this size are skipped
-		if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, "the linear copy was released (vr_hip_release_linear_copy): set the volume again");
+		if (const int rc = need_linear(c, "set the volume again")) return rc;
 		c->copy_failed[k] = false;                   // an explicit request retries an earlier refusal
 		const int rc = build_copy(c, k);
 		if (rc != VR_OK && worst == VR_OK) { worst = rc; if (c->err.empty() || rc == VR_ERR_ALLOC) fail(c, rc, "a brick copy was not built (less than half of the HBM would stay free, or allocation failed)"); }
 	}
-	if (copies) { c->map_cached = 0; c->map_next = 0; }
+	if (copies) forget_tile_mappings(c);
 	return worst;
 }
 

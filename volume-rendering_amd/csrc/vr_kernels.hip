@@ -585,6 +585,101 @@ __device__ __forceinline__ float rlane(float v, int lane) { return __uint_as_flo
 template <typename T> __device__ __forceinline__ void hold_scalar(const T &v) { asm volatile("" :: "s"(v)); }
 template <typename... T> __device__ __forceinline__ void hold_scalars(const T &...v) { (void) std::initializer_list<int>{ (hold_scalar(v), 0)... }; }
 
+// -- lane -> pixel of the frame buffer, for a workgroup of THREADS threads on tile (tile_x, tile_y): lx / ly wrap for the pixels left of /
+//    below the buffer (tile phase).  One wavefront = one 8x8 pixel tile; 8 waves = 32x16 pixels, 16 waves = 32x32.  Inside the wave each
+//    group of 16 consecutive lanes is a 4x4-pixel block (not two 8-pixel rows): a compact block keeps the group's samples inside the
+//    fewest cache sectors whatever the view direction.  SQUARE_WAVES: the wave shape is 8x8 whatever lane_map says (the column kernels).
+template <uint32_t THREADS, bool SQUARE_WAVES = false>
+__device__ __forceinline__ void lane_pixel(const RayKernelArgs &a, uint32_t tile_x, uint32_t tile_y, uint32_t &lx, uint32_t &ly) {
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint32_t qd = lane >> 4;
+	// Order of the 16 lanes inside the group, picked per frame by the host (vr_hip_api.cpp choose_tile_mapping): the vector
+	// memory pipeline handles 4 consecutive lanes together and is fastest when their addresses share one aligned 16-byte
+	// chunk, so the 4 lanes should be the 4 pixels whose samples lie closest together in the brick order.
+	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;                             // kLaneRows: lanes run along screen x
+	const uint32_t order = a.lane_map & 3u, shape = THREADS == 512u && !SQUARE_WAVES ? (a.lane_map >> 2) : 0u;
+	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
+	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
+	// Shape of the wave's pixel tile inside the 32x16-pixel workgroup tile (bits 2.. of lane_map): 0 = 8x8 (four 4x4 groups as 2x2),
+	// 1 = 16 wide x 4 high (the groups side by side; the 8 waves 2 across x 4 down), 2 = 4 wide x 16 high (8 waves across).
+	uint32_t wx, wy, ox, oy;
+	if (shape == 1u) { wx = qd * 4u + gu; wy = gv; ox = (wave & 1u) * 16u; oy = (wave >> 1) * 4u; }
+	else if (shape == 2u) { wx = gu; wy = qd * 4u + gv; ox = wave * 4u; oy = 0u; }
+	else { wx = (qd & 1u) * 4u + gu; wy = (qd >> 1) * 4u + gv; ox = (wave & 3u) * 8u; oy = (wave >> 2) * 8u; }
+	lx = tile_x * 32u + ox + wx - a.phase_x;
+	ly = tile_y * (THREADS / 32u) + oy + wy - a.phase_y;
+}
+// row of the frame buffer -> row of the view (the band partition of vr_render_params)
+__device__ __forceinline__ uint32_t frame_row(const RayKernelArgs &a, uint32_t ly) {
+	const uint32_t band = ly / a.p.band_rows;
+	return (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
+}
+
+// -- the ray of view pixel (gx, gy): View::get_ray (ViewBase.h:23-35, its order of operations), Raycaster::intersect and the
+//    termination guard, once per ray instead of a counter per sample: k advances by `step` every iteration as long as
+//    ky + step != ky (fp32 spacing grows with magnitude, so that holds for every k <= ky), and the march is cut after
+//    kMaxRaySteps steps.  Neither condition can trigger for a view the reference can produce (k spans <= 2*sqrt(3)).
+//    Returned by value, the view read by index: handed out through references (or read through ld3) the ray lands in scratch.
+//    ORTHOGONAL: for kernels the host never launches for a perspective view — their direction stays the wave-uniform kernel argument.
+struct PixelRay { f3 origin, dir; float kx, ky; bool alive; };
+template <bool ORTHOGONAL = false>
+__device__ __forceinline__ PixelRay pixel_ray(const RayKernelArgs &a, uint32_t gx, uint32_t gy) {
+	PixelRay r;
+	const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u));
+	const float fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
+	const f3 vo = mk3(a.p.view.origin[0], a.p.view.origin[1], a.p.view.origin[2]);
+	const f3 vd = mk3(a.p.view.direction[0], a.p.view.direction[1], a.p.view.direction[2]);
+	const f3 vr_ = mk3(a.p.view.right_plane[0], a.p.view.right_plane[1], a.p.view.right_plane[2]);
+	const f3 vu = mk3(a.p.view.up_plane[0], a.p.view.up_plane[1], a.p.view.up_plane[2]);
+	if (!ORTHOGONAL && a.p.view.perspective) {
+		r.origin = vo;
+		r.dir = mk3(vd.x + vr_.x * fx, vd.y + vr_.y * fx, vd.z + vr_.z * fx);
+		r.dir = mk3(r.dir.x + vu.x * fy, r.dir.y + vu.y * fy, r.dir.z + vu.z * fy);
+	} else {
+		r.dir = vd;
+		r.origin = mk3(vo.x + vr_.x * fx, vo.y + vr_.y * fx, vo.z + vr_.z * fx);
+		r.origin = mk3(r.origin.x + vu.x * fy, r.origin.y + vu.y * fy, r.origin.z + vu.z * fy);
+	}
+	r.kx = 0; r.ky = 0;
+	r.alive = gx < a.p.view.width && gy < a.p.view.height;
+	r.alive = r.alive && intersect(r.origin, r.dir, r.kx, r.ky);
+	const float step = a.p.ray_step;
+	r.alive = r.alive && (r.ky + step > r.ky);
+	r.ky = flmin(r.ky, r.kx + step * (float) kMaxRaySteps);
+	return r;
+}
+
+// -- the address tables of the quad / voxel / oct bricks into LDS; no barrier.  Entry j of a table belongs to cell
+//    clamp(j - kLutPad, 0, dim - 1): the pad entries repeat the edge cells.
+__device__ __forceinline__ uint32_t lut_cell_of(uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); }
+template <int BPV, int ADDR, int LAYOUT>
+__device__ __forceinline__ void stage_brick_tables(const RayKernelArgs &a, uint32_t *lut) {
+	typedef LutCfg<ADDR> L;
+	constexpr uint32_t kThreads = L::threads;
+	const uint32_t t = threadIdx.x;
+	const uint32_t nx = a.dim_x, ny = a.dim_y, nz = a.dim_z;
+	const uint32_t elem = LAYOUT == kLayoutVoxel ? BPV : (LAYOUT == kLayoutOct ? 8u * BPV : 4u * BPV);   // bytes per element: one voxel, a quad, or the 2x2x2 neighbourhood
+#ifdef VR_BOUNDS_CHECK
+	if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = ny + 2 * kLutPad; bc_table_entries[2] = nz + 2 * kLutPad; }
+#endif
+	const uint32_t row = a.nbx * kBrickPitch;                        // elements per brick row / slab
+	const uint64_t slab = (uint64_t) a.nby * row;
+	for (uint32_t jj = t; jj < nz + 2 * kLutPad; jj += kThreads) {
+		const uint32_t i = lut_cell_of(jj, nz);
+		const uint32_t j = i + 1 < nz ? i + 1 : i;
+		const uint64_t z0 = ((i >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, i & 7u)) * elem;
+		const uint64_t z1 = ((j >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, j & 7u)) * elem;
+		if (ADDR == kAddr32) {
+			lut[2 * jj] = (uint32_t) z0; lut[2 * jj + 1] = (uint32_t) z1;
+		} else {
+			lut[4 * jj] = (uint32_t) z0; lut[4 * jj + 1] = (uint32_t) (z0 >> 32);
+			lut[4 * jj + 2] = (uint32_t) z1; lut[4 * jj + 3] = (uint32_t) (z1 >> 32);
+		}
+	}
+	for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, nx); lut[L::x_at + j] = ((i >> 3) * kBrickPitch + brick_spread(BPV, a.brick_plane, 0, i & 7u)) * elem; }
+	for (uint32_t j = t; j < ny + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, ny); lut[L::y_at + j] = ((i >> 3) * row + brick_spread(BPV, a.brick_plane, 1, i & 7u)) * elem; }
+}
+
 // ---- the ray-march kernel ------------------------------------------------------------------------------------------
 
 template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
@@ -638,8 +733,6 @@ void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const 
 	// -- stage TF (+ deltas), the ESL bit-volume and the brick address tables in LDS
 	{
 		const uint32_t t = threadIdx.x;
-		// entry j of a table belongs to cell clamp(j - kLutPad, 0, dim - 1): the pad entries repeat the edge cells
-		auto cell_of = [](uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); };
 		if (kUseLut && is_run_layout(LAYOUT)) {
 			// r = the run axis (z, or y for kLayoutRunY), o = the other column axis (y, or z); bricks: x fastest, then o, then r.
 			// kLayoutRunDual: a tile that reads the copy along y builds ITS tables exactly like kLayoutRunY and marches with the
@@ -653,35 +746,13 @@ void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const 
 			if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = no + 2 * kLutPad; bc_table_entries[2] = nr + 2 * kLutPad; }
 #endif
 			for (uint32_t j = t; j < nr + 2 * kLutPad; j += kThreads) {
-				const uint32_t i = cell_of(j, nr);
+				const uint32_t i = lut_cell_of(j, nr);
 				const uint64_t z0 = copy_base + (i >> 3) * slab + (i & 7u) * 4u;
 				lut[2 * j] = (uint32_t) z0; lut[2 * j + 1] = (uint32_t) (z0 >> 32);
 			}
-			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, nx); lut[L::x_at + j] = (i >> 3) * kRunBrickBytes + run_cell_spread(0, i & 7u); }
-			for (uint32_t j = t; j < no + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, no); lut[L::y_at + j] = (i >> 3) * a.nbx * kRunBrickBytes + run_cell_spread(1, i & 7u); }
-		} else if (kUseLut) {
-			const uint32_t nx = a.dim_x, ny = a.dim_y, nz = a.dim_z;
-			const uint32_t elem = LAYOUT == kLayoutVoxel ? BPV : (LAYOUT == kLayoutOct ? 8u * BPV : 4u * BPV);   // bytes per element: one voxel, a quad, or the 2x2x2 neighbourhood
-#ifdef VR_BOUNDS_CHECK
-			if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = ny + 2 * kLutPad; bc_table_entries[2] = nz + 2 * kLutPad; }
-#endif
-			const uint32_t row = a.nbx * kBrickPitch;                        // elements per brick row / slab
-			const uint64_t slab = (uint64_t) a.nby * row;
-			for (uint32_t jj = t; jj < nz + 2 * kLutPad; jj += kThreads) {
-				const uint32_t i = cell_of(jj, nz);
-				const uint32_t j = i + 1 < nz ? i + 1 : i;
-				const uint64_t z0 = ((i >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, i & 7u)) * elem;
-				const uint64_t z1 = ((j >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, j & 7u)) * elem;
-				if (ADDR == kAddr32) {
-					lut[2 * jj] = (uint32_t) z0; lut[2 * jj + 1] = (uint32_t) z1;
-				} else {
-					lut[4 * jj] = (uint32_t) z0; lut[4 * jj + 1] = (uint32_t) (z0 >> 32);
-					lut[4 * jj + 2] = (uint32_t) z1; lut[4 * jj + 3] = (uint32_t) (z1 >> 32);
-				}
-			}
-			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, nx); lut[L::x_at + j] = ((i >> 3) * kBrickPitch + brick_spread(BPV, a.brick_plane, 0, i & 7u)) * elem; }
-			for (uint32_t j = t; j < ny + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, ny); lut[L::y_at + j] = ((i >> 3) * row + brick_spread(BPV, a.brick_plane, 1, i & 7u)) * elem; }
-		}
+			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, nx); lut[L::x_at + j] = (i >> 3) * kRunBrickBytes + run_cell_spread(0, i & 7u); }
+			for (uint32_t j = t; j < no + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, no); lut[L::y_at + j] = (i >> 3) * a.nbx * kRunBrickBytes + run_cell_spread(1, i & 7u); }
+		} else if constexpr (kUseLut) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);      // (kUseLut: not the linear array, so L is LutCfg<ADDR>)
 		if (t <= VR_TF_SIZE) {
 			const f4 *tf4 = (const f4 *) tf_g;
 			uint32_t i0 = t < VR_TF_SIZE ? t : VR_TF_SIZE - 1;
@@ -699,59 +770,18 @@ void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const 
 	uint32_t tile_x, tile_y;
 	tile_to_xy(a.tiles_x, a.tiles_y, tile_of_group, blockIdx.x, tile_x, tile_y);
 
-	// -- one wavefront = one 8x8 pixel tile; 8 waves = 32x16 pixels, 16 waves = 32x32.  Inside the wave each group of 16
-	//    consecutive lanes is a 4x4-pixel block (not two 8-pixel rows): a compact block keeps the group's samples inside the
-	//    fewest cache sectors whatever the view direction.
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	const uint32_t qd = lane >> 4;
-	// Order of the 16 lanes inside the group, picked per frame by the host (vr_hip_api.cpp choose_tile_mapping): the vector
-	// memory pipeline handles 4 consecutive lanes together and is fastest when their addresses share one aligned 16-byte
-	// chunk, so the 4 lanes should be the 4 pixels whose samples lie closest together in the brick order.
-	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;                             // kLaneRows: lanes run along screen x
-	const uint32_t order = a.lane_map & 3u, shape = kThreads == 512u ? (a.lane_map >> 2) : 0u;
-	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
-	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
-	// Shape of the wave's pixel tile inside the 32x16-pixel workgroup tile (bits 2.. of lane_map): 0 = 8x8 (four 4x4 groups as 2x2),
-	// 1 = 16 wide x 4 high (the groups side by side; the 8 waves 2 across x 4 down), 2 = 4 wide x 16 high (8 waves across).
-	uint32_t wx, wy, ox, oy;
-	if (shape == 1u) { wx = qd * 4u + gu; wy = gv; ox = (wave & 1u) * 16u; oy = (wave >> 1) * 4u; }
-	else if (shape == 2u) { wx = gu; wy = qd * 4u + gv; ox = wave * 4u; oy = 0u; }
-	else { wx = (qd & 1u) * 4u + gu; wy = (qd >> 1) * 4u + gv; ox = (wave & 3u) * 8u; oy = (wave >> 2) * 8u; }
-	const uint32_t lx = tile_x * 32u + ox + wx - a.phase_x;                      // wraps for the pixels left of / below the buffer
-	const uint32_t ly = tile_y * (kThreads / 32u) + oy + wy - a.phase_y;
+	uint32_t lx, ly;
+	lane_pixel<kThreads>(a, tile_x, tile_y, lx, ly);
 	if (lx >= a.p.out_width || ly >= a.p.out_rows)
 		return;                                     // no barrier below this point
-	const uint32_t band = ly / a.p.band_rows;
-	const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
-	const uint32_t gx = a.p.x0 + lx;
+	const uint32_t lane = threadIdx.x & 63u;
 	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
 
-	// -- View::get_ray (ViewBase.h:23-35)
-	f3 origin, dir;
-	bool alive = gx < a.p.view.width && gy < a.p.view.height;
-	{
-		const f3 vo = ld3(a.p.view.origin), vd = ld3(a.p.view.direction);
-		const f3 vr_ = ld3(a.p.view.right_plane), vu = ld3(a.p.view.up_plane);
-		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u));
-		const float fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
-		if (a.p.view.perspective) {
-			origin = vo;
-			dir = mk3(vd.x + vr_.x * fx, vd.y + vr_.y * fx, vd.z + vr_.z * fx);
-			dir = mk3(dir.x + vu.x * fy, dir.y + vu.y * fy, dir.z + vu.z * fy);
-		} else {
-			dir = vd;
-			origin = mk3(vo.x + vr_.x * fx, vo.y + vr_.y * fx, vo.z + vr_.z * fx);
-			origin = mk3(origin.x + vu.x * fy, origin.y + vu.y * fy, origin.z + vu.z * fy);
-		}
-	}
-	float kx = 0, ky = 0;
-	alive = alive && intersect(origin, dir, kx, ky);
+	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
+	f3 origin = ray.origin, dir = ray.dir;
+	float kx = ray.kx, ky = ray.ky;
 	const float step = a.p.ray_step;
-	// Termination guard, once per ray instead of a counter per sample: k advances by `step` every iteration as long as
-	// ky + step != ky (fp32 spacing grows with magnitude, so that holds for every k <= ky), and the march is cut after
-	// kMaxRaySteps steps.  Neither condition can trigger for a view the reference can produce (k spans <= 2*sqrt(3)).
-	alive = alive && (ky + step > ky);
-	ky = flmin(ky, kx + step * (float) kMaxRaySteps);
+	bool alive = ray.alive;
 	const bool hit = alive;
 	f3 pt = march_point<SAMPLING>(origin, dir, kx);
 
@@ -1219,35 +1249,19 @@ __device__ __forceinline__ f3 col_origin_again(const f4 (&org_l)[512], uint32_t 
 __device__ __forceinline__ void col_ray_setup(const RayKernelArgs &a, f4 (&org_l)[512], ColRay &r) {
 	uint32_t tile_x, tile_y;
 	tile_to_xy<VR_COL_XCD_MODE>(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
-	// pixel of this lane: the general kernel's mapping (lane order, 8x8 waves, tile phase)
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, qd = lane >> 4;
-	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;
-	const uint32_t order = a.lane_map & 3u;
-	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
-	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
-	const uint32_t wx = (qd & 1u) * 4u + gu, wy = (qd >> 1) * 4u + gv, ox = (wave & 3u) * 8u, oy = (wave >> 2) * 8u;
-	const uint32_t lx = tile_x * 32u + ox + wx - a.phase_x, ly = tile_y * 16u + oy + wy - a.phase_y;
+	uint32_t lx, ly;
+	lane_pixel<512u, true>(a, tile_x, tile_y, lx, ly);
 	r.in_frame = lx < a.p.out_width && ly < a.p.out_rows;
-	const uint32_t band = ly / a.p.band_rows;
-	const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
-	const uint32_t gx = a.p.x0 + lx;
 	r.out_index = r.in_frame ? ly * a.p.out_width + lx : 0xffffffffu;
 
-	// -- View::get_ray (ViewBase.h:23-35), orthogonal branch only (the host never launches these kernels for a perspective view)
-	bool alive = r.in_frame && gx < a.p.view.width && gy < a.p.view.height;
-	r.dir = ld3(a.p.view.direction);
-	{
-		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u)), fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
-		const f3 o = mk3(a.p.view.origin[0] + a.p.view.right_plane[0] * fx, a.p.view.origin[1] + a.p.view.right_plane[1] * fx, a.p.view.origin[2] + a.p.view.right_plane[2] * fx);
-		r.origin = mk3(o.x + a.p.view.up_plane[0] * fy, o.y + a.p.view.up_plane[1] * fy, o.z + a.p.view.up_plane[2] * fy);
-	}
+	// (perspective is wave-uniform and never true here: the host never launches these kernels for a perspective view)
+	const PixelRay ray = pixel_ray<true>(a, a.p.x0 + lx, frame_row(a, ly));
+	r.dir = ray.dir; r.origin = ray.origin;
 	r.org_slot = threadIdx.x * (uint32_t) sizeof(f4);
 	{ f4 o4; o4.x = r.origin.x; o4.y = r.origin.y; o4.z = r.origin.z; o4.w = 0.0f; org_l[threadIdx.x] = o4; }      // read by this thread only: no barrier
-	r.kx = 0; r.ky = 0;
-	alive = alive && intersect(r.origin, r.dir, r.kx, r.ky);
+	r.kx = ray.kx; r.ky = ray.ky;
 	r.step = a.p.ray_step;
-	alive = alive && (r.ky + r.step > r.ky);                                 // termination guard (see raymarch_kernel)
-	r.ky = flmin(r.ky, r.kx + r.step * (float) kMaxRaySteps);
+	const bool alive = r.in_frame && ray.alive;
 	r.alive = alive;
 	r.alive_mask = __builtin_amdgcn_ballot_w64(alive);
 	if (!alive) r.ky = -1.0f;
@@ -2119,36 +2133,6 @@ void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, 
 constexpr int kMipBatch = VR_MIP_BATCH;
 extern __shared__ __attribute__((aligned(16))) uint8_t mip_bound_lds[];      // kMipBoundEntries bytes of dynamic LDS, only for frames that skip
 
-// the address tables of the quad / voxel / oct bricks into LDS, as raymarch_kernel stages them for these layouts; no barrier
-template <int BPV, int ADDR, int LAYOUT>
-__device__ __forceinline__ void stage_brick_tables(const RayKernelArgs &a, uint32_t *lut) {
-	typedef LutCfg<ADDR> L;
-	constexpr uint32_t kThreads = L::threads;
-	const uint32_t t = threadIdx.x;
-	auto cell_of = [](uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); };
-	const uint32_t nx = a.dim_x, ny = a.dim_y, nz = a.dim_z;
-	const uint32_t elem = LAYOUT == kLayoutVoxel ? BPV : (LAYOUT == kLayoutOct ? 8u * BPV : 4u * BPV);
-#ifdef VR_BOUNDS_CHECK
-	if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = ny + 2 * kLutPad; bc_table_entries[2] = nz + 2 * kLutPad; }
-#endif
-	const uint32_t row = a.nbx * kBrickPitch;
-	const uint64_t slab = (uint64_t) a.nby * row;
-	for (uint32_t jj = t; jj < nz + 2 * kLutPad; jj += kThreads) {
-		const uint32_t i = cell_of(jj, nz);
-		const uint32_t j = i + 1 < nz ? i + 1 : i;
-		const uint64_t z0 = ((i >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, i & 7u)) * elem;
-		const uint64_t z1 = ((j >> 3) * slab + brick_spread(BPV, a.brick_plane, 2, j & 7u)) * elem;
-		if (ADDR == kAddr32) {
-			lut[2 * jj] = (uint32_t) z0; lut[2 * jj + 1] = (uint32_t) z1;
-		} else {
-			lut[4 * jj] = (uint32_t) z0; lut[4 * jj + 1] = (uint32_t) (z0 >> 32);
-			lut[4 * jj + 2] = (uint32_t) z1; lut[4 * jj + 3] = (uint32_t) (z1 >> 32);
-		}
-	}
-	for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, nx); lut[L::x_at + j] = ((i >> 3) * kBrickPitch + brick_spread(BPV, a.brick_plane, 0, i & 7u)) * elem; }
-	for (uint32_t j = t; j < ny + 2 * kLutPad; j += kThreads) { const uint32_t i = cell_of(j, ny); lut[L::y_at + j] = ((i >> 3) * row + brick_spread(BPV, a.brick_plane, 1, i & 7u)) * elem; }
-}
-
 template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
 __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
 void mip_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
@@ -2169,51 +2153,19 @@ void mip_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float
 	}
 	__syncthreads();
 
-	// -- workgroup -> tile -> pixel, as raymarch_kernel (tile = workgroup id: every ray of a MIP frame without skipping is a full march)
-	uint32_t tile_x, tile_y;
+	// -- tile = workgroup id: every ray of a MIP frame without skipping is a full march
+	uint32_t tile_x, tile_y, lx, ly;
 	tile_to_xy(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	const uint32_t qd = lane >> 4;
-	uint32_t gu = lane & 3u, gv = (lane >> 2) & 3u;
-	const uint32_t order = a.lane_map & 3u, shape = kThreads == 512u ? (a.lane_map >> 2) : 0u;
-	if (order == kLaneBlocks) { gu = ((lane >> 1) & 2u) | (lane & 1u); gv = ((lane >> 2) & 2u) | ((lane >> 1) & 1u); }
-	else if (order == kLaneColumns) { const uint32_t t = gu; gu = gv; gv = t; }
-	uint32_t wx, wy, ox, oy;
-	if (shape == 1u) { wx = qd * 4u + gu; wy = gv; ox = (wave & 1u) * 16u; oy = (wave >> 1) * 4u; }
-	else if (shape == 2u) { wx = gu; wy = qd * 4u + gv; ox = wave * 4u; oy = 0u; }
-	else { wx = (qd & 1u) * 4u + gu; wy = (qd >> 1) * 4u + gv; ox = (wave & 3u) * 8u; oy = (wave >> 2) * 8u; }
-	const uint32_t lx = tile_x * 32u + ox + wx - a.phase_x;
-	const uint32_t ly = tile_y * (kThreads / 32u) + oy + wy - a.phase_y;
+	lane_pixel<kThreads>(a, tile_x, tile_y, lx, ly);
 	if (lx >= a.p.out_width || ly >= a.p.out_rows)
 		return;                                     // no barrier below this point
-	const uint32_t band = ly / a.p.band_rows;
-	const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows);
-	const uint32_t gx = a.p.x0 + lx;
 	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
 
-	// -- View::get_ray (ViewBase.h:23-35) and Raycaster::intersect, as raymarch_kernel
-	f3 origin, dir;
-	bool alive = gx < a.p.view.width && gy < a.p.view.height;
-	{
-		const f3 vo = ld3(a.p.view.origin), vd = ld3(a.p.view.direction);
-		const f3 vr_ = ld3(a.p.view.right_plane), vu = ld3(a.p.view.up_plane);
-		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u));
-		const float fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
-		if (a.p.view.perspective) {
-			origin = vo;
-			dir = mk3(vd.x + vr_.x * fx, vd.y + vr_.y * fx, vd.z + vr_.z * fx);
-			dir = mk3(dir.x + vu.x * fy, dir.y + vu.y * fy, dir.z + vu.z * fy);
-		} else {
-			dir = vd;
-			origin = mk3(vo.x + vr_.x * fx, vo.y + vr_.y * fx, vo.z + vr_.z * fx);
-			origin = mk3(origin.x + vu.x * fy, origin.y + vu.y * fy, origin.z + vu.z * fy);
-		}
-	}
-	float kx = 0, ky = 0;
-	alive = alive && intersect(origin, dir, kx, ky);
+	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
+	f3 origin = ray.origin, dir = ray.dir;
+	float kx = ray.kx, ky = ray.ky;
 	const float step = a.p.ray_step;
-	alive = alive && (ky + step > ky);              // the termination guard of raymarch_kernel
-	ky = flmin(ky, kx + step * (float) kMaxRaySteps);
+	const bool alive = ray.alive;
 	const bool hit = alive;
 	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a segment: position 0, never live
 
@@ -2448,20 +2400,25 @@ static void dispatch_axis_flag(uint32_t axis, bool flag, F &&f) {
 
 template <int ADDR, int LAYOUT> constexpr uint32_t variant_threads() { return LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads; }
 
+// workgroup tiles (32 pixels wide, threads / 32 high) that cover the frame buffer shifted by the tile phase
+static void tile_grid(uint32_t out_width, uint32_t out_rows, uint32_t phase_x, uint32_t phase_y, uint32_t threads, uint32_t &tiles_x, uint32_t &tiles_y) {
+	tiles_x = (out_width + phase_x + 31u) / 32u;
+	tiles_y = (out_rows + phase_y + threads / 32u - 1u) / (threads / 32u);
+}
+
 // what launch_raymarch will do with these arguments (launch_frame asks before it launches)
 RaymarchPlan plan_raymarch(const RayKernelArgs &a, bool have_bricked, uint32_t bpv) {
 	if (have_bricked && (a.layout == kLayoutColumn || a.layout == kLayoutVoxCol)) {      // the column kernels: 512 threads = 32x16 pixels
 		RaymarchPlan plan;
 		plan.reads_linear = false;
-		plan.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u; plan.tiles_y = (a.p.out_rows + a.phase_y + 15u) / 16u;
+		tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, 512u, plan.tiles_x, plan.tiles_y);
 		return plan;
 	}
 	return select_variant(a, have_bricked, bpv, [&](auto, auto, auto addr, auto layout, bool reads_linear) {
 		constexpr uint32_t threads = variant_threads<decltype(addr)::value, decltype(layout)::value>();
 		RaymarchPlan plan;
 		plan.reads_linear = reads_linear;
-		plan.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u;
-		plan.tiles_y = (a.p.out_rows + a.phase_y + threads / 32u - 1u) / (threads / 32u);
+		tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, plan.tiles_x, plan.tiles_y);
 		plan.tile_h = threads / 32u;
 		return plan;
 	});
@@ -2471,7 +2428,7 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
                            const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
 	if (bricked != nullptr && (args.layout == kLayoutColumn || args.layout == kLayoutVoxCol)) {      // orthogonal view along args.col_axis, full march, 1-byte voxels (launch_frame)
 		RayKernelArgs a = args;
-		a.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u; a.tiles_y = (a.p.out_rows + a.phase_y + 15u) / 16u;
+		tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, 512u, a.tiles_x, a.tiles_y);
 		const dim3 grid(a.tiles_x * a.tiles_y), block(512);
 		auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream, a, (const uint8_t *) bricked, tf, (uint32_t *) out); };
 		// lateral direction components exactly 0: no lane can change its column — the kernel without the flip logic
@@ -2492,8 +2449,7 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
 		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
 		constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
 		RayKernelArgs a = args;
-		a.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u;
-		a.tiles_y = (a.p.out_rows + a.phase_y + threads / 32u - 1u) / (threads / 32u);
+		tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
 		// Run-brick frames are launched with 16 KiB of unused dynamic LDS: 3 instead of 4 workgroups per CU (24 waves).  Their waves
 		// touch ~10 cache lines per step, 32 of them overflow the 256 lines of the 32 KiB L1 between two steps and the L2 catches only a
 		// quarter of that reuse (measured: fabric requests -11 %, frame time -2 ... -5 % on those views; the VALU-bound quad-brick views
@@ -2522,8 +2478,7 @@ hipError_t launch_mip(const RayKernelArgs &args, const void *linear, const void 
 		else {
 			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
 			RayKernelArgs a = args;
-			a.tiles_x = (a.p.out_width + a.phase_x + 31u) / 32u;
-			a.tiles_y = (a.p.out_rows + a.phase_y + threads / 32u - 1u) / (threads / 32u);
+			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
 			// the bound table is dynamic LDS, so that frames which do not skip keep every resident workgroup the address tables allow
 			const uint32_t dynamic_lds = a.p.esl != 0u ? kMipBoundEntries : 0u;
 			hipLaunchKernelGGL((mip_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
@@ -2611,7 +2566,6 @@ void tile_estimate_kernel(const RayKernelArgs a, uint32_t tile_h, const uint32_t
 	const uint32_t t = gid >> 3, probe = gid & 7u;                      // eight lanes per tile, one ray each
 	uint32_t tile_x = 0, tile_y = 0;
 	if (t < ntiles) tile_to_xy(a.tiles_x, a.tiles_y, t, t, tile_x, tile_y);
-	const f3 vo = ld3(a.p.view.origin), vd = ld3(a.p.view.direction), vr_ = ld3(a.p.view.right_plane), vu = ld3(a.p.view.up_plane);
 	const float edge = flmin(flmin(a.p.esl_block_size[0], a.p.esl_block_size[1]), a.p.esl_block_size[2]);
 	uint32_t best = 0;
 	do {
@@ -2620,15 +2574,10 @@ void tile_estimate_kernel(const RayKernelArgs a, uint32_t tile_h, const uint32_t
 		const uint32_t px = (probe & 3u) * 8u + 4u, py = (probe >> 2) * (tile_h / 2u) + tile_h / 4u;
 		const uint32_t lx = tile_x * 32u + px - a.phase_x, ly = tile_y * tile_h + py - a.phase_y;
 		if (lx >= a.p.out_width || ly >= a.p.out_rows) continue;
-		const uint32_t band = ly / a.p.band_rows;
-		const uint32_t gy = (band * a.p.band_stride + a.p.band_first) * a.p.band_rows + (ly - band * a.p.band_rows), gx = a.p.x0 + lx;
-		if (gx >= a.p.view.width || gy >= a.p.view.height) continue;
-		const float fx = (float) ((int) gx - (int) (a.p.view.width / 2u)), fy = (float) ((int) gy - (int) (a.p.view.height / 2u));
-		f3 origin = vo, dir = vd;
-		if (a.p.view.perspective) dir = mk3(vd.x + vr_.x * fx + vu.x * fy, vd.y + vr_.y * fx + vu.y * fy, vd.z + vr_.z * fx + vu.z * fy);
-		else origin = mk3(vo.x + vr_.x * fx + vu.x * fy, vo.y + vr_.y * fx + vu.y * fy, vo.z + vr_.z * fx + vu.z * fy);
-		float kx, ky;
-		if (!intersect(origin, dir, kx, ky)) continue;
+		const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
+		if (!ray.alive) continue;
+		const f3 origin = ray.origin, dir = ray.dir;
+		const float kx = ray.kx, ky = ray.ky;
 		const float longest = flmax(flmax(__builtin_fabsf(dir.x), __builtin_fabsf(dir.y)), __builtin_fabsf(dir.z));
 		const float dk = 0.5f * edge / flmax(longest, 1e-6f);
 		if (!(dk > 0.0f)) continue;
