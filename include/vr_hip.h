@@ -159,8 +159,14 @@ int vr_hip_set_brick_plane(vr_ctx *ctx, int32_t plane);
 
 /* Which copy the TRILINEAR frames that take the column march read: 0 = the windows of 16 plain voxels (VR_COPY_COLV_*, 1 byte per
  * voxel) wherever the host can bound the cell columns of every 8x8-pixel wave to 64 (default; the quad-element windows otherwise);
- * 1 = always the quad-element windows (VR_COPY_COL_*, 16/3 bytes per voxel; the round-4 march).  Speed only; A/B and testing aid.
- * No reference counterpart. */
+ * 1 = always the quad-element windows (VR_COPY_COL_*, 16/3 bytes per voxel; the round-4 march); 2 = as 0, but without the second
+ * copy described next.  In mode 0 a LIT frame (light_kd > 0.01) that marches over the voxel windows fetches its shading samples —
+ * positions a few cells off the ray, outside what the wave holds — from the quad-element windows of the same axis, one 8-byte load
+ * instead of eight byte loads: the first such frame along an axis builds that copy too (16/3 bytes per voxel: 5.35 GiB per axis at
+ * 1024^3 beside the 1 GiB of voxel windows; all three axes visited: about 16 GiB more than mode 2 holds).  Where it cannot be had
+ * (the half-of-the-HBM rule of vr_hip_prepare, an allocation failure, the linear array released) the frame shades by byte loads as
+ * in mode 2, with the same image; vr_launch_info::column_shade_pairs tells which.  Unlit frames never ask for it.  Mode 2 is the
+ * memory opt-out.  Speed only; A/B and testing aid.  No reference counterpart. */
 int vr_hip_set_column_copy(vr_ctx *ctx, uint32_t mode);
 
 /* Which pixels of a 4x4-pixel block share a lane quad, and where the tile grid starts: speed only, images are identical.
@@ -238,6 +244,8 @@ typedef struct vr_launch_info {
 	uint32_t straddle_permille;   /* orthogonal views along an axis: lane groups that still straddle cells under the chosen phase */
 	uint32_t column_voxels; /* layout 7 with TRILINEAR: 1 = the march read the windows of 16 plain voxels (VR_COPY_COLV_*), 0 = the
 	                           quad-element windows (VR_COPY_COL_*); vr_hip_set_column_copy */
+	uint32_t column_shade_pairs; /* column_voxels = 1: 1 = the shading samples were fetched from the quad-element windows (one 8-byte load
+	                           each), 0 = from the voxel windows (eight byte loads: unlit frames, mode 2, or that copy could not be had) */
 } vr_launch_info;
 int vr_hip_last_launch(vr_ctx *ctx, vr_launch_info *out);
 
@@ -322,7 +330,7 @@ uint32_t vr_hip_multi_default_band_rows(uint32_t height, uint32_t n);
 #define VR_COPY_COL_Y    (1u << 8)   /* elements along the axis in ONE aligned 16-byte word; what TRILINEAR reads for full-march frames of */
 #define VR_COPY_COL_Z    (1u << 9)   /* ORTHOGONAL views along that axis: one gather and one transparency test per ~3 samples (vr_device.h) */
 #define VR_COPY_COLV_X   (1u << 10)  /* the same for NEAREST: 16 consecutive VOXELS of a cell column in one aligned 16-byte word (1 byte per voxel): */
-#define VR_COPY_COLV_Y   (1u << 11)  /* one gather and one transparency test per sixteen samples; TRILINEAR reads them too (vr_hip_set_column_copy) */
+#define VR_COPY_COLV_Y   (1u << 11)  /* one gather and one transparency test per sixteen samples; TRILINEAR reads them too, and then shades from VR_COPY_COL_* (vr_hip_set_column_copy) */
 #define VR_COPY_COLV_Z   (1u << 12)
 #define VR_COPY_ALL      0x1fffu
 #define VR_COPY_KINDS    13

@@ -31,7 +31,8 @@ def main():
     ap.add_argument("--each", action="store_true", help="synchronise after every launch and list the kernel time of each")
     ap.add_argument("--sched", type=int, default=1, help="vr_hip_set_tile_scheduling: 0 workgroup order, 1 measured-cost order")
     ap.add_argument("--wide", type=int, default=0, help="vr_hip_set_wide_addressing value (2: 64-bit z tables, 1024-thread workgroups)")
-    ap.add_argument("--column-copy", type=int, default=0, choices=(0, 1), help="vr_hip_set_column_copy: 1 = TRILINEAR column views from the quad-element windows (colmarch_kernel)")
+    ap.add_argument("--column-copy", type=int, default=0, choices=(0, 1, 2), help="vr_hip_set_column_copy: 1 = TRILINEAR column views from the quad-element windows (colmarch_kernel), "
+                    "2 = voxel windows with byte-load shading (no quad-element copy beside them)")
     a = ap.parse_args()
     vr = importlib.import_module("volume-rendering_amd")
     r = vr.HipRenderer(0)

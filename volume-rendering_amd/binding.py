@@ -62,7 +62,7 @@ class VrTiming(C.Structure):
 
 class VrLaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("layout", "brick_plane", "lane_map", "phase_x", "phase_y", "clamp_fetch", "tiles_x", "tiles_y",
-                                          "ordered", "straddle_permille", "column_voxels")]
+                                          "ordered", "straddle_permille", "column_voxels", "column_shade_pairs")]
 
 
 def library_path():

@@ -66,6 +66,7 @@ struct RayKernelArgs {
 	uint32_t force_wide;               // testing aid: 1 = arithmetic 64-bit path, 2 = 64-bit table path, even for small volumes
 	uint32_t nbx, nby, nbz;            // bricks per axis (bricked layout)
 	uint64_t alt_copy;                 // kLayoutRunDual: address of the run copy along y (the kernel's `vol` argument is the copy along z)
+	                                   // kLayoutVoxCol: the quad-element windows of the march axis (kCopyColX ..) that voxcol_pairs_kernel shades from, or 0
 	uint32_t dual_analytic;            // kLayoutRunDual: 1 = every tile picks its run copy from dual_bits (no launch-order entry needed)
 	uint32_t dual_shift;               // ... one bit per group of (1 << dual_shift) consecutive tile NUMBERS (>= 6: 64 numbers = one 8x8-tile block of the numbering)
 	uint32_t dual_bits[32];            // ... bit set = the block's tiles read the copy with runs along y (vr_hip_api.cpp dual_choice_bits)
@@ -85,7 +86,8 @@ struct RayKernelArgs {
 		float dir[3];  float kd_scaled;
 		float light[3]; uint32_t nbu;  // lateral blocks along u (col_blocks(dim_u))
 		float lh[3];   uint32_t nw;    // windows per column (col_windows(dim_m))
-		uint32_t dim[3], pad;          // Model::dims (colmarch_nearest_kernel: map_float_int of the shading position)
+		uint32_t dim[3], nwq;          // Model::dims (colmarch_nearest_kernel: map_float_int of the shading position); windows per column of the
+		                               // quad-element copy at alt_copy (voxcol_pairs_kernel: nw is then the voxel windows')
 	} col_shade;
 #ifdef VR_BOUNDS_CHECK
 	// `make EXTRA=-DVR_BOUNDS_CHECK` (debug build, not the product): every gather address of the march is held against the array it must
@@ -180,7 +182,9 @@ struct TileSchedule { const uint32_t *order = nullptr; uint32_t *cost = nullptr;
 //   kLayoutVoxCol : the column-march views and the TRILINEAR arithmetic of kLayoutColumn, read from the NEAREST windows of 16 plain voxels
 //                   (kCopyColVox*, 1 byte per voxel): a wave gathers the rectangle of cell columns its lanes sample, one column per
 //                   lane, and hands every lane its 2x2 corner columns by cross-lane permutes (voxcol_tri_kernel).  Taken where the host
-//                   can bound that rectangle to 64 columns (vr_hip_api.cpp), kLayoutColumn otherwise.
+//                   can bound that rectangle to 64 columns (vr_hip_api.cpp), kLayoutColumn otherwise.  A LIT frame fetches its shading
+//                   samples (positions off the wave's rectangle) from the quad-element windows of the same axis, one 8-byte load instead
+//                   of eight byte loads (voxcol_pairs_kernel), when that copy can be had too.
 enum : uint32_t { kLayoutLinear = 0, kLayoutBricked = 1, kLayoutRun = 2, kLayoutRunY = 3, kLayoutVoxel = 4, kLayoutOct = 5, kLayoutRunDual = 6, kLayoutColumn = 7,
                   kLayoutVoxCol = 8 };
 __host__ __device__ constexpr bool is_run_layout(int layout) { return layout == (int) kLayoutRun || layout == (int) kLayoutRunY || layout == (int) kLayoutRunDual; }

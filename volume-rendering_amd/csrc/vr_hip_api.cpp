@@ -53,7 +53,8 @@ struct vr_ctx {
 	float copy_build_ms[kCopyKinds] = {};
 	bool copy_failed[kCopyKinds] = {};
 	int32_t column_force = 0;               // vr_hip_set_brick_plane: 0 = per view (views along a volume axis), 1 (plane 8) = every orthogonal full-march frame, -1 (plane 9) = never
-	uint32_t column_copy = 0;               // vr_hip_set_column_copy: 0 = TRILINEAR column frames read the voxel windows where a wave's columns fit, 1 = the quad-element windows
+	uint32_t column_copy = 0;               // vr_hip_set_column_copy: 0 = TRILINEAR column frames read the voxel windows where a wave's columns fit (lit frames shade from the
+	                                        // quad-element windows), 1 = the quad-element windows, 2 = as 0, shading by byte loads from the voxel windows (no second copy)
 	float upload_ms = 0;                    // host -> HBM copy (or generation) of the linear array in the last set_volume
 	int32_t brick_plane_force = -1;         // -1 = per view (plane perpendicular to the dominant view axis; run bricks for oblique views),
 	                                        // 0..2 = that chunk plane, 3 = the run bricks (testing)
@@ -490,7 +491,7 @@ hipError_t bounds_check_arm(vr_ctx *c, RayKernelArgs &a, const vr_params *p, con
 	a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
 	             copy_bytes(c, copy_kind_of(a, p->sampling));
 	if (column) a.bc_bytes += 2ull * kColPadBytes;
-	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, kCopyRunY) : 0;
+	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, a.layout == kLayoutVoxCol ? kCopyColX + a.col_axis : (uint32_t) kCopyRunY) : 0;      // (the pair fetch never reads the padding)
 	a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
 	// self-test of the net itself: VR_BC_SELFTEST=1 halves the size the checks hold the gathers against — a full-march frame must then fail
 	if (const char *e = getenv("VR_BC_SELFTEST")) if (atoi(e) == 1) a.bc_bytes /= 2;
@@ -648,7 +649,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// — the first frame of a new view already reads the right copies.  vr_hip_set_brick_plane(6) keeps the round-3 MEASURED choice
 	// (frames 0-3 of a parameter set on one copy each, the last two recording tile costs, choice kernel, per-block choice from frame 4 on)
 	// as the validator of that rule; 7 = alternating tiles (testing: the copies meet at tile boundaries all over the frame).
-	bool dual_analytic = false;
+	bool dual_analytic = false, shade_pairs = false;
 	int dual_stage = -1;                                 // measured / alternating choice only: -1 no; 0..3: the four frames before; 4: per-tile choice in use
 	const bool dual_test = c->brick_plane_force == (int) kPlanes + 4, dual_measured = c->brick_plane_force == (int) kPlanes + 3;
 	if (dual_candidate && is_run_layout(a.layout) && !p->esl && p->ray_threshold >= 1.0f && !a.clamp_fetch && c->bpv == 1 &&
@@ -686,7 +687,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		// for the +1 neighbours of a trilinear sample and + 1 for a column flip.  The quad-element windows (colmarch_kernel) otherwise.
 		const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
 		bool voxcol = false;
-		if (!nearest && c->column_copy == 0 && col_copy_bytes(c->dim, (uint32_t) m, true) < (1ull << 32)) {      // (the kernel's explicit fetches use 32-bit offsets)
+		if (!nearest && c->column_copy != 1u && col_copy_bytes(c->dim, (uint32_t) m, true) < (1ull << 32)) {      // (the kernel's explicit fetches use 32-bit offsets)
 			auto span = [&](int i) { return (int) std::floor(7.0f * (std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i]) + 4; };
 			voxcol = span(m == 0 ? 1 : 0) * span(m == 2 ? 1 : 2) <= 64;
 		}
@@ -703,6 +704,10 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			for (int i = 0; i < 3; i++) a.col_shade.dim[i] = c->dim[i];
 			a.col_shade.nbu = col_blocks(c->dim[m == 0 ? 1 : 0]);
 			a.col_shade.nw = col_windows(c->dim[m], nearest || voxcol ? kColVoxCells : kColCells);
+			a.col_shade.nwq = col_windows(c->dim[m]);
+			// a lit voxel-window frame shades from the quad-element windows of the same axis (voxcol_pairs_kernel: one 8-byte load per shaded
+			// sample instead of eight byte loads) — a second copy of 16/3 bytes per voxel, which vr_hip_set_column_copy(2) declines
+			shade_pairs = voxcol && p->light_kd > 0.01f && c->column_copy == 0;
 			dual_analytic = false; dual_stage = -1;
 		}
 	}
@@ -724,6 +729,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		}
 		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, true, a.layout);      // no quad copy either
 	}
+	// ... and the copy its shading samples read.  Refused or impossible (as above): the frame shades by byte loads from the voxel windows
+	if (shade_pairs && a.layout == kLayoutVoxCol && brick_copy != nullptr) a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyColX + a.col_axis);
 	// Shape of a wave's pixel tile (8x8, 16x4 or 4x16 inside the 32x16-pixel workgroup tile): a perspective view along a volume axis
 	// that reads run bricks gets its waves elongated along the screen direction the RUNS map to — the lanes of a wave then share the
 	// 36-byte runs (and their cache lines) instead of spreading over twice as many cell columns.  Measured on the benchmark's
@@ -881,10 +888,11 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		c->cost_map_tiles_x = plan.tiles_x; c->cost_map_tiles_y = plan.tiles_y;
 	}
 
-	// (the TRILINEAR column march over the voxel windows reports layout 7, the column march, and column_voxels = 1)
+	// (the TRILINEAR column march over the voxel windows reports layout 7, the column march, and column_voxels = 1; column_shade_pairs = 1
+	// when it shades from the quad-element windows)
 	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
 	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u,
-	                                 a.layout == kLayoutVoxCol ? 1u : 0u };
+	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u };
 
 	uint64_t frame_seq = 0;
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
@@ -1098,7 +1106,7 @@ int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t 
 	if (plan.reads_linear && c->vol == nullptr)
 		return fail(c, VR_ERR_NOT_READY, "this MIP frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                 "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again");
-	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u };
+	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u };
 	uint64_t frame_seq = 0;
 	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, a.p.esl ? c->mip_bounds : nullptr, dev_rgba, stream); });
 }
@@ -1307,7 +1315,8 @@ int vr_hip_set_brick_plane(vr_ctx *c, int32_t plane) {
 
 int vr_hip_set_column_copy(vr_ctx *c, uint32_t mode) {
 	if (c == nullptr) return VR_ERR_INVALID;
-	if (mode > 1u) return fail(c, VR_ERR_INVALID, "column copy must be 0 (voxel windows where a wave's columns fit, else quad-element windows) or 1 (quad-element windows)");
+	if (mode > 2u) return fail(c, VR_ERR_INVALID, "column copy must be 0 (voxel windows where a wave's columns fit, else quad-element windows; lit frames shade from the "
+	                                              "quad-element windows), 1 (quad-element windows) or 2 (as 0, shading from the voxel windows)");
 	c->column_copy = mode;
 	return VR_OK;
 }

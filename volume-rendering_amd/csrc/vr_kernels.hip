@@ -1307,6 +1307,21 @@ __device__ __forceinline__ uint64_t col_scalar_base(const uint8_t *copy, int64_t
 	const uint64_t b = (uint64_t) (uintptr_t) copy + (uint64_t) ref - (1ull << 30);
 	return ((uint64_t) rfl((uint32_t) (b >> 32)) << 32) | rfl((uint32_t) b);
 }
+// Explicit fetch from a QUAD-ELEMENT window copy (kCopyCol*, march axis M): the address of the element pair (march index i, i + 1) of a
+// texel-space position — 8 adjacent bytes of one window, 4-byte aligned — given the copy's base, the clamp maxima, its lateral blocks
+// along u and its windows per column.  Clamp addressing: any position is in bounds.  64-bit: the copy may exceed 4 GiB.
+template <int M>
+__device__ __forceinline__ const uint8_t *col_pair_address(const RayKernelArgs &a, const uint8_t *copy_p, float mx, float my, float mz, uint32_t blocks_u, uint32_t windows,
+                                                           float xb, float yb, float zb) {
+	constexpr int U = M == 0 ? 1 : 0, V = M == 2 ? 1 : 2;
+	const int ix = (int) __builtin_amdgcn_fmed3f(xb, 0.0f, mx), iy = (int) __builtin_amdgcn_fmed3f(yb, 0.0f, my), iz = (int) __builtin_amdgcn_fmed3f(zb, 0.0f, mz);
+	const uint32_t iu = (uint32_t) (U == 0 ? ix : iy), iv = (uint32_t) (V == 1 ? iy : iz), im = (uint32_t) (M == 0 ? ix : (M == 1 ? iy : iz));
+	const uint32_t wq = __umulhi(im, 0xAAAAAAABu) >> 1, sub = im - wq * 3u;
+	const uint32_t block = col_lateral_block(iu, iv, blocks_u) * windows + wq;
+	const uint32_t in_block = col_in_block(iu, iv) + sub * 4u;      // < 256: summed in 32 bits
+	const uint8_t *p = copy_p + ((uint64_t) block * kColBlockBytes + in_block);
+	return VR_BC_POINTER(a, const uint8_t *, p, 8u);
+}
 
 // The wave-uniform sample sequence, 64 samples at a time: lane j of `kvec` holds k of sample n + j, `wvec` the window its cell along m
 // lies in (cell_to_window: the kernel's own cell arithmetic and cells per window).  The reference forms k by repeated fp32 additions
@@ -1476,8 +1491,10 @@ struct ColFrontier {
 
 // One TRILINEAR sample at `k` whose element pair is (w0, w1): the general kernel's body from the transparency test on.  B = the
 // texel-space ray's offset (coordinate = fma(k, A, B), A from the argument segment); shade_corners(copy, ds, dh, sx, sy, sz, l0, l1)
-// fetches the element pair of the shading sample — the one thing that depends on the copy.
-template <int SAMPLING, int M, class ShadeCorners>
+// fetches the element pair of the shading sample — the one thing that depends on the copy.  PAIR_COPY: that fetch reads the quad-element
+// windows of the same axis beside the kernel's own copy; it is then handed their base (RayKernelArgs::alt_copy) and window count
+// (col_shade.nwq, in dh.nw) instead of the kernel's, out of the same grouped scalar loads.
+template <int SAMPLING, int M, bool PAIR_COPY = false, class ShadeCorners>
 __device__ __forceinline__ void col_tri_sample(const RayKernelArgs &a, uint32_t w0, uint32_t w1, float k, const f3 &B, ColRay &ray, uint64_t &live, f4 &acc,
                                                const f4 (&tf_l)[VR_TF_SIZE + 1], const f4 (&dtf_l)[VR_TF_SIZE + 1], const f4 (&org_l)[512], ShadeCorners shade_corners) {
 	constexpr bool kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;
@@ -1507,8 +1524,8 @@ __device__ __forceinline__ void col_tri_sample(const RayKernelArgs &a, uint32_t 
 				const f3 org = col_origin_again(org_l, ray.org_slot);                              // (its LDS read is in flight with the scalar load below)
 				RayKernelArgs::ColDenseShade dh;                                                   // (one scalar load again)
 				for (int i = 0; i < 3; i++) { dh.dir[i] = q->col_shade.dir[i]; dh.light[i] = q->col_shade.light[i]; dh.lh[i] = q->col_shade.lh[i]; }
-				dh.kd_scaled = q->col_shade.kd_scaled; dh.nbu = q->col_shade.nbu; dh.nw = q->col_shade.nw;
-				const uint8_t *const copy_p = ((ColConstKernelArguments) q)->copy;
+				dh.kd_scaled = q->col_shade.kd_scaled; dh.nbu = q->col_shade.nbu; dh.nw = PAIR_COPY ? q->col_shade.nwq : q->col_shade.nw;
+				const uint8_t *const copy_p = PAIR_COPY ? (const uint8_t *) (uintptr_t) q->alt_copy : ((ColConstKernelArguments) q)->copy;
 				hold_scalars(dh.dir[0], dh.dir[1], dh.dir[2], dh.kd_scaled, dh.light[0], dh.light[1], dh.light[2], dh.lh[0], dh.lh[1], dh.lh[2]);
 				hold_scalars(dh.nbu, dh.nw, (uint64_t) (uintptr_t) copy_p);
 				const f3 p3 = march_point<SAMPLING>(org, mk3(dh.dir[0], dh.dir[1], dh.dir[2]), k);
@@ -1579,16 +1596,6 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 	uint64_t live = ray.alive_mask;
 	float k = ray.kx;                               // the sample being processed (wave-uniform on the column path, per lane on the fallback)
 
-	// explicit fetch of the element pair (march index i, i + 1) of a texel-space position, clamp addressing: any position is in bounds
-	auto pair_address = [&](const uint8_t *copy_p, float mx, float my, float mz, uint32_t blocks_u, uint32_t windows, float xb, float yb, float zb) {
-		const int ix = (int) __builtin_amdgcn_fmed3f(xb, 0.0f, mx), iy = (int) __builtin_amdgcn_fmed3f(yb, 0.0f, my), iz = (int) __builtin_amdgcn_fmed3f(zb, 0.0f, mz);
-		const uint32_t iu = (uint32_t) (U == 0 ? ix : iy), iv = (uint32_t) (V == 1 ? iy : iz), im = (uint32_t) (M == 0 ? ix : (M == 1 ? iy : iz));
-		const uint32_t wq = __umulhi(im, 0xAAAAAAABu) >> 1, sub = im - wq * 3u;
-		const uint32_t block = col_lateral_block(iu, iv, blocks_u) * windows + wq;
-		const uint32_t in_block = col_in_block(iu, iv) + sub * 4u;      // < 256: summed in 32 bits
-		const uint8_t *p = copy_p + ((uint64_t) block * kColBlockBytes + in_block);
-		return VR_BC_POINTER(a, const uint8_t *, p, 8u);
-	};
 	auto coords = [&](ColConstArgs q, float kk, float &xb, float &yb, float &zb) {          // fma(k, A, B) with A = direction * N/2 (col_sample: the same fp32 products, formed by the host)
 		xb = VR_FMA(kk, q->col_sample.ax, B.x); yb = VR_FMA(kk, q->col_sample.ay, B.y); zb = VR_FMA(kk, q->col_sample.az, B.z);
 	};
@@ -1596,7 +1603,7 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 		ColConstArgs q = col_dense_args();
 		float xb, yb, zb;
 		coords(q, kk, xb, yb, zb);
-		const uint2 both = *(const uint2 *) pair_address(((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb);
+		const uint2 both = *(const uint2 *) col_pair_address<M>(a, ((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb);
 		w0 = both.x; w1 = both.y;
 	};
 	// the same as a MANAGED gather (the compiler does not see it: a load it knows to be in flight across the window loop's back edge makes
@@ -1605,12 +1612,12 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 		ColConstArgs q = col_dense_args();
 		float xb, yb, zb;
 		coords(q, kk, xb, yb, zb);
-		managed_load64(both, (uint64_t) (uintptr_t) pair_address(((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb));
+		managed_load64(both, (uint64_t) (uintptr_t) col_pair_address<M>(a, ((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb));
 	};
 	auto sample = [&](uint32_t w0, uint32_t w1) {                          // the shading sample's pair: one 8-byte load
 		col_tri_sample<SAMPLING, M>(a, w0, w1, k, B, ray, live, acc, tf_l, dtf_l, org_l,
 			[&](const uint8_t *copy_p, const RayKernelArgs::ColDenseSample &ds, const RayKernelArgs::ColDenseShade &dh, float sx, float sy, float sz, uint32_t &l0, uint32_t &l1) {
-				const uint2 both = *(const uint2 *) pair_address(copy_p, ds.max_x, ds.max_y, ds.max_z, dh.nbu, dh.nw, sx, sy, sz);
+				const uint2 both = *(const uint2 *) col_pair_address<M>(a, copy_p, ds.max_x, ds.max_y, ds.max_z, dh.nbu, dh.nw, sx, sy, sz);
 				l0 = both.x; l1 = both.y;
 			});
 	};
@@ -1904,6 +1911,10 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 // exact per sample: no event windows.  The transparency test is ONE per window and wave: the slices 16w .. 16w + 16 of every column of
 // the rectangle (the 16 cells of window w need the first slice of window w + 1 too).  Waves that cannot share the k sequence or the
 // rectangle march per lane with explicit byte loads from the same copy; the shading sample is an explicit fetch of its 2 x 2 x 2 corners.
+// PAIRS (voxcol_pairs_kernel): both explicit fetches — the shading sample's and the per-lane march's — read the element pair of the
+// position from the QUAD-ELEMENT windows of the same axis instead (col_pair_address: one 8-byte load, as colmarch_kernel; base in
+// RayKernelArgs::alt_copy, window count in col_shade.nwq).  The march itself streams the voxel windows as before.  The same values, so
+// the same image; the host launches it for lit frames when that copy can be had (vr_hip_api.cpp launch_frame).
 // prefetch depth in windows of 16 cells (the window after the one consumed has landed too: it holds the last cell's second slice)
 #ifndef VR_VOXCOL_DEPTH
 #define VR_VOXCOL_DEPTH 3
@@ -1914,13 +1925,11 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 constexpr int kVoxColDepth = VR_VOXCOL_DEPTH, kVoxColSlots = kVoxColDepth + 1;
 static_assert(kVoxColDepth >= 2 && 2 * kVoxColSlots + kVoxColDepth + 4 <= 64, "kColPadBytes");
 
-template <int SAMPLING, int M, bool FLIPS>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(VR_VOXCOL_WAVES, 8)))       // 64 VGPRs, 80 SGPRs, no spills: tests/test_voxcol_march.py
-void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, const float *__restrict__ tf_g, uint32_t *__restrict__ out) {
+template <int SAMPLING, int M, bool FLIPS, bool PAIRS>
+__device__ __forceinline__ void voxcol_march(const RayKernelArgs &a, const uint8_t *__restrict__ copy, const float *__restrict__ tf_g, uint32_t *__restrict__ out,
+                                             f4 (&tf_l)[VR_TF_SIZE + 1], f4 (&dtf_l)[VR_TF_SIZE + 1], f4 (&org_l)[512]) {
 	constexpr int U = M == 0 ? 1 : 0, V = M == 2 ? 1 : 2;
 	constexpr int kCells = (int) kColVoxCells;
-	__shared__ f4 tf_l[VR_TF_SIZE + 1], dtf_l[VR_TF_SIZE + 1];
-	__shared__ f4 org_l[512];
 	stage_tf_with_deltas(tf_l, dtf_l, tf_g);
 	__syncthreads();
 	ColRay ray;
@@ -1941,9 +1950,15 @@ void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, 
 	float k = ray.kx;
 
 	// the eight corner voxels of a texel-space position as the quad-element pair (march index i, i + 1), by explicit byte loads from the
-	// voxel windows; every index clamped (at the upper faces like the quad copy: the weight there is exactly 0): any position is in bounds
+	// voxel windows; every index clamped (at the upper faces like the quad copy: the weight there is exactly 0): any position is in bounds.
+	// PAIRS: the pair itself, one 8-byte load from the quad-element windows (copy_p / windows are then that copy's)
 	auto corners_at = [&](const uint8_t *copy_p, float mx, float my, float mz, uint32_t blocks_u, uint32_t windows, float xb, float yb, float zb,
 	                      uint32_t &w0, uint32_t &w1) {
+		if constexpr (PAIRS) {
+			const uint2 both = *(const uint2 *) col_pair_address<M>(a, copy_p, mx, my, mz, blocks_u, windows, xb, yb, zb);
+			w0 = both.x; w1 = both.y;
+			return;
+		}
 		const uint32_t ix = (uint32_t) (int) __builtin_amdgcn_fmed3f(xb, 0.0f, mx), iy = (uint32_t) (int) __builtin_amdgcn_fmed3f(yb, 0.0f, my),
 		               iz = (uint32_t) (int) __builtin_amdgcn_fmed3f(zb, 0.0f, mz);
 		const float fu = U == 0 ? mx : my, fv = V == 1 ? my : mz, fm = M == 0 ? mx : (M == 1 ? my : mz);
@@ -1960,10 +1975,11 @@ void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, 
 	auto fetch_at = [&](float kk, uint32_t &w0, uint32_t &w1) {         // the corners of the sample at kk, from each lane's true column
 		ColConstArgs q = col_dense_args();
 		const float xb = VR_FMA(kk, q->col_sample.ax, B.x), yb = VR_FMA(kk, q->col_sample.ay, B.y), zb = VR_FMA(kk, q->col_sample.az, B.z);
-		corners_at(((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb, w0, w1);
+		corners_at(PAIRS ? (const uint8_t *) (uintptr_t) q->alt_copy : ((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z,
+		           q->col_shade.nbu, PAIRS ? q->col_shade.nwq : q->col_shade.nw, xb, yb, zb, w0, w1);
 	};
-	auto sample = [&](uint32_t w0, uint32_t w1) {                          // the shading sample's pair: eight byte loads
-		col_tri_sample<SAMPLING, M>(a, w0, w1, k, B, ray, live, acc, tf_l, dtf_l, org_l,
+	auto sample = [&](uint32_t w0, uint32_t w1) {                          // the shading sample's pair: eight byte loads (PAIRS: one 8-byte load)
+		col_tri_sample<SAMPLING, M, PAIRS>(a, w0, w1, k, B, ray, live, acc, tf_l, dtf_l, org_l,
 			[&](const uint8_t *copy_p, const RayKernelArgs::ColDenseSample &ds, const RayKernelArgs::ColDenseShade &dh, float sx, float sy, float sz, uint32_t &l0, uint32_t &l1) {
 				corners_at(copy_p, ds.max_x, ds.max_y, ds.max_z, dh.nbu, dh.nw, sx, sy, sz, l0, l1);
 			});
@@ -2099,6 +2115,22 @@ void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, 
 		col_drain(slot, carry);
 	} else per_lane_march();
 	col_store(ray, acc);
+}
+
+template <int SAMPLING, int M, bool FLIPS>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(VR_VOXCOL_WAVES, 8)))       // 64 VGPRs, 80 SGPRs, no spills: tests/test_voxcol_march.py
+void voxcol_tri_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, const float *__restrict__ tf_g, uint32_t *__restrict__ out) {
+	__shared__ f4 tf_l[VR_TF_SIZE + 1], dtf_l[VR_TF_SIZE + 1];
+	__shared__ f4 org_l[512];
+	voxcol_march<SAMPLING, M, FLIPS, false>(a, copy, tf_g, out, tf_l, dtf_l, org_l);
+}
+// ... shading from the quad-element windows at a.alt_copy (PAIRS): tests/test_voxcol_pairs.py holds these twelve to the same limits
+template <int SAMPLING, int M, bool FLIPS>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(VR_VOXCOL_WAVES, 8)))
+void voxcol_pairs_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, const float *__restrict__ tf_g, uint32_t *__restrict__ out) {
+	__shared__ f4 tf_l[VR_TF_SIZE + 1], dtf_l[VR_TF_SIZE + 1];
+	__shared__ f4 org_l[512];
+	voxcol_march<SAMPLING, M, FLIPS, true>(a, copy, tf_g, out, tf_l, dtf_l, org_l);
 }
 
 // ---- maximum-intensity projection (vr_hip_render_mip) ---------------------------------------------------------
@@ -2435,13 +2467,14 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
 		const uint32_t m = a.col_axis;
 		const bool flips = a.p.view.direction[m == 0u ? 1 : 0] != 0.0f || a.p.view.direction[m == 2u ? 1 : 2] != 0.0f;
 		const bool voxels = a.layout == kLayoutVoxCol;                      // TRILINEAR over the voxel windows (kCopyColVoxX ..): voxcol_tri_kernel
+		const bool pairs = voxels && a.alt_copy != 0ull;                    // ... shading from the quad-element windows at alt_copy: voxcol_pairs_kernel
 		dispatch_axis_flag(m, flips, [&](auto axis, auto flag) {
 			constexpr int AX = decltype(axis)::value;
 			constexpr bool FL = decltype(flag)::value;
 			constexpr int T = VR_SAMPLE_TRILINEAR, Q8 = VR_SAMPLE_TRILINEAR_Q8;
 			if (a.p.sampling == VR_SAMPLE_NEAREST) go(colmarch_nearest_kernel<AX, FL>);      // voxel windows (kCopyColVoxX ..)
-			else if (a.p.sampling == VR_SAMPLE_TRILINEAR_Q8) { if (voxels) go(voxcol_tri_kernel<Q8, AX, FL>); else go(colmarch_kernel<Q8, AX, FL>); }
-			else if (voxels) go(voxcol_tri_kernel<T, AX, FL>); else go(colmarch_kernel<T, AX, FL>);
+			else if (a.p.sampling == VR_SAMPLE_TRILINEAR_Q8) { if (pairs) go(voxcol_pairs_kernel<Q8, AX, FL>); else if (voxels) go(voxcol_tri_kernel<Q8, AX, FL>); else go(colmarch_kernel<Q8, AX, FL>); }
+			else if (pairs) go(voxcol_pairs_kernel<T, AX, FL>); else if (voxels) go(voxcol_tri_kernel<T, AX, FL>); else go(colmarch_kernel<T, AX, FL>);
 		});
 		return hipGetLastError();
 	}

@@ -79,7 +79,8 @@ class HipRenderer:
         self._check(self._L.vr_hip_set_brick_plane(self._ctx, int(plane)), "set_brick_plane")
 
     def set_column_copy(self, mode=0):
-        """TRILINEAR column march: 0 voxel windows where a wave's columns fit (default), 1 quad-element windows; speed only."""
+        """TRILINEAR column march: 0 voxel windows where a wave's columns fit, lit frames shading from the quad-element windows (default),
+        1 quad-element windows, 2 voxel windows only (no second copy); speed and memory only."""
         self._check(self._L.vr_hip_set_column_copy(self._ctx, int(mode)), "set_column_copy")
 
     def set_tile_mapping(self, lane_map=-1, phase_x=0, phase_y=0):
@@ -91,7 +92,8 @@ class HipRenderer:
         self._check(self._L.vr_hip_set_tile_scheduling(self._ctx, int(mode)), "set_tile_scheduling")
 
     def last_launch(self):
-        """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille)."""
+        """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
+        column_voxels, column_shade_pairs)."""
         info = VrLaunchInfo()
         self._check(self._L.vr_hip_last_launch(self._ctx, C.byref(info)), "last_launch")
         return {n: int(getattr(info, n)) for n, _ in VrLaunchInfo._fields_}
