@@ -188,3 +188,81 @@ def compare_frames(a, b):
     """(#differing pixels, max abs channel delta)"""
     d = np.abs(a.astype(np.int16) - b.astype(np.int16))
     return int((d.max(axis=-1) != 0).sum()), int(d.max())
+
+
+# ---- the column marches' edge cases (tests/test_column_edges.py) --------------------------------------------------------------------
+
+class ColumnScene:
+    """A volume and everything a frame of it needs: voxels (z, y, x), premultiplied transfer function, ESL bits and block geometry, the
+    default ray step.  `name` and `tf_name` go into the failure messages."""
+
+    def __init__(self, name, vox, tf, esl, block_dims, block_size, ray_step, tf_name="default"):
+        self.name, self.tf_name, self.vox = name, tf_name, np.ascontiguousarray(vox)
+        self.tf, self.esl = np.ascontiguousarray(tf, np.float32), np.ascontiguousarray(esl, np.uint32)
+        self.block_dims, self.block_size, self.ray_step = int(block_dims), [float(b) for b in block_size], np.float32(ray_step)
+        self.dims = self.vox.shape[::-1]                                     # x, y, z
+        self.key = (name, tf_name, self.vox.shape, str(self.vox.dtype))
+
+    @classmethod
+    def from_golden(cls, golden, name):
+        st = golden.volume_state(name)
+        return cls(name, golden.voxels(name), st["tf"], st["esl"], st["esl_block_dims"], st["esl_block_size"], st["ray_step"])
+
+    @classmethod
+    def synthetic(cls, oracle, name, vox, base_tf, tf_name):
+        tf, esl, bd, bs, ray_step = oracle.scene_for(vox, base_tf)
+        return cls(name, vox, tf, esl, bd, bs, ray_step, tf_name)
+
+    def load(self, gpu):
+        gpu.set_transfer_fn(self.tf, self.esl)
+        gpu.set_volume(self.vox)
+
+
+def smooth_noisy_volume(shape_zyx, seed):
+    """u8 field of shape (z, y, x): a Gaussian bump off the centre (transparent corners, opaque core under the default transfer function)
+    plus noise of 0..23, so that reading a neighbouring voxel instead of the right one changes the sample."""
+    rng = np.random.default_rng(seed)
+    z, y, x = shape_zyx
+    zz, yy, xx = np.mgrid[0:z, 0:y, 0:x].astype(np.float64)
+    r2 = sum(((g - (n - 1) * c) / (0.45 * n + 0.5)) ** 2 for g, n, c in ((xx, x, 0.42), (yy, y, 0.55), (zz, z, 0.47)))
+    return np.clip(230.0 * np.exp(-r2) + rng.integers(0, 24, (z, y, x)), 0, 255).astype(np.uint8)
+
+
+def column_params(vr, scene, view, sampling, light_kd, ray_threshold, step_scale=1.0):
+    """Whole-frame parameters of `view` over `scene`: ESL off, the scene's ray step times `step_scale` (rounded as fp32)."""
+    p = vr.VrParams()
+    p.view = view
+    p.ray_step = float(np.float32(scene.ray_step) * np.float32(step_scale))
+    p.ray_threshold, p.light_kd, p.esl, p.sampling = float(ray_threshold), float(light_kd), 0, sampling
+    p.esl_block_dims = scene.block_dims
+    for j in range(3):
+        p.esl_block_size[j] = scene.block_size[j]
+    return vr.whole_frame(p)
+
+
+def axis_view(vr, dims_xyz, axis, sign, cells_per_pixel=0.5, distance=2.0, shift=0.3, margin=8, min_pixels=18):
+    """Orthogonal view along `axis` (0 = x) in direction `sign`, built by hand: exact zeros in the direction, the origin on the axis
+    `distance` before the centre (inside the cube below 1.0) and `shift` pixels off it, `cells_per_pixel` along both screen axes.  The frame
+    holds the whole cube plus `margin` empty pixels per screen axis (at least `min_pixels`)."""
+    iu, iv = (axis + 1) % 3, (axis + 2) % 3
+    v = vr.VrView()
+    pitch_u, pitch_v = np.float32(2.0 * cells_per_pixel) / np.float32(dims_xyz[iu]), np.float32(2.0 * cells_per_pixel) / np.float32(dims_xyz[iv])
+    v.width = max(int(np.ceil(dims_xyz[iu] / cells_per_pixel)) + margin, min_pixels)
+    v.height = max(int(np.ceil(dims_xyz[iv] / cells_per_pixel)) + margin, min_pixels)
+    v.perspective = 0
+    for j in range(3):
+        v.origin[j] = v.direction[j] = v.right_plane[j] = v.up_plane[j] = 0.0
+    v.direction[axis] = float(sign)
+    v.origin[axis] = -float(sign) * float(distance)
+    v.origin[iu], v.origin[iv] = float(np.float32(shift) * pitch_u), float(np.float32(shift) * pitch_v)
+    v.right_plane[iu], v.up_plane[iv] = float(pitch_u), float(pitch_v)
+    v.light_pos[0], v.light_pos[1], v.light_pos[2] = 0.5, -1.0, 3.0
+    return v
+
+
+def voxel_windows_fit(p, dims_xyz, march_axis):
+    """The host's condition for the voxel-window kernels (vr_hip_api.cpp): along each lateral axis a wave's 8x8 pixels span at most
+    floor(7 * cells per pixel) + 4 cell columns, and the rectangle of both must fit the wave's 64 lanes."""
+    span = [int(np.floor(np.float32(7.0) * (abs(np.float32(p.view.right_plane[i])) + abs(np.float32(p.view.up_plane[i]))) * (np.float32(0.5) * np.float32(dims_xyz[i])))) + 4
+            for i in range(3)]
+    return span[1 if march_axis == 0 else 0] * span[1 if march_axis == 2 else 2] <= 64
