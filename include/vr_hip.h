@@ -230,6 +230,55 @@ int vr_hip_render_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, v
 int vr_hip_render_mip(vr_ctx *ctx, const vr_params *params, uint8_t *host_rgba);
 int vr_hip_render_mip_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
 
+/* ---- shaded isosurface with depth: the third projection.  No reference counterpart. ----
+ * The first point along every ray where the interpolated field reaches `level`, shaded from the field's gradient, and the depth of that
+ * point.  Per pixel:
+ *  1. Ray.  View::get_ray + Raycaster::intersect exactly as in vr_hip_render.  A miss leaves the pixel (0,0,0,0) and the depth -1.
+ *  2. Sample sequence.  The samples are those of the march with leaping off: `while (kx <= ky) { sample at kx; kx += ray_step; }`, k
+ *     accumulated by repeated addition.  Nothing below changes this sequence; it is the MIP frame's sequence.
+ *  3. Field value and first hit.  v(k) is the TRILINEAR (or _Q8) interpolated RAW value at texel coordinates fma(k, A, B), with the A, B
+ *     and lerps of the TRILINEAR mode.  The first hit is the first sample i with v(k_i) >= level.  No such sample: pixel (0,0,0,0),
+ *     depth -1.
+ *  4. Refinement.  If i = 0 the hit is k* = k_0: the surface is already reached where the ray enters the cube, and nothing is refined.
+ *     Otherwise lo = k_(i-1), the accumulated k of the previous sample, whose value is < level by construction, and hi = k_i; `refine`
+ *     times: `mid = 0.5f * (lo + hi); if (v(mid) >= level) hi = mid; else lo = mid;`.  Then k* = hi.
+ *  5. Colour.  base = the linearly filtered transfer-function lookup of `level` with the arithmetic of a composited sample's lookup
+ *     (_Q8: rounded weight): the premultiplied entry as stored, so an isosurface at level l and a MIP pixel whose maximum is l have the
+ *     same base colour.
+ *  6. Shading.  If light_kd <= 0.01f then f = 1 and no gradient is fetched.  Otherwise, with (xb, yb, zb) = fma(k*, A, B), the gradient
+ *     is central differences one texel apart, clamp addressing as everywhere: gx = (v(xb + 1, yb, zb) - v(xb - 1, yb, zb)) * half.x,
+ *     likewise gy and gz; half = N/2 takes the texel gradient to model space, where the cube is [-1,1]^3 whatever the dims.
+ *     gg = fma(gz, gz, fma(gy, gy, gx * gx)).  If gg is not > 0 then s = 0.  Else, with pt = origin + direction * k* (fused),
+ *     dl = light_pos - pt, il = rsqrt_nr(fma(dl.z, dl.z, fma(dl.y, dl.y, dl.x * dl.x))) and dot = fma(gz, dl.z, fma(gy, dl.y, gx * dl.x)):
+ *     s = fminf(fabsf((dot * rsqrt_nr(gg)) * il), 1.0f), rsqrt_nr the Newton reciprocal square root of the TRILINEAR mode's light vector.
+ *     The shading is two-sided: a surface seen from inside the bright region is lit like one seen from outside.
+ *     f = fma(light_kd, s, 1.0f - light_kd).
+ *  7. Pixel.  write_color(base.x * f, base.y * f, base.z * f, base.w).  ray_threshold is ignored.
+ *  8. Depth.  Where a buffer is given, it holds out_width * out_rows floats laid out exactly like the RGBA buffer (x0, out_width,
+ *     out_rows, band_*): k* for a surface pixel and -1.0f for every other pixel, rows with gy >= height included.  k is the parameter of
+ *     the pixel's own ray: position = origin + direction * k with the origin and direction get_ray gives that pixel — the perspective
+ *     direction is NOT normalised, so k is not a distance there.  The RGBA bytes do not depend on whether depth is asked for.
+ *  9. params.esl selects EXACT acceleration.  0: every sample of the march is fetched.  Otherwise the kernel may skip the fetch of a
+ *     march sample whose bound is below `level`: the 3x3x3-dilated maximum of the sample's block in the grid of vr_hip_volume_minmax,
+ *     widened exactly as a MIP frame widens it for TRILINEAR / _Q8 and 2-byte voxels.  As for MIP, params.esl_block_* and the ESL bits
+ *     of vr_hip_set_transfer_fn are not used.  k += ray_step still runs for every sample; bisection and gradient fetches are never
+ *     skipped.  Images and depths with esl on and off are identical byte for byte.
+ * 10. Errors.  VR_SAMPLE_NEAREST -> VR_ERR_INVALID (a gradient-shaded first hit is defined on the interpolated field: the two TRILINEAR
+ *     modes are supported).  A NULL iso, a non-finite level, or refine > 16 -> VR_ERR_INVALID.  Everything else follows
+ *     vr_hip_render_mip: the NULL conventions, VR_ERR_NOT_READY without volume or transfer function, the guards on ray_step.
+ * 11. Shared behaviour with MIP frames.  The frame reads what a MIP frame of the same view and sampling reads — quad bricks with the
+ *     per-view chunk plane, oct bricks for 2-byte voxels where a MIP frame takes them, the linear array under VR_LAYOUT_LINEAR —, never
+ *     a run copy or a column window; the copy is built on first use.  vr_hip_set_wide_addressing, vr_hip_set_tile_mapping,
+ *     vr_hip_set_layout and vr_hip_set_brick_plane(5) apply; frames are counted by vr_hip_timing and described by vr_hip_last_launch.
+ *     vr_hip_render_iso is one launch plus one copy to the host per buffer.  It renders on a single device: the vr_hip_multi_* path
+ *     has no isosurface. */
+typedef struct vr_iso {
+	float    level;    /* in RAW voxel units: 0..255 for 1-byte voxels, 0..65535 for 2-byte voxels; must be finite */
+	uint32_t refine;   /* bisection steps after the first hit, 0..16 */
+} vr_iso;
+int vr_hip_render_iso(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, uint8_t *host_rgba, float *host_depth /* may be NULL */);
+int vr_hip_render_iso_device(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

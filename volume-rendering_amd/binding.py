@@ -47,6 +47,11 @@ class VrParams(C.Structure):
         return other
 
 
+class VrIso(C.Structure):
+    """vr_iso: the level in RAW voxel units (0..255 / 0..65535) and the bisection steps after the first hit (0..16)"""
+    _fields_ = [("level", C.c_float), ("refine", C.c_uint32)]
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -111,6 +116,8 @@ def lib():
         "vr_hip_render_device": (C.c_int, [vp, P(VrParams), vp, vp]),
         "vr_hip_render_mip": (C.c_int, [vp, P(VrParams), vp]),
         "vr_hip_render_mip_device": (C.c_int, [vp, P(VrParams), vp, vp]),
+        "vr_hip_render_iso": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp]),
+        "vr_hip_render_iso_device": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp, vp]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

@@ -88,7 +88,11 @@ class HipRenderer : public Renderer {
 		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
 		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
 		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
-		void set_mip(bool mip) { mip_ = mip; }
+		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = false; }
+		// on: render_volume() produces the shaded isosurface at `level` (raw voxel units) with `refine` bisection steps (vr_hip_render_iso;
+		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
+		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
+		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = false; }
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:
@@ -101,6 +105,8 @@ class HipRenderer : public Renderer {
 		vr_sampling sampling_;
 		bool device_buffer_;
 		bool mip_;
+		bool iso_;
+		vr_iso iso_params_;
 		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
 };
 

@@ -3,7 +3,8 @@
 // summary table (VolR.cpp:200-223) and, for eyeballing, a PPM writer for single frames.  There is no interactive mode.
 //
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
-//              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-o <frame.ppm>]
+//              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
+//              [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -39,6 +40,8 @@ void print_usage() {
 	       "  -s <width> <height> : viewport, 128..2048 like the reference\n  -d <device> : GPU index\n"
 	       "  -devices <a,b,...> : split every frame over these GPUs (interleaved bands gathered on the first one over xGMI)\n"
 	       "  -mip : maximum-intensity projection instead of the composite (single device)\n"
+	       "  -iso <level> [-refine <n>] : shaded isosurface at <level> (raw voxel units), n bisection steps (default 4, 0..16), from the\n"
+	       "         trilinear renderer (-r 1; renderer 0 keeps compositing in benchmark mode); single device, excludes -mip\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -238,7 +241,9 @@ int write_ppm(const char *path) {
 
 int main(int argc, char **argv) {
 	std::string file_name, out_ppm;
-	bool benchmark_mode = false, persp = false, have_pose = false, mip = false;
+	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false;
+	float iso_level = 0.0f;
+	int iso_refine = 4;
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
 	ViewBase::reset();
 	for (int i = 1; i < argc; i++) {
@@ -276,6 +281,8 @@ int main(int argc, char **argv) {
 		else if (strcmp(arg, "-bg") == 0 || strcmp(arg, "-b") == 0) benchmark_mode = true;
 		else if (strcmp(arg, "-persp") == 0) persp = true;
 		else if (strcmp(arg, "-mip") == 0) mip = true;
+		else if (strcmp(arg, "-iso") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); iso = true; } }
+		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
 		else if (strcmp(arg, "-pose") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) pose[k] = (float) atof(argv[++i]); have_pose = true; } }
 		else if (strcmp(arg, "-o") == 0) { if (need(1)) out_ppm = argv[++i]; }
 		else printf("Warning: unknown argument: %s\n", arg);
@@ -305,6 +312,15 @@ int main(int argc, char **argv) {
 		if (!device_list.empty()) { printf("Error: -mip renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
 		for (int i = 0; i < PROFILER_RENDERERS; i++) renderers[i]->set_mip(true);
 		printf("Maximum-intensity projection\n");
+	}
+
+	if (iso) {
+		if (!device_list.empty()) { printf("Error: -iso renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		if (mip) { printf("Error: -iso and -mip exclude each other\n"); return EXIT_FAILURE; }
+		if (iso_refine < 0 || iso_refine > 16) { printf("Error: -refine must be in 0..16\n"); return EXIT_FAILURE; }
+		if (!benchmark_mode && renderer_id != 1) { printf("Error: -iso needs the trilinear renderer (-r 1): an isosurface is defined on the interpolated field\n"); return EXIT_FAILURE; }
+		renderers[1]->set_iso(true, iso_level, (uint32_t) iso_refine);
+		printf("Isosurface at level %g, %d bisection steps\n", iso_level, iso_refine);
 	}
 
 	int rc = EXIT_SUCCESS;

@@ -333,6 +333,13 @@ hipError_t launch_mip_bounds(const uint8_t *minmax_dev /* launch_minmax */, uint
 hipError_t launch_mip(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                       const uint8_t *bounds, void *out_rgba, hipStream_t stream);
 
+// ---- shaded isosurface with depth (include/vr_hip.h vr_hip_render_iso) ----
+// One isosurface frame.  `a`, `linear`, `bricked` and `bounds` as for launch_mip, a.p.sampling TRILINEAR or TRILINEAR_Q8 (anything else, or a
+// layout a MIP frame of those samplings never takes, is hipErrorInvalidValue); a.p.esl != 0 = skip the fetch of samples whose widened
+// TRILINEAR bound (the second half of `bounds`) is below `level`.  out_depth (out_width * out_rows floats, laid out like out_rgba) may be NULL.
+hipError_t launch_iso(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                      const uint8_t *bounds, float level, uint32_t refine, void *out_rgba, void *out_depth, hipStream_t stream);
+
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);
 

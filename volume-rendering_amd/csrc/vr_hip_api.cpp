@@ -99,6 +99,8 @@ struct vr_ctx {
 	uint8_t *mip_bounds = nullptr; bool mip_bounds_ready = false;
 	struct MipMap { vr_params p; uint32_t dim[3], layout, brick_plane, lane_map, phase_x, phase_y, straddle_permille; };
 	MipMap mip_map[16]; uint32_t mip_mapped = 0, mip_map_next = 0;
+	// isosurface: the depth buffer of the host entry point (vr_hip_render_iso), one float per pixel of the window, allocated on first use
+	float *iso_depth = nullptr; size_t iso_depth_bytes = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -381,7 +383,7 @@ void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
 	else { a.esl_div_magic = (uint32_t) ((1ull << 32) / bd + 1); a.esl_div_shift = 0; }
 }
 
-// ---- what launch_frame and launch_mip_frame (further down) decide the same way ----------------------------------------------------
+// ---- what launch_frame and launch_full_march_frame (further down) decide the same way ----------------------------------------------------
 
 // the copy a frame of this layout reads (not asked for kLayoutLinear)
 uint32_t copy_kind_of(const RayKernelArgs &a, uint32_t sampling) {
@@ -1044,10 +1046,12 @@ int build_mip_bounds(vr_ctx *c) {
 	return VR_OK;
 }
 
-// One MIP frame (include/vr_hip.h vr_hip_render_mip): the copy it reads — voxel bricks for NEAREST, quad bricks of the plane across the
-// view (oct bricks for 2-byte voxels where a DVR frame takes them) for TRILINEAR, the linear array under VR_LAYOUT_LINEAR —, the tile
-// mapping of a DVR frame of the same view, one launch, one event pair.
-int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+// One frame of a projection that marches every ray in full — MIP (vr_hip_render_mip) or isosurface (vr_hip_render_iso), `what` in
+// messages: the copy it reads — voxel bricks for NEAREST, quad bricks of the plane across the view (oct bricks for 2-byte voxels where a
+// DVR frame takes them) for TRILINEAR, the linear array under VR_LAYOUT_LINEAR —, the block maxima when esl is on, the tile mapping of a
+// DVR frame of the same view, one launch, one event pair.  launch(a, brick_copy, bounds or NULL) starts the kernel.
+template <class Launch>
+int launch_full_march_frame(vr_ctx *c, const vr_params *p, hipStream_t stream, const char *what, Launch &&launch) {
 	RayKernelArgs a;
 	volume_args(c, p, a);
 	a.force_wide = c->force_wide;
@@ -1104,11 +1108,34 @@ int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t 
 	}
 	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
 	if (plan.reads_linear && c->vol == nullptr)
-		return fail(c, VR_ERR_NOT_READY, "this MIP frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
-		                                 "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again");
+		return fail(c, VR_ERR_NOT_READY, (std::string("this ") + what + " frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
+		                                  "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again").c_str());
 	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u };
 	uint64_t frame_seq = 0;
-	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, a.p.esl ? c->mip_bounds : nullptr, dev_rgba, stream); });
+	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch(a, brick_copy, a.p.esl ? c->mip_bounds : nullptr); });
+}
+
+int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	return launch_full_march_frame(c, p, stream, "MIP", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
+		return launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, bounds, dev_rgba, stream);
+	});
+}
+
+// One isosurface frame (include/vr_hip.h vr_hip_render_iso): what a MIP frame of the same view and sampling reads and maps, another kernel
+int launch_iso_frame(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	return launch_full_march_frame(c, p, stream, "isosurface", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
+		return launch_iso(a, c->vol, brick_copy, c->bpv, c->tf, bounds, iso->level, iso->refine, dev_rgba, dev_depth, stream);
+	});
+}
+
+// what the two isosurface entry points check beyond render_preamble
+int validate_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso) {
+	if (iso == nullptr) return fail(c, VR_ERR_INVALID, "iso is NULL");
+	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
+		return fail(c, VR_ERR_INVALID, "an isosurface is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (!std::isfinite(iso->level)) return fail(c, VR_ERR_INVALID, "iso level must be finite");
+	if (iso->refine > 16u) return fail(c, VR_ERR_INVALID, "iso refine must be in 0..16");
+	return VR_OK;
 }
 
 // what the four render entry points check first; host_frame: the frame goes through the window buffer to host memory
@@ -1199,6 +1226,7 @@ void vr_hip_destroy(vr_ctx *c) {
 	free_bricks(c);
 	if (c->minmax) (void) hipFree(c->minmax);
 	if (c->mip_bounds) (void) hipFree(c->mip_bounds);
+	if (c->iso_depth) (void) hipFree(c->iso_depth);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
 	if (c->stream) (void) hipStreamDestroy(c->stream);
@@ -1415,6 +1443,31 @@ int vr_hip_render_mip(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 	rc = launch_mip_frame(c, p, c->fb, c->stream);
 	if (rc) return rc;
 	return frame_to_host(c, host_rgba, (size_t) p->out_width * p->out_rows * 4, t0);
+}
+
+int vr_hip_render_iso_device(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_iso(c, p, iso)) return rc;
+	return launch_iso_frame(c, p, iso, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t *host_rgba, float *host_depth) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_iso(c, p, iso);
+	if (rc) return rc;
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	if (host_depth != nullptr && c->iso_depth_bytes != c->fb_bytes) {      // sized with the window (render_preamble: the frame fits)
+		VR_TRY(c, drain(c));
+		if (c->iso_depth) { (void) hipFree(c->iso_depth); c->iso_depth = nullptr; c->iso_depth_bytes = 0; }
+		VR_TRY(c, hipMalloc((void **) &c->iso_depth, c->fb_bytes));
+		c->iso_depth_bytes = c->fb_bytes;
+	}
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_iso_frame(c, p, iso, c->fb, host_depth ? c->iso_depth : nullptr, c->stream);
+	if (rc) return rc;
+	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->iso_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
 }
 
 #ifdef VR_MIP_STATS

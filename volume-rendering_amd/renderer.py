@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrError, VrLaunchInfo, VrParams, VrTiming, lib
+from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib
 
 
 class HipRenderer:
@@ -142,6 +142,24 @@ class HipRenderer:
         """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
         self._check(self._L.vr_hip_render_mip_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
                                                      C.c_void_p(stream) if stream else None), "render_mip_device")
+
+    # -- shaded isosurface with depth (vr_hip_render_iso: the first sample along every ray that reaches `level`, refined by bisection)
+    def render_iso(self, params, level, refine=4, depth=False):
+        """Host-buffer flavour: an (out_rows, out_width, 4) uint8 array, or with depth=True (rgba, depth): depth is float32
+        (out_rows, out_width), the ray parameter k of the surface point (position = origin + direction * k of the pixel's own ray; the
+        perspective direction is not normalised) and -1 where there is none.  `level` in raw voxel units; params.sampling must be one of
+        the TRILINEAR modes; params.esl != 0 = exact fetch skipping by block maxima."""
+        iso = VrIso(float(level), int(refine))
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
+        self._check(self._L.vr_hip_render_iso(self._ctx, C.byref(params), C.byref(iso), out.ctypes.data, dep.ctypes.data if depth else None), "render_iso")
+        return (out, dep) if depth else out
+
+    def render_iso_device(self, params, level, refine, dev_ptr, depth_ptr=None, stream=None):
+        """Device-buffer flavour: asynchronous launch into `dev_ptr` (RGBA8) and, if given, `depth_ptr` (float32) on `stream` (raw hipStream_t or None)."""
+        iso = VrIso(float(level), int(refine))
+        self._check(self._L.vr_hip_render_iso_device(self._ctx, C.byref(params), C.byref(iso), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
+                                                     C.c_void_p(stream) if stream else None), "render_iso_device")
 
     # -- timing (Profiler.cpp:46-67)
     def timing(self):
