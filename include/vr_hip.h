@@ -279,6 +279,41 @@ typedef struct vr_iso {
 int vr_hip_render_iso(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, uint8_t *host_rgba, float *host_depth /* may be NULL */);
 int vr_hip_render_iso_device(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
 
+/* ---- clip region for all three projections: a crop box and a cutting plane.  No reference counterpart. ----
+ * The clip is context state, like the layout knobs: it applies to every later composite (vr_hip_render*), MIP (vr_hip_render_mip*) and
+ * isosurface (vr_hip_render_iso*) frame of the context, and through the per-device contexts to vr_hip_multi_* frames
+ * (vr_hip_multi_set_clip).  NULL switches clipping off, which is the default; without a clip every frame is what it was.  vr_params and
+ * every other struct keep their size and layout.  Clipping only narrows each ray's segment [kx, ky] before the march.  Per pixel, right
+ * after View::get_ray and Raycaster::intersect have produced origin, dir, kx, ky and reported a hit:
+ *  1. Box.  d' = dir with exact zeros replaced by 0.00001f, as inside intersect.  k1 = (box_min - origin) / d' and
+ *     k2 = (box_max - origin) / d' per component, IEEE division; kxb = the max over the axes of min(k1, k2), kyb = the min over the axes of
+ *     max(k1, k2), min / max being the `a < b ? a : b` / `a > b ? a : b` of flmin / flmax in the association order of intersect.  Then
+ *     kx = flmax(kx, kxb) and ky = flmin(ky, kyb).  A box equal to [-1,1]^3 therefore changes no bit.
+ *  2. Plane, from the unreplaced dir.  dn = fma(n.z, dir.z, fma(n.y, dir.y, n.x * dir.x)) and, with o = origin,
+ *     on = fma(n.z, o.z, fma(n.y, o.y, fma(n.x, o.x, d))).  dn > 0: kx = flmax(kx, -on / dn).  dn < 0: ky = flmin(ky, -on / dn).
+ *     dn == 0: the ray is kept unchanged if on >= 0, else it is a miss.  (All four plane members 0: dn == 0 and on == 0, no plane.)
+ *  3. Hit test.  The ray is a hit iff (kx < ky) && (ky > 0).  A miss is treated exactly as an intersect miss: pixel (0,0,0,0), isosurface
+ *     depth -1.
+ *  4. March.  Everything after that is the frame's own definition applied to the clipped segment.  Composite: the leaping loop and the
+ *     accumulation `while (kx <= ky)` start at the clipped kx.  MIP / isosurface: the sample sequence is
+ *     `k = kx; while (k <= ky) { ...; k += ray_step; }` from the clipped kx.  Isosurface: a hit at sample 0 is k* = kx — a cut through the
+ *     region at or above the level shows the cut face, shaded from the field's gradient there; depth stays the parameter of the pixel's
+ *     own ray.  Exact acceleration is per sample and untouched: the ESL bits, the transparent-sample shortcut, the MIP / isosurface block
+ *     bounds, early termination.
+ *  5. Guards.  The two guards on ray_step (ky + step > ky, the cap on the number of steps) look at the UNCLIPPED segment, which contains
+ *     the clipped one; they cannot bind for parameters the entry points accept.
+ *  6. Errors.  VR_ERR_INVALID for a non-finite member and for box_min[i] >= box_max[i].  A box that misses the cube is valid: every
+ *     frame is empty.
+ *  7. What a clipped frame reads.  The linear array, quad, voxel or oct bricks — never a run copy or a column window, whatever
+ *     vr_hip_set_brick_plane forces (3, 4, 6, 7, 8 fall back to the quad copy of plane (x,y)): vr_launch_info::layout is never 2, 3, 6
+ *     or 7 for a clipped frame.  Setting a clip that differs from the current one forgets the cached tile mappings and recorded tile
+ *     orders (placement only; they are keyed by vr_params alone). */
+typedef struct vr_clip {
+	float box_min[3], box_max[3]; /* model space; the cube is [-1,1]^3 whatever the dims */
+	float plane[4];               /* kept half-space: n.x*x + n.y*y + n.z*z + d >= 0; all four 0 = no plane */
+} vr_clip;
+int vr_hip_set_clip(vr_ctx *ctx, const vr_clip *clip);       /* NULL = clipping off (the default) */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {
@@ -344,6 +379,7 @@ vr_ctx *vr_hip_multi_context(vr_multi *m, int rank);               /* the per-de
 const char *vr_hip_multi_transport(const vr_multi *m);             /* "rccl" | "peer-copy" | "single" */
 int  vr_hip_multi_set_window(vr_multi *m, uint32_t width, uint32_t height);
 int  vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf_premult_rgba, const uint32_t *esl_bits);
+int  vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip);      /* vr_hip_set_clip on every device's context */
 int  vr_hip_multi_set_volume(vr_multi *m, const void *host_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);
 int  vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bytes_per_voxel);
 int  vr_hip_multi_render(vr_multi *m, const vr_params *params, uint8_t *host_rgba);           /* whole frame -> host buffer */

@@ -61,6 +61,10 @@ int vr_host_quantize(const uint8_t *data16, uint32_t width, uint32_t height, uin
  * Uses the volume previously given to vr_host_raycaster_set_volume (voxels must still be valid) and `view`.
  * Returns what render_volume returns (0 / 1). */
 int vr_host_render_frame(int device, uint32_t sampling, const vr_view *view, uint8_t *host_rgba);
+/* The clip region vr_host_render_frame hands its renderer before the frame: volr::HipRenderer::set_clip(const vr_clip *), which forwards
+ * to vr_hip_set_clip, or with a device list to vr_hip_multi_set_clip (include/vr_hip.h has the contract).  NULL = none (the default).
+ * Process-global like the rest of this file; an invalid clip makes vr_host_render_frame return 1. */
+void vr_host_set_clip(const vr_clip *clip);
 
 #ifdef __cplusplus
 }

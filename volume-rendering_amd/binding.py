@@ -52,6 +52,22 @@ class VrIso(C.Structure):
     _fields_ = [("level", C.c_float), ("refine", C.c_uint32)]
 
 
+class VrClip(C.Structure):
+    """vr_clip: the crop box in model space (the cube is [-1,1]^3) and the kept half-space n.x*x + n.y*y + n.z*z + d >= 0 (all four 0 = no plane)"""
+    _fields_ = [("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("plane", C.c_float * 4)]
+
+
+def make_clip(box_min=None, box_max=None, plane=None):
+    """A VrClip; a missing box is [-1,1]^3, a missing plane is zeros (no plane)."""
+    clip = VrClip()
+    for i in range(3):
+        clip.box_min[i] = -1.0 if box_min is None else float(box_min[i])
+        clip.box_max[i] = 1.0 if box_max is None else float(box_max[i])
+    for i in range(4):
+        clip.plane[i] = 0.0 if plane is None else float(plane[i])
+    return clip
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -110,6 +126,7 @@ def lib():
         "vr_hip_set_brick_plane": (C.c_int, [vp, C.c_int32]),
         "vr_hip_set_column_copy": (C.c_int, [vp, u32]),
         "vr_hip_set_tile_scheduling": (C.c_int, [vp, u32]),
+        "vr_hip_set_clip": (C.c_int, [vp, P(VrClip)]),
         "vr_hip_last_launch": (C.c_int, [vp, P(VrLaunchInfo)]),
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
         "vr_hip_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -137,6 +154,7 @@ def lib():
         "vr_hip_multi_transport": (C.c_char_p, [vp]),
         "vr_hip_multi_set_window": (C.c_int, [vp, u32, u32]),
         "vr_hip_multi_set_transfer_fn": (C.c_int, [vp, vp, vp]),
+        "vr_hip_multi_set_clip": (C.c_int, [vp, P(VrClip)]),
         "vr_hip_multi_set_volume": (C.c_int, [vp, vp, u32, u32, u32, u32]),
         "vr_hip_multi_generate_volume": (C.c_int, [vp, u32, u32, u32, u32]),
         "vr_hip_multi_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -159,6 +177,7 @@ def lib():
         "vr_host_raycaster_reset_ray_step": (None, []),
         "vr_host_raycaster_get": (C.c_int, [P(VrParams), vp, vp, vp, vp]),
         "vr_host_render_frame": (C.c_int, [C.c_int, u32, P(VrView), vp]),
+        "vr_host_set_clip": (None, [P(VrClip)]),
         "vr_host_load_model": (C.c_int, [C.c_char_p, P(u32)]),
         "vr_host_set_raw_dims": (None, [u32, u32, u32, u32]),
         "vr_host_model_voxels": (vp, []),

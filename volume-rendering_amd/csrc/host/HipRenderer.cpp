@@ -92,6 +92,14 @@ int HipRenderer::set_volume(Model volume) {
 	return rc == 0 ? 0 : 1;
 }
 
+int HipRenderer::set_clip(const vr_clip *clip) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	const int rc = multi_ ? vr_hip_multi_set_clip(multi_, clip) : vr_hip_set_clip(ctx_, clip);
+	return rc == 0 ? 0 : 1;
+}
+
 int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 	if (!ok() || buffer == nullptr)
 		return 1;

@@ -93,6 +93,10 @@ class HipRenderer : public Renderer {
 		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
 		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = false; }
+		// The clip region of every later frame of this renderer — composite, set_mip and set_iso alike, and with a device list every device's
+		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
+		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.
+		int set_clip(const vr_clip *clip);
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:

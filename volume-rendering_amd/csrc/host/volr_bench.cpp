@@ -4,7 +4,7 @@
 //
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
-//              [-o <frame.ppm>]
+//              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -42,6 +42,8 @@ void print_usage() {
 	       "  -mip : maximum-intensity projection instead of the composite (single device)\n"
 	       "  -iso <level> [-refine <n>] : shaded isosurface at <level> (raw voxel units), n bisection steps (default 4, 0..16), from the\n"
 	       "         trilinear renderer (-r 1; renderer 0 keeps compositing in benchmark mode); single device, excludes -mip\n"
+	       "  -clip-box <x0> <y0> <z0> <x1> <y1> <z1> : crop every frame to this box (model space: the volume is [-1,1]^3)\n"
+	       "  -clip-plane <nx> <ny> <nz> <d> : keep the half-space nx*x + ny*y + nz*z + d >= 0; both work with the composite, -mip and -iso\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -244,6 +246,8 @@ int main(int argc, char **argv) {
 	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false;
 	float iso_level = 0.0f;
 	int iso_refine = 4;
+	bool clip_box = false, clip_plane = false;
+	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
 	ViewBase::reset();
 	for (int i = 1; i < argc; i++) {
@@ -283,6 +287,10 @@ int main(int argc, char **argv) {
 		else if (strcmp(arg, "-mip") == 0) mip = true;
 		else if (strcmp(arg, "-iso") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); iso = true; } }
 		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
+		else if (strcmp(arg, "-clip-box") == 0) {
+			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
+		}
+		else if (strcmp(arg, "-clip-plane") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) clip.plane[k] = (float) atof(argv[++i]); clip_plane = true; } }
 		else if (strcmp(arg, "-pose") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) pose[k] = (float) atof(argv[++i]); have_pose = true; } }
 		else if (strcmp(arg, "-o") == 0) { if (need(1)) out_ppm = argv[++i]; }
 		else printf("Warning: unknown argument: %s\n", arg);
@@ -321,6 +329,15 @@ int main(int argc, char **argv) {
 		if (!benchmark_mode && renderer_id != 1) { printf("Error: -iso needs the trilinear renderer (-r 1): an isosurface is defined on the interpolated field\n"); return EXIT_FAILURE; }
 		renderers[1]->set_iso(true, iso_level, (uint32_t) iso_refine);
 		printf("Isosurface at level %g, %d bisection steps\n", iso_level, iso_refine);
+	}
+
+	if (clip_box || clip_plane) {
+		for (int i = 0; i < PROFILER_RENDERERS; i++)
+			if (renderers[i]->set_clip(&clip) != 0) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }
+		printf("Clip region:");
+		if (clip_box) printf(" box (%g, %g, %g) - (%g, %g, %g)", clip.box_min[0], clip.box_min[1], clip.box_min[2], clip.box_max[0], clip.box_max[1], clip.box_max[2]);
+		if (clip_plane) printf(" plane %g x + %g y + %g z + %g >= 0", clip.plane[0], clip.plane[1], clip.plane[2], clip.plane[3]);
+		printf("\n");
 	}
 
 	int rc = EXIT_SUCCESS;

@@ -34,6 +34,9 @@ View view_from_c(const vr_view &v) {
 
 const float kBenchPoses[4][3] = { { 0, 0, 0 }, { -45, -45, 0 }, { 90, 0, 0 }, { 180, 90, 0 } };   // VolR.cpp:233-246
 
+bool host_clip_on = false;          // vr_host_set_clip: what vr_host_render_frame hands its renderer
+vr_clip host_clip;
+
 }  // namespace
 
 extern "C" {
@@ -120,11 +123,17 @@ int vr_host_quantize(const uint8_t *data16, uint32_t w, uint32_t h, uint32_t d, 
 	return VR_OK;
 }
 
+void vr_host_set_clip(const vr_clip *clip) {
+	host_clip_on = clip != nullptr;
+	if (clip != nullptr) host_clip = *clip;
+}
+
 int vr_host_render_frame(int device, uint32_t sampling, const vr_view *view, uint8_t *host_rgba) {
 	if (view == nullptr) return 1;
 	RaycasterBase::set_view(view_from_c(*view));                                  // VolR.cpp:107
 	HipRenderer renderer(RaycasterBase::raycaster, device, (vr_sampling) sampling);
 	if (!renderer.ok()) return 1;
+	if (host_clip_on && renderer.set_clip(&host_clip) != 0) return 1;
 	return renderer.render_volume((uchar4 *) host_rgba, RaycasterBase::raycaster);  // VolR.cpp:110
 }
 

@@ -89,6 +89,10 @@ struct RayKernelArgs {
 		uint32_t dim[3], nwq;          // Model::dims (colmarch_nearest_kernel: map_float_int of the shading position); windows per column of the
 		                               // quad-element copy at alt_copy (voxcol_pairs_kernel: nw is then the voxel windows')
 	} col_shade;
+	// vr_hip_set_clip (include/vr_hip.h vr_clip): the crop box and the kept half-space of a clipped frame.  Read by the
+	// *_clipped kernels only (vr_kernels.hip clip_segment) — the kernels of unclipped frames never look at these words; clip_on is for the host
+	uint32_t clip_on;
+	float    clip_min[3], clip_max[3], clip_plane[4];
 #ifdef VR_BOUNDS_CHECK
 	// `make EXTRA=-DVR_BOUNDS_CHECK` (debug build, not the product): every gather address of the march is held against the array it must
 	// lie in, every address-table index against its padded table, the tile-cost slot against its buffer; the first violation is recorded

@@ -101,6 +101,8 @@ struct vr_ctx {
 	MipMap mip_map[16]; uint32_t mip_mapped = 0, mip_map_next = 0;
 	// isosurface: the depth buffer of the host entry point (vr_hip_render_iso), one float per pixel of the window, allocated on first use
 	float *iso_depth = nullptr; size_t iso_depth_bytes = 0;
+	// clip region (vr_hip_set_clip): narrows the segment of every ray of every later frame; such frames run the *_clipped kernels
+	bool clip_on = false; vr_clip clip = {};
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -374,6 +376,11 @@ void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 	a.tf_zero_below = c->tf_zero_below;
 	a.nbx = (c->dim[0] + kBrickEdge - 1) / kBrickEdge; a.nby = (c->dim[1] + kBrickEdge - 1) / kBrickEdge;
 	a.nbz = (c->dim[2] + kBrickEdge - 1) / kBrickEdge;
+	if (c->clip_on) {
+		a.clip_on = 1u;
+		for (int i = 0; i < 3; i++) { a.clip_min[i] = c->clip.box_min[i]; a.clip_max[i] = c->clip.box_max[i]; }
+		for (int i = 0; i < 4; i++) a.clip_plane[i] = c->clip.plane[i];
+	}
 }
 
 // index / block edge of the ESL grid, prepared as shift or multiply-high (RaycasterBase.h:59-63)
@@ -576,7 +583,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		a.near_scaled = (pow2(c->dim[0]) && pow2(c->dim[1]) && pow2(c->dim[2]) && !(c->force_clamp_fetch & 2u)) ? 1u : 0u;
 	}
 	a.force_wide = c->force_wide;
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
 	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
@@ -608,6 +615,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			}
 		}
 		if (plane == kPlanes + 3 || plane == kPlanes + 4) { run_candidate = true; dual_candidate = true; }     // forced: 6 = measured per-tile choice, 7 = alternating tiles
+		// a clipped frame reads no run copy (there is no clipped kernel for them): the quad copy of the view's plane, (x,y) where a run copy is forced
+		if (clip) { run_candidate = run_if_unaligned = dual_candidate = false; if (plane >= kPlanes) plane = kPlaneXY; }
 		if (plane < kPlanes && copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
 		else if (plane == kPlanes && copy_possible(c, kCopyRunZ)) a.layout = kLayoutRun;               // forced: 3 = runs along z, 4 = runs along y
 		else if (plane == kPlanes + 1 && copy_possible(c, kCopyRunY)) a.layout = kLayoutRunY;
@@ -676,7 +685,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// Early ray termination alone is fine (the kernels clear a terminated lane's live bit like the general one; the k sequence stays shared);
 	// such frames give up the measured-cost tile order, which the column kernels do not take.
 	static const bool col_ert = [] { const char *e = getenv("VR_COL_ERT"); return e == nullptr || atoi(e) != 0; }();      // VR_COL_ERT=0: A/B
-	if (bricked && c->bpv == 1 && !c->force_wide && !p->view.perspective && !p->esl && (p->ray_threshold >= 1.0f || col_ert) &&
+	// Not a clipped frame: the column kernels march the whole cube on state the rays of a wave share, and a clipped segment is per ray.
+	if (bricked && !clip && c->bpv == 1 && !c->force_wide && !p->view.perspective && !p->esl && (p->ray_threshold >= 1.0f || col_ert) &&
 	    !a.clamp_fetch && c->column_force >= 0 && (c->brick_plane_force < 0 || c->column_force > 0)) {
 		const float *d = va.d;
 		const int m = va.major;
@@ -729,7 +739,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			forget_tile_mappings(c);                         // lane orders were chosen for the copy that could not be had
 			brick_copy = copy_for(c, kCopyQuadXY);
 		}
-		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, true, a.layout);      // no quad copy either
+		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, !clip, a.layout);      // no quad copy either
 	}
 	// ... and the copy its shading samples read.  Refused or impossible (as above): the frame shades by byte loads from the voxel windows
 	if (shade_pairs && a.layout == kLayoutVoxCol && brick_copy != nullptr) a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyColX + a.col_axis);
@@ -1353,6 +1363,25 @@ int vr_hip_set_tile_scheduling(vr_ctx *c, uint32_t mode) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (mode > 2u) return fail(c, VR_ERR_INVALID, "tile scheduling mode must be 0 (workgroup id), 1 (measured-cost order) or 2 (workgroup id + cost map)");
 	c->tile_scheduling = mode;
+	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_set_clip(vr_ctx *c, const vr_clip *clip) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (clip != nullptr) {
+		if (!finite3(clip->box_min) || !finite3(clip->box_max) || !finite3(clip->plane) || !std::isfinite(clip->plane[3]))
+			return fail(c, VR_ERR_INVALID, "clip members must be finite");
+		for (int i = 0; i < 3; i++)
+			if (clip->box_min[i] >= clip->box_max[i]) return fail(c, VR_ERR_INVALID, "clip box_min must be below box_max on every axis");
+	}
+	const bool on = clip != nullptr;
+	if (on == c->clip_on && (!on || memcmp(&c->clip, clip, sizeof *clip) == 0)) return VR_OK;
+	// The mapping and order caches are keyed by vr_params alone.  Both are placement only — an order recorded under another clip would still
+	// give the same image — but it describes other ray lengths and must not be mistaken for this clip's.  (Buffers of frames in flight stay.)
+	c->clip_on = on;
+	if (on) c->clip = *clip;
+	forget_tile_mappings(c);
 	forget_recorded_orders(c);
 	return VR_OK;
 }

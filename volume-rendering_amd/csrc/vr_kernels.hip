@@ -649,6 +649,38 @@ __device__ __forceinline__ PixelRay pixel_ray(const RayKernelArgs &a, uint32_t g
 	return r;
 }
 
+// -- the clip region of a clipped frame (include/vr_hip.h vr_hip_set_clip), applied to the segment pixel_ray found:
+//    the crop box narrows [kx, ky] by intersect's own slab arithmetic (exact zeros of the direction replaced, IEEE divisions, its order of
+//    flmin / flmax — the box [-1,1]^3 changes no bit), the plane by the parameter at which the ray crosses it, formed from the unreplaced
+//    direction.  Returns intersect's hit test on the narrowed segment; a miss is a miss of the cube.  The two guards of pixel_ray have
+//    looked at the unclipped segment, which contains this one.
+//    The ten constants are read HERE, behind the table staging, through a laundered pointer to the kernel-argument segment (the dual_bits
+//    pattern of vr_raymarch_body.inc; RayKernelArgs is the first argument of all three kernels: offset 0): read as members of the by-value argument
+//    they are loaded at the kernel's entry with the rest of it and stay live across the staging code, the SGPR peak — measured +10 SGPRs on
+//    every instantiation.
+__device__ __forceinline__ bool clip_segment(f3 origin, f3 dir, float &kx, float &ky) {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;      // constant address space: scalar loads
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	f3 d = dir;
+	if (d.x == 0) d.x = 0.00001f;
+	if (d.y == 0) d.y = 0.00001f;
+	if (d.z == 0) d.z = 0.00001f;
+	const f3 k1 = mk3((a->clip_min[0] - origin.x) / d.x, (a->clip_min[1] - origin.y) / d.y, (a->clip_min[2] - origin.z) / d.z);
+	const f3 k2 = mk3((a->clip_max[0] - origin.x) / d.x, (a->clip_max[1] - origin.y) / d.y, (a->clip_max[2] - origin.z) / d.z);
+	const float kxb = flmax(flmax(flmin(k1.x, k2.x), flmin(k1.y, k2.y)), flmin(k1.z, k2.z));
+	const float kyb = flmin(flmin(flmax(k1.x, k2.x), flmax(k1.y, k2.y)), flmax(k1.z, k2.z));
+	kx = flmax(kx, kxb);
+	ky = flmin(ky, kyb);
+	const float dn = VR_FMA(a->clip_plane[2], dir.z, VR_FMA(a->clip_plane[1], dir.y, a->clip_plane[0] * dir.x));
+	const float on = VR_FMA(a->clip_plane[2], origin.z, VR_FMA(a->clip_plane[1], origin.y, VR_FMA(a->clip_plane[0], origin.x, a->clip_plane[3])));
+	bool kept = true;
+	if (dn > 0) kx = flmax(kx, -on / dn);
+	else if (dn < 0) ky = flmin(ky, -on / dn);
+	else kept = on >= 0;                            // the ray runs inside the plane's direction (no plane: 0 >= 0)
+	return kept && (kx < ky) && (ky > 0);
+}
+
 // -- the address tables of the quad / voxel / oct bricks into LDS; no barrier.  Entry j of a table belongs to cell
 //    clamp(j - kLutPad, 0, dim - 1): the pad entries repeat the edge cells.
 __device__ __forceinline__ uint32_t lut_cell_of(uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); }
@@ -682,466 +714,29 @@ __device__ __forceinline__ void stage_brick_tables(const RayKernelArgs &a, uint3
 
 // ---- the ray-march kernel ------------------------------------------------------------------------------------------
 
+// raymarch_kernel and raymarch_clipped (a clipped frame, vr_hip_set_clip: the segment of every ray narrowed by clip_segment) are ONE body,
+// vr_raymarch_body.inc, compiled twice with CLIP = false / true.  Two kernels, not a flag in the kernel argument: the hot variants sit at the
+// 80-SGPR limit.  And the text itself inside each kernel, not a shared __device__ function template: as a function of its own the body is
+// optimised before it is inlined, the loop vectoriser then decides the table-staging loops of the 64-bit-table and run-brick variants the
+// other way, and those instantiations of the UNCLIPPED kernel take 17-28 more SGPRs (measured).
 template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
 __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
 void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
                      const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                      const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
-	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
-	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live
-	// there or during the march — the workgroup's start time and the address of its tile's cost word wait in LDS (one record per
-	// workgroup, written by thread 0 before the staging barrier) for the end of every wave.  (A per-wave record indexed by the wave's
-	// hardware slot, HW_ID, was tried and is WRONG: a wave that is context-switched out and back — several queues share the GPU —
-	// comes back in another slot, reads a record nobody wrote, and the atomic below goes to a wild address.)
-	__shared__ uint32_t group_sched[4];
-	const uint32_t order_entry = tile_order ? tile_order[blockIdx.x] : blockIdx.x;
-	// kLayoutRunDual: bit 31 of the entry selects the tile's copy (runs along y instead of z); it waits in LDS like the rest of the record
-	const uint32_t tile_of_group = LAYOUT == kLayoutRunDual ? (order_entry & ~kTileAltBit) : order_entry;
-	typedef LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)> L;
-	constexpr uint32_t kThreads = L::threads;
-	// kLayoutRunDual: which of the two run copies this tile reads.  From the launch-order entry (measured choice, testing aid), or —
-	// the product's rule, no history needed — from the bit the HOST set for the tile's group of 64 consecutive tile numbers, i.e. its
-	// 8x8-tile block (RayKernelArgs::dual_bits: the analytic entry-face rule of vr_hip_api.cpp dual_choice_bits).  Read through a laundered pointer to the kernel-argument segment
-	// (`a` is the first argument: offset 0) so that nothing of it stays in scalar registers across the staging code.
-	bool alt_tile = LAYOUT == kLayoutRunDual && (order_entry & kTileAltBit) != 0u;
-	if (LAYOUT == kLayoutRunDual && a.dual_analytic != 0u) {
-		typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;      // constant address space: scalar loads
-		ConstArgs q = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
-		asm volatile("" : "+s"(q));
-		const uint32_t bit = tile_of_group >> q->dual_shift;        // groups of consecutive tile NUMBERS: 64 = one 8x8-tile block of the numbering
-		const uint32_t word = q->dual_bits[(bit >> 5) & (kDualWords - 1u)];
-		alt_tile = __builtin_amdgcn_readfirstlane((int) ((word >> (bit & 31u)) & 1u)) != 0;       // uniform by construction (kernel arguments and the tile number only)
-	}
-	if (threadIdx.x == 0) {
-#ifdef VR_BOUNDS_CHECK
-		if (tile_of_group >= a.bc_ntiles) { bc_report(a, kBcCostSlot, tile_of_group, a.bc_ntiles); tile_cost = nullptr; }
-#endif
-		const uint64_t slot = tile_cost ? (uint64_t) (uintptr_t) (tile_cost + tile_of_group) : 0ull;
-		group_sched[0] = (uint32_t) (__builtin_readcyclecounter() >> 6); group_sched[1] = (uint32_t) slot; group_sched[2] = (uint32_t) (slot >> 32);
-		group_sched[3] = alt_tile ? 1u : 0u;
-	}
-	constexpr bool kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;        // 8-bit filter weights; everything else as TRILINEAR
-	constexpr bool kUseLut = L::max_dim != 0;
-	__shared__ LdsTables lds;
-	__shared__ __attribute__((aligned(16))) uint32_t lut[L::words];
-#ifdef VR_LDS_PAD          // tuning aid: occupy extra LDS to lower the number of resident workgroups per CU
-	__shared__ uint32_t lds_pad[VR_LDS_PAD / 4];
-	if (a.dim_x == 0xffffffffu) lds_pad[threadIdx.x] = 1;
-#endif
-
-	// -- stage TF (+ deltas), the ESL bit-volume and the brick address tables in LDS
-	{
-		const uint32_t t = threadIdx.x;
-		if (kUseLut && is_run_layout(LAYOUT)) {
-			// r = the run axis (z, or y for kLayoutRunY), o = the other column axis (y, or z); bricks: x fastest, then o, then r.
-			// kLayoutRunDual: a tile that reads the copy along y builds ITS tables exactly like kLayoutRunY and marches with the
-			// y and z components of its texel-space ray exchanged — the table regions then meet the coordinates they were built for.
-			const bool along_y = LAYOUT == kLayoutRunY || alt_tile;
-			const uint32_t nx = a.dim_x, nr = along_y ? a.dim_y : a.dim_z, no = along_y ? a.dim_z : a.dim_y;
-			const uint32_t nbo = along_y ? a.nbz : a.nby;
-			const uint64_t slab = (uint64_t) a.nbx * nbo * kRunBrickBytes;
-			const uint64_t copy_base = alt_tile ? a.alt_copy : (uint64_t) (uintptr_t) vol;
-#ifdef VR_BOUNDS_CHECK
-			if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = no + 2 * kLutPad; bc_table_entries[2] = nr + 2 * kLutPad; }
-#endif
-			for (uint32_t j = t; j < nr + 2 * kLutPad; j += kThreads) {
-				const uint32_t i = lut_cell_of(j, nr);
-				const uint64_t z0 = copy_base + (i >> 3) * slab + (i & 7u) * 4u;
-				lut[2 * j] = (uint32_t) z0; lut[2 * j + 1] = (uint32_t) (z0 >> 32);
-			}
-			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, nx); lut[L::x_at + j] = (i >> 3) * kRunBrickBytes + run_cell_spread(0, i & 7u); }
-			for (uint32_t j = t; j < no + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, no); lut[L::y_at + j] = (i >> 3) * a.nbx * kRunBrickBytes + run_cell_spread(1, i & 7u); }
-		} else if constexpr (kUseLut) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);      // (kUseLut: not the linear array, so L is LutCfg<ADDR>)
-		if (t <= VR_TF_SIZE) {
-			const f4 *tf4 = (const f4 *) tf_g;
-			uint32_t i0 = t < VR_TF_SIZE ? t : VR_TF_SIZE - 1;
-			uint32_t i1 = t + 1 < VR_TF_SIZE ? t + 1 : VR_TF_SIZE - 1;
-			f4 c0 = tf4[i0], c1 = tf4[i1];
-			lds.tf[t] = c0;
-			f4 d; d.x = c1.x - c0.x; d.y = c1.y - c0.y; d.z = c1.z - c0.z; d.w = c1.w - c0.w;
-			lds.dtf[t] = d;
-		}
-		for (uint32_t i = t; i < VR_ESL_VOLUME_SIZE; i += kThreads) lds.esl[i] = esl_g[i];
-		if (SAMPLING == VR_SAMPLE_NEAREST && BPV == 1 && t < 256u) lds.unit[t] = (float) t / 255.0f;   // the same IEEE division, once
-	}
-	__syncthreads();
-
-	uint32_t tile_x, tile_y;
-	tile_to_xy(a.tiles_x, a.tiles_y, tile_of_group, blockIdx.x, tile_x, tile_y);
-
-	uint32_t lx, ly;
-	lane_pixel<kThreads>(a, tile_x, tile_y, lx, ly);
-	if (lx >= a.p.out_width || ly >= a.p.out_rows)
-		return;                                     // no barrier below this point
-	const uint32_t lane = threadIdx.x & 63u;
-	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
-
-	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
-	f3 origin = ray.origin, dir = ray.dir;
-	float kx = ray.kx, ky = ray.ky;
-	const float step = a.p.ray_step;
-	bool alive = ray.alive;
-	const bool hit = alive;
-	f3 pt = march_point<SAMPLING>(origin, dir, kx);
-
-	// -- empty space leaping loop (CPURenderer.cpp:18-25)
-	// Cooperative look-ahead for zero-leap chains (round 4).  A ray that runs exactly along a block face (rows / columns of pixels of the
-	// axis-aligned views; a few rays of every view) finds its block empty but its distance to the exit plane 0 at EVERY sample: it leaps by
-	// floor(0 / step) * step = 0 and probes again one step on — up to ~1000 dependent probes by one or two lanes of a wave that is alone
-	// on its SIMD at the end of the frame (the default mode's tail).  While at most VR_ESL_COOP_LANES lanes still probe and one of them
-	// has just leapt by exactly 0, the whole wave evaluates that ray's next positions — the j-th active lane the position j rounds of
-	// "+= 0; += step" on, formed EXACTLY (inside a binade fl(k + step) = k + round_u(step): an arithmetic progression, see ColBatch;
-	// else by the sequential additions) — and the ray jumps to the first position whose probe is not again "empty block, zero leap",
-	// which the ordinary step below then evaluates.  Exact by construction.
-#ifndef VR_ESL_COOP_LANES
-#define VR_ESL_COOP_LANES 8
-#endif
-	if (a.p.esl) {
-		bool probing = alive;
-		uint64_t zero_leap = 0ull, pm;                                  // lanes whose last probe leapt by exactly 0
-		int coop_pause = 0;                                             // a look-ahead that skipped fewer than four positions cost more than it saved: pause (perspective views: their chains are short)
-		while ((pm = __builtin_amdgcn_ballot_w64(probing)) != 0ull) {
-			const uint64_t chain = pm & zero_leap;
-			if (coop_pause > 0) coop_pause--;
-			else if (VR_ESL_COOP_LANES > 0 && chain != 0ull && __builtin_popcountll(pm) <= VR_ESL_COOP_LANES) {
-				const int leader = __builtin_ctzll(chain);
-				const f3 lo = mk3(rlane(origin.x, leader), rlane(origin.y, leader), rlane(origin.z, leader)), ld = mk3(rlane(dir.x, leader), rlane(dir.y, leader), rlane(dir.z, leader));
-				const float k0 = rlane(kx, leader), kend = rlane(ky, leader);
-				// (pixels outside the buffer have left the kernel: position j of the chain lives in the j-th ACTIVE lane)
-				const uint64_t here = __builtin_amdgcn_ballot_w64(true);
-				const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t) (here >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) here, 0u));
-				float mine;
-				{
-					const float k1 = k0 + step, delta = k1 - k0, low = step - delta;
-					const uint32_t e = __float_as_uint(k0) >> 23;
-					const float half_ulp = __uint_as_float((e > 24u ? e - 24u : 1u) << 23), klast = VR_FMA(63.0f, delta, k0);
-					const bool fast = rfl((e > 24u && (__float_as_uint(klast) >> 23) == e && __builtin_fabsf(low) != half_ulp && delta > 0.0f) ? 1u : 0u) != 0u;
-					if (fast) mine = VR_FMA((float) rank, delta, k0);
-					else {
-						float run = k0;
-						mine = k0;
-						#pragma nounroll
-						for (uint32_t j = 1; j < 64u; j++) { run = run + step; mine = rank >= j ? run : mine; }
-					}
-				}
-				const f3 lp = march_point<SAMPLING>(lo, ld, mine);
-				const BlockIdx lb = block_index(a, lp);
-				bool goes_on = mine <= kend && block_empty(lds, lb);
-				if (goes_on) goes_on = leap_empty_space(a, lb, lp, ld) == 0.0f;
-				const uint64_t stops = here & ~__builtin_amdgcn_ballot_w64(goes_on);
-				const int first = stops != 0ull ? __builtin_ctzll(stops) : 63 - __builtin_clzll(here);      // the first position that does not go on (else the last: the step below re-evaluates it)
-				const float k_new = rlane(mine, first);
-				if ((int) lane == leader) { kx = k_new; pt = march_point<SAMPLING>(origin, dir, kx); }
-				if (__builtin_popcountll(here & ((1ull << first) - 1ull)) < 4) coop_pause = 24;
-			}
-			bool zl = false;
-			if (probing) {
-				const BlockIdx blk = block_index(a, pt);
-				if (kx <= ky && block_empty(lds, blk)) {
-					const float leap = leap_empty_space(a, blk, pt, dir);
-					zl = leap == 0.0f;
-					kx += leap;
-					kx += step;
-					pt = march_point<SAMPLING>(origin, dir, kx);
-				} else {
-					probing = false;
-				}
-			}
-			zero_leap = __builtin_amdgcn_ballot_w64(zl);
-		}
-	}
-	alive = alive && (kx <= ky);                    // CPURenderer.cpp:26-27: fully empty ray — pixel keeps the clear value
-	const bool visible = alive;
-
-	// -- colour accumulation loop (CPURenderer.cpp:29-39 / GPURenderer4.cu:75-86), front to back, premultiplied
-	f4 acc; acc.x = acc.y = acc.z = acc.w = 0.0f;
-	const f3 light = ld3(a.p.view.light_pos);
-	const float kd = a.p.light_kd;
-	const bool lit = kd > 0.01f;
-	const float threshold = a.p.ray_threshold;
-	if (SAMPLING == VR_SAMPLE_NEAREST) {
-		// Same loop shape as the TRILINEAR branch below (prefetch of sample i+1, finished lanes composited with weight 0,
-		// per-wave transparent-sample shortcut, two samples per exit vote); the arithmetic is the reference's, unfused:
-		// acc + cur * 0 == acc exactly, and map_float_int clamps every index, so speculative fetches stay in bounds.
-		// In-bounds speculative fetches without clamping to 0: every fetch position is taken at min(k, ky), on the ray's own
-		// segment inside the cube (for live lanes that IS the sample position); lanes without a segment march position 0.
-		// clamp_fetch (far-away views, see TRILINEAR) falls back to the reference's two-sided clamp.
-		const int tf_zero_idx = (int) a.tf_zero_below;                 // entries 0..tf_zero_idx are (0,0,0,0)
-		const int opaque_above = (tf_zero_idx + 1) * VR_TF_RATIO * (BPV == 1 ? 1 : 256) - 1;
-		uint64_t live = __builtin_amdgcn_ballot_w64(alive);            // liveness as one scalar wave mask (see TRILINEAR)
-		if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; pt = origin; }
-		constexpr bool kTables = is_brick_table_layout(LAYOUT) && ADDR != kAddrWide;  // padded address tables (kLutPad)
-		auto march = [&](auto clamp_tag, auto scaled_tag) {
-		constexpr bool kClamp = decltype(clamp_tag)::value;
-		// kFree: fetch positions are NOT pulled back to the ray's segment — a finished lane's k simply stops (its step becomes 0, a
-		// wave-uniform branch when a lane finishes), so a speculative position lies at most two steps past the exit point, inside
-		// the table padding.  Otherwise (no tables, or the clamping variant) every fetch position is taken at min(k, ky) / clamped.
-		constexpr bool kFree = !kClamp && kTables;
-		constexpr bool kScaled = kFree && decltype(scaled_tag)::value;               // sample_nearest_scaled
-		constexpr bool kLazy = kFree && VR_LAZY_EXIT;
-		const f3 so = kScaled ? mk3(origin.x * a.half_x, origin.y * a.half_y, origin.z * a.half_z) : origin;
-		const f3 sd = kScaled ? mk3(dir.x * a.half_x, dir.y * a.half_y, dir.z * a.half_z) : dir;
-		float step_v = kFree ? select_lanes(live, step) : step;
-		auto fetch_at = [&](float k) {
-			if (!kClamp && !kFree) k = __builtin_fminf(k, ky);
-			const f3 p = mk3(so.x + sd.x * k, so.y + sd.y * k, so.z + sd.z * k);      // CPURenderer.cpp:17,24,38: two roundings per axis
-			if (kClamp) return sample_nearest<BPV, ADDR, LAYOUT, true>(vol, a, lut, p);
-			if (kScaled) return sample_nearest_scaled<BPV, ADDR, LAYOUT, true>(vol, a, lut, p);
-			return sample_nearest_incube<BPV, ADDR, LAYOUT, true>(vol, a, lut, p);
-		};
-		constexpr bool kManaged = Managed<BPV, ADDR, LAYOUT>::value;
-		// kDepth samples ahead: slot j carries the fetched word and the k of its sample
-		uint32_t word[kSlots]; float ks[kSlots];
-		ks[0] = kx; word[kSlots - 1] = 0;
-		static_for<0, kDepth>([&](auto j) {
-			if constexpr (j.value > 0) ks[j.value] = ks[j.value - 1] + step_v;
-			word[j.value] = fetch_at(ks[j.value]);
-		});
-		auto step_sample = [&](auto jc) {
-			constexpr int c = decltype(jc)::value, n = (c + kDepth) % kSlots, nx = (c + 1) % kSlots;
-			ks[n] = ks[(n + kSlots - 1) % kSlots] + step_v;
-			word[n] = fetch_at(ks[n]);
-			__builtin_amdgcn_sched_barrier(0);
-			kx = ks[c];
-			const float kn = ks[nx];
-			(void) kn;
-			// Nothing that reads the fetched word may move above this point: the compiler otherwise hoists such work to the loop latch,
-			// behind an s_waitcnt vmcnt(0) that drains the prefetches in flight once per iteration.
-			if (kManaged) { pin(word[c]); managed_wait<kDepth>(); pin(word[c]); }
-			else pin(word[c]);
-			const uint32_t s = voxel_of<BPV, LAYOUT>(word[c]);
-			// transfer_fn[sample / TF_RATIO] (CPURenderer.cpp:31) is (0,0,0,0) for index <= tf_zero_idx, i.e. for
-			// s <= opaque_above = (tf_zero_idx + 1) * TF_RATIO * (1 or 256) - 1: tested on the voxel itself, the index is only formed
-			// by the few samples that get past the test
-			if ((__builtin_amdgcn_sicmp((int) s, opaque_above, kIcmpSGT) & live) != 0ull && VR_OPEN_LANES(acc.w, live) != 0ull) {
-				if (kLazy) {                                                                      // this sample's own segment test (see the loop)
-					const uint64_t inside = __builtin_amdgcn_fcmpf(kx, ky, kFcmpOLE);
-					if ((live & ~inside) != 0ull) { live &= inside; step_v = select_lanes(live, step); }       // a lane that is dropped here stops HERE:
-				}                                                                                 // the rotation test only looks at lanes still marked live
-				uint32_t idx = (BPV == 1 ? s : (s >> 8)) / VR_TF_RATIO;
-				asm volatile("" : "+v"(idx));                                                       // keep the index arithmetic inside the branch
-				f4 cur = lds.tf[idx];
-				const uint64_t shaded = lit ? (__builtin_amdgcn_fcmpf(cur.w, 0.05f, kFcmpOGT) & live) : 0ull;
-				if (shaded != 0ull) {                                                             // RaycasterBase.h:87-98 shade
-					const float raw = BPV == 1 ? 255.0f : 65535.0f;
-					pt = march_point<SAMPLING>(origin, dir, kx);                                  // the sample's own position
-					f3 d = mk3(light.x - pt.x, light.y - pt.y, light.z - pt.z);
-					float inv = 1.0f / __builtin_sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-					f3 l = mk3(d.x * inv, d.y * inv, d.z * inv);
-					f3 ps = mk3(pt.x + l.x * 0.01f, pt.y + l.y * 0.01f, pt.z + l.z * 0.01f);
-					const uint32_t s_l = voxel_of<BPV, LAYOUT>(sample_nearest<BPV, ADDR, LAYOUT>(vol, a, lut, ps));
-					const float sl = BPV == 1 ? lds.unit[s_l] : (float) s_l / raw;                  // RaycasterBase.h:93-96
-					const float sc = BPV == 1 ? lds.unit[s] : (float) s / raw;
-					const float diffuse = select_lanes(shaded, (sl - sc) * kd);                   // x + 0 == x: unshaded lanes unchanged
-					cur.x += diffuse; cur.y += diffuse; cur.z += diffuse;
-				}
-				const float t = select_lanes(live, 1 - acc.w);                                    // CPURenderer.cpp:34
-				acc.x = acc.x + cur.x * t; acc.y = acc.y + cur.y * t;
-				acc.z = acc.z + cur.z * t; acc.w = acc.w + cur.w * t;
-				live &= ~__builtin_amdgcn_fcmpf(acc.w, threshold, kFcmpOGT);                      // CPURenderer.cpp:35-36
-				if (kFree) step_v = select_lanes(live, step);                                     // terminated rays stop marching
-			}
-			if (!kLazy) {
-				const uint64_t still = __builtin_amdgcn_fcmpf(kn, ky, kFcmpOLE);
-				if (kFree && (live & ~still) != 0ull) step_v = select_lanes(live & still, step);      // a lane has just left its segment
-				live &= still;
-			}
-		};
-		// kLazy: `live` is brought up to date once per rotation of the slots (the k of the next sample against the end of the segment),
-		// and by every sample that composites, for itself.  In between a finished lane still counts as live: its fetches lie in the
-		// table padding (kOverrunSteps), a transparent sample does nothing with it, a compositing sample tests it first.
-		while (live != 0ull) {
-			static_for<0, kSlots>(step_sample);
-			if (kLazy) {
-				const uint64_t still = __builtin_amdgcn_fcmpf(ks[0], ky, kFcmpOLE);
-				if ((live & ~still) != 0ull) step_v = select_lanes(live & still, step);
-				live &= still;
-			}
-		}
-		if (kManaged) {                                              // nothing in flight into registers we release
-			static_for<0, kSlots>([&](auto j) { pin(word[j.value]); });
-			managed_wait<0>();
-			static_for<0, kSlots>([&](auto j) { pin(word[j.value]); });
-		}
-		};
-		if (a.clamp_fetch) march(std::true_type(), std::false_type());
-		else if (kTables && a.near_scaled) march(std::false_type(), std::true_type());
-		else march(std::false_type(), std::false_type());
-	} else {
-		// texel-space ray: coordinate = fma(k, A, B) (see oracle/vr_oracle.c axis_setup)
-		f3 A = mk3(dir.x * a.half_x, dir.y * a.half_y, dir.z * a.half_z);
-		f3 B = mk3(VR_FMA(origin.x, a.half_x, a.off_x), VR_FMA(origin.y, a.half_y, a.off_y), VR_FMA(origin.z, a.half_z, a.off_z));
-		// Lanes that are finished keep executing an in-bounds fetch with a zero weight instead of being masked off:
-		// acc = fma(cur, 0, acc) leaves them bit-for-bit unchanged, and the loop body needs no per-lane control flow
-		// except the shading block.  The wave leaves when no lane is alive.
-		// In bounds without clamping three coordinates per sample: every fetch position is taken at min(k, ky), i.e. on the
-		// ray's own segment inside the cube, where truncation alone gives the clamped cell (tri_issue); lanes that never
-		// had a segment march the constant position 0.  The host switches the coordinate clamp back on (clamp_fetch) for
-		// views so far from the volume that fp32 rounding of the coordinates could leave (-1, N).
-		if (!alive) { kx = 0.0f; ky = 0.0f; A = mk3(0.0f, 0.0f, 0.0f); B = A; }
-		// kLayoutRunDual, tile on the copy along y: the texel-space ray is kept with y and z EXCHANGED — that is what the tile's
-		// address tables index (staging above); the few samples that are filtered put the two coordinates back (same fma, same bits)
-		if (LAYOUT == kLayoutRunDual && group_sched[3] != 0u) { float t = A.y; A.y = A.z; A.z = t; t = B.y; B.y = B.z; B.z = t; }
-		constexpr bool kTables = LAYOUT != kLayoutLinear && ADDR != kAddrWide;        // padded address tables (kLutPad)
-		auto march = [&](auto clamp_tag) {                    // instantiated for both settings: no per-sample test of the flag
-			constexpr bool kClamp = decltype(clamp_tag)::value;
-			constexpr bool kFree = !kClamp && kTables;        // see the NEAREST loop: no min(k, ky), finished lanes stop instead
-			constexpr bool kLazy = kFree && VR_LAZY_EXIT;     // exit test once per rotation of the slots (see the NEAREST loop)
-			// Software pipeline: the loads of sample i+2 are issued before sample i is
-			// unpacked, filtered and composited, so memory round trips overlap the arithmetic inside every wave (on top of the
-			// 8 waves per SIMD).  The body is written once (`step_sample`) and instantiated once per fetch slot and iteration
-			// with the slots rotated: no register copies, one exit vote per three samples (a finished wave at worst composites
-			// two more weight-0 samples).
-			auto issue = [&](float k) {
-				if (!kClamp && !kFree) k = __builtin_fminf(k, ky);
-				return tri_issue<BPV, ADDR, LAYOUT, true>(vol, a, lut, VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z), kClamp);
-			};
-			constexpr bool kManaged = ManagedTri<BPV, ADDR, LAYOUT>::value;
-			// Lane liveness is kept as ONE 64-bit wave mask in scalar registers (`live`), updated with v_cmp results
-			// (__builtin_amdgcn_fcmpf returns the wave's compare mask) — no per-lane control flow, no mask <-> VGPR round trips:
-			// the body is straight-line code with two wave-uniform branches (transparent shortcut, shading block).
-			uint64_t live = __builtin_amdgcn_ballot_w64(alive);
-			float step_v = kFree ? select_lanes(live, step) : step;       // per-lane step: 0 once the lane is finished
-			// kDepth samples ahead (three for 2-byte voxels, whose slots hold four words: 64 VGPRs keep 8 waves per SIMD):
-			// slot j carries the fetched words and the k of its sample
-			constexpr int kDepth = is_run_layout(LAYOUT) ? kRunDepth : (BPV == 1 ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth)), kSlots = kDepth + 1;
-			TriFetch<BPV, LAYOUT> f[kSlots]; float ks[kSlots];
-			ks[0] = kx;
-			f[kSlots - 1].w0 = f[kSlots - 1].w1 = f[kSlots - 1].w2 = f[kSlots - 1].w3 = 0; f[kSlots - 1].q = 0; f[kSlots - 1].q2 = 0; f[kSlots - 1].o = (u32x4) (0u);
-			static_for<0, kDepth>([&](auto j) {
-				if constexpr (j.value > 0) ks[j.value] = ks[j.value - 1] + step_v;
-				f[j.value] = issue(ks[j.value]);
-			});
-			auto step_sample = [&](auto jc) {
-				constexpr int c = decltype(jc)::value, n = (c + kDepth) % kSlots, nx = (c + 1) % kSlots;
-				ks[n] = ks[(n + kSlots - 1) % kSlots] + step_v;
-				f[n] = issue(ks[n]);
-#ifndef VR_NO_SCHED_BARRIER
-				__builtin_amdgcn_sched_barrier(0);
-#endif
-				TriFetch<BPV, LAYOUT> &cur = f[c];
-				kx = ks[c];
-				const float kn = ks[nx];
-				(void) kn;
-			(void) kn;
-				// Exact shortcuts, decided per wave.  Entries 0..tf_zero_below of the premultiplied TF are all zero (the reference's
-				// default TF is zero below 10 % density), so a sample whose TF coordinate tb is <= tf_zero_below has colour
-				// (0,0,0,0), is never shaded (alpha 0 <= 0.05) and leaves acc bit-for-bit unchanged.
-				//  (1) before any arithmetic: if all 8 corner voxels of every live lane are below the power of two `skip_below`
-				//      (a bit test on the packed words), the interpolated value is too — a lerp never leaves [min, max] of its
-				//      operands, fp32 rounding included — and skip_below was chosen on the host so that tb <= tf_zero_below
-				//      follows: the wave skips unpacking, the 7 lerps and everything after them;
-				//  (2) after the interpolation: the same test on tb itself skips the LDS lookups, the shading test and the composite.
-				// pinned below the issue (see the NEAREST loop), on the slot's own registers: waits only for the slot's loads
-				if (kManaged && is_run_layout(LAYOUT)) {               // one 8-byte gather per slot: kDepth younger ones may be in flight
-					pin(cur.q); managed_wait<kDepth>(); pin(cur.q);
-					cur.w0 = (uint32_t) cur.q; cur.w1 = (uint32_t) (cur.q >> 32);
-				} else if (kManaged && LAYOUT == kLayoutOct) {         // one 16-byte gather per slot (2-byte voxels, oct bricks)
-					pin(cur.o); managed_wait<kDepth>(); pin(cur.o);
-					cur.w0 = cur.o.x; cur.w1 = cur.o.y; cur.w2 = cur.o.z; cur.w3 = cur.o.w;
-				} else if (kManaged && BPV == 2) {                     // two 8-byte gathers per slot (2-byte voxels)
-					pin(cur.q, cur.q2); managed_wait<2 * kDepth>(); pin(cur.q, cur.q2);
-					cur.w0 = (uint32_t) cur.q; cur.w1 = (uint32_t) (cur.q >> 32); cur.w2 = (uint32_t) cur.q2; cur.w3 = (uint32_t) (cur.q2 >> 32);
-				} else if (kManaged) {                                 // two 4-byte gathers per slot: 2 * kDepth younger ones
-					pin(cur.w0, cur.w1); managed_wait<2 * kDepth>(); pin(cur.w0, cur.w1);
-				} else if (LAYOUT != kLayoutLinear && BPV == 1) pin(cur.w0, cur.w1);
-				else pin(cur.w0, cur.w1, cur.w2, cur.w3);
-				const TriFetch<BPV, LAYOUT> &now = cur;
-				uint32_t corners;
-				if (LAYOUT != kLayoutLinear) corners = BPV == 1 ? (now.w0 | now.w1) : (now.w0 | now.w1 | now.w2 | now.w3);
-				else                          corners = now.w0 | now.w1 | now.w2 | now.w3;
-				// skip_cmp is 0; a TF without leading zero entries (nothing may be skipped) comes with skip_mask 0 and skip_cmp 1: 0 != 1 always
-				if ((__builtin_amdgcn_uicmp(corners & a.skip_mask, a.skip_cmp, kIcmpNE) & live) != 0ull && VR_OPEN_LANES(acc.w, live) != 0ull) {
-				if (kLazy) {
-					const uint64_t inside = __builtin_amdgcn_fcmpf(kx, ky, kFcmpOLE);
-					if ((live & ~inside) != 0ull) { live &= inside; step_v = select_lanes(live, step); }
-				}
-				const float xb = VR_FMA(kx, A.x, B.x);                                                            // where the words were fetched
-				float yb = VR_FMA(kx, A.y, B.y), zb = VR_FMA(kx, A.z, B.z);
-				// kLayoutRunDual: read again from LDS here, so that the flag occupies no register across the march — through an index the
-				// compiler cannot see through, or it hoists the read out of the loop (a volatile access would become a FLAT load with a
-				// vmcnt(0) wait behind it: the whole prefetch pipeline drained per filtered sample)
-				bool along_y = false;
-				if (LAYOUT == kLayoutRunDual) {
-					uint32_t opaque_zero;
-					asm volatile("v_mov_b32 %0, 0" : "=v"(opaque_zero));
-					along_y = group_sched[3u + opaque_zero] != 0u;
-				}
-				if (LAYOUT == kLayoutRunDual && along_y) { const float t = yb; yb = zb; zb = t; }                 // the true coordinates again
-				const float raw = tri_resolve<BPV, LAYOUT, kQ8>(now, a, xb, yb, zb, along_y);                 // GPURenderer4.cu:76
-				// GPURenderer4.cu:77 filtered TF: texel coordinate tb, entries floor(tb) and floor(tb)+1
-				const float tb = __builtin_amdgcn_fmed3f(VR_FMA(raw, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
-				if ((__builtin_amdgcn_fcmpf(tb, a.tf_zero_below, kFcmpOGE) & live) != 0ull) {
-					f4 c;
-					{
-						const uint32_t i = (uint32_t) (int) tb;
-						const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
-						const f4 c0 = lds.tf[i], dc = lds.dtf[i];
-						c.x = VR_FMA(w, dc.x, c0.x); c.y = VR_FMA(w, dc.y, c0.y);
-						c.z = VR_FMA(w, dc.z, c0.z); c.w = VR_FMA(w, dc.w, c0.w);
-					}
-					const uint64_t shaded = lit ? (__builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live) : 0ull;   // GPURenderer4.cu:78
-					if (shaded != 0ull) {                                                              // GPURenderer4.cu:41-51 shade_texture
-						const f3 p3 = march_point<SAMPLING>(origin, dir, kx);
-						const f3 d = mk3(light.x - p3.x, light.y - p3.y, light.z - p3.z);
-						const float inv = rsqrt_nr(VR_FMA(d.z, d.z, VR_FMA(d.y, d.y, d.x * d.x)));
-						const float lx = VR_FMA(d.x * inv, a.lh_x, xb), ly = VR_FMA(d.y * inv, a.lh_y, yb), lz = VR_FMA(d.z * inv, a.lh_z, zb);
-						TriFetch<BPV, LAYOUT> lf;
-						if (LAYOUT == kLayoutRunDual) {                     // clamp with the true bounds, then hand the tile's table order over
-							const float cy = __builtin_amdgcn_fmed3f(ly, 0.0f, a.max_y), cz = __builtin_amdgcn_fmed3f(lz, 0.0f, a.max_z);
-							lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, __builtin_amdgcn_fmed3f(lx, 0.0f, a.max_x), along_y ? cz : cy, along_y ? cy : cz, false);
-						} else lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, lx, ly, lz, true);
-						const float raw_l = tri_resolve<BPV, LAYOUT, kQ8>(lf, a, lx, ly, lz, along_y);
-						const float diffuse = select_lanes(shaded, (raw_l - raw) * a.kd_scaled);       // 0 for lanes that are not shaded
-						c.x += diffuse; c.y += diffuse; c.z += diffuse;
-					}
-					const float t = select_lanes(live, 1 - acc.w);                                     // finished lanes: weight 0
-					acc.x = VR_FMA(c.x, t, acc.x); acc.y = VR_FMA(c.y, t, acc.y);
-					acc.z = VR_FMA(c.z, t, acc.z); acc.w = VR_FMA(c.w, t, acc.w);
-					live &= ~__builtin_amdgcn_fcmpf(acc.w, threshold, kFcmpOGT);                        // ERT (CPURenderer.cpp:35-36)
-					if (kFree) step_v = select_lanes(live, step);                                       // terminated rays stop marching
-				}
-				}
-				if (!kLazy) {
-					const uint64_t still = __builtin_amdgcn_fcmpf(kn, ky, kFcmpOLE);                    // the loop condition
-					if (kFree && (live & ~still) != 0ull) step_v = select_lanes(live & still, step);    // a lane has just left its segment
-					live &= still;
-				}
-			};
-			while (live != 0ull) {
-				static_for<0, kSlots>(step_sample);
-				if (kLazy) {
-					const uint64_t still = __builtin_amdgcn_fcmpf(ks[0], ky, kFcmpOLE);
-					if ((live & ~still) != 0ull) step_v = select_lanes(live & still, step);
-					live &= still;
-				}
-			}
-			if (kManaged) {                                            // nothing in flight into registers we release
-				auto pin_slot = [&](auto j) { if (is_run_layout(LAYOUT)) pin(f[j.value].q); else if (LAYOUT == kLayoutOct) pin(f[j.value].o); else if (BPV == 2) pin(f[j.value].q, f[j.value].q2); else pin(f[j.value].w0, f[j.value].w1); };
-				static_for<0, kSlots>(pin_slot);
-				managed_wait<0>();
-				static_for<0, kSlots>(pin_slot);
-			}
-		};
-		if (a.clamp_fetch) march(std::true_type()); else march(std::false_type());
-	}
-
-	// -- RaycasterBase.h:44-50 write_color (+ the fused clear: misses and fully-empty rays store 0)
-	uint32_t rgba = 0;
-	if (hit && visible) {
-		rgba = map_float_int(acc.x, 256) | (map_float_int(acc.y, 256) << 8) |
-		       (map_float_int(acc.z, 256) << 16) | (map_float_int(acc.w, 256) << 24);
-	}
-	*out_px = rgba;
-	// cost of the tile = the end of its last wave after the start of the workgroup, in 64-cycle units (at least 1); every wave
-	// reports, through the first of its lanes that is still here
-	const uint32_t lane_id = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-	if (lane_id == (uint32_t) __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) {
-		const uint32_t *w = group_sched;
-		const uint64_t slot = ((uint64_t) w[2] << 32) | w[1];
-		if (slot != 0ull) atomicMax((uint32_t *) (uintptr_t) slot, ((uint32_t) (__builtin_readcyclecounter() >> 6) - w[0]) | 1u);
-	}
+	constexpr bool CLIP = false;
+#include "vr_raymarch_body.inc"
+}
+// ... of a clipped frame (vr_hip_set_clip): the linear array, the quad, voxel and oct bricks — never a run copy (launch_frame).  Its own
+// name, so that the register tests of raymarch_kernel's instantiations count what they counted; tests/test_clip_model.py holds these
+template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
+__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
+void raymarch_clipped(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
+                      const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
+                      const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
+	static_assert(!is_run_layout(LAYOUT), "a clipped frame never reads a run copy");
+	constexpr bool CLIP = true;
+#include "vr_raymarch_body.inc"
 }
 
 // ---- the column march (kLayoutColumn, round 4) -----------------------------------------------------------------------------------
@@ -2165,174 +1760,21 @@ void voxcol_pairs_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy
 constexpr int kMipBatch = VR_MIP_BATCH;
 extern __shared__ __attribute__((aligned(16))) uint8_t mip_bound_lds[];      // kMipBoundEntries bytes of dynamic LDS, only for frames that skip
 
+// mip_kernel and mip_clipped (a clipped frame: the segment narrowed by clip_segment) are one body, vr_mip_body.inc, compiled with CLIP = false / true
 template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
 __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
 void mip_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
                 uint32_t *__restrict__ out) {
-	typedef LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)> L;
-	constexpr uint32_t kThreads = L::threads;
-	constexpr bool kNearest = SAMPLING == VR_SAMPLE_NEAREST, kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;
-	__shared__ __attribute__((aligned(16))) uint32_t lut[L::words];
-	const bool skipping = a.p.esl != 0u;                            // wave-uniform: a kernel argument
-	uint32_t volume_max = 0u;
-	if constexpr (L::max_dim != 0) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);
-	if (skipping) {
-		// (32-bit copies: static LDS in front of the dynamic region may leave its base at any multiple of 4)
-		const uint32_t *src = (const uint32_t *) (bounds_g + (kNearest ? 0u : kMipBoundEntries));
-		uint32_t *dst = (uint32_t *) mip_bound_lds;
-		for (uint32_t i = threadIdx.x; i < kMipBoundEntries / 4u; i += kThreads) dst[i] = src[i];
-		volume_max = *(const uint32_t *) (bounds_g + 2u * kMipBoundEntries);
-	}
-	__syncthreads();
-
-	// -- tile = workgroup id: every ray of a MIP frame without skipping is a full march
-	uint32_t tile_x, tile_y, lx, ly;
-	tile_to_xy(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
-	lane_pixel<kThreads>(a, tile_x, tile_y, lx, ly);
-	if (lx >= a.p.out_width || ly >= a.p.out_rows)
-		return;                                     // no barrier below this point
-	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
-
-	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
-	f3 origin = ray.origin, dir = ray.dir;
-	float kx = ray.kx, ky = ray.ky;
-	const float step = a.p.ray_step;
-	const bool alive = ray.alive;
-	const bool hit = alive;
-	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a segment: position 0, never live
-
-	// -- the march: kMipBatch samples issued, then consumed.  With skipping, `need` is decided against the m of the batch's start: a
-	//    smaller m only keeps a fetch that a later one would have made unnecessary.
-	float k = kx;
-	bool live = alive;
-#ifdef VR_MIP_STATS
-	uint32_t stat_samples = 0u, stat_fetches = 0u;
-#define VR_MIP_COUNT(is_live, is_needed) do { stat_samples += (is_live) ? 1u : 0u; stat_fetches += (is_needed) ? 1u : 0u; } while (0)
-#define VR_MIP_COUNT_REST() do { if (live && k <= ky) stat_samples += (uint32_t) ((ky - k) / step) + 1u; } while (0)      /* what a stopped ray leaves out (approximate) */
-#else
-#define VR_MIP_COUNT(is_live, is_needed) do { } while (0)
-#define VR_MIP_COUNT_REST() do { } while (0)
-#endif
-	f4 colour; colour.x = colour.y = colour.z = colour.w = 0.0f;
-	const f4 *tf4 = (const f4 *) tf_g;
-	auto bound_index = [&](f3 pos) { const BlockIdx b = block_index(a, pos); return (b.z * VR_ESL_VOLUME_DIMS + b.y) * VR_ESL_VOLUME_DIMS + b.x; };
-	// Two instantiations of each loop, like the clamp tags of raymarch_kernel.  Without skipping the batch is straight-line code: every
-	// lane fetches — a finished lane where its k stopped, the same cell again — and only the maximum looks at liveness.  With skipping a
-	// fetch sits behind the wave's vote and the lane's own need; what it loaded is consumed behind the same vote after the whole batch
-	// was issued, so the compiler cannot pull the consumer (and the wait in front of it) up to the load.
-	if constexpr (kNearest) {
-		auto widen = [](uint32_t high) { return BPV == 1 ? high : ((high << 8) | 0xffu); };
-		const uint32_t stop_at = widen(volume_max);
-		uint32_t m = 0u;
-		auto march = [&](auto skip_tag) {
-			constexpr bool kSkip = decltype(skip_tag)::value;
-			while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
-				uint32_t word[kMipBatch];
-				uint64_t fetched[kMipBatch];
-				bool counts[kMipBatch];
-				#pragma unroll
-				for (int u = 0; u < kMipBatch; u++) {
-					const f3 pos = march_point<SAMPLING>(origin, dir, k);
-					counts[u] = live;
-					if constexpr (kSkip) {
-						const bool need = live && widen(mip_bound_lds[bound_index(pos)]) > m;
-						fetched[u] = __builtin_amdgcn_ballot_w64(need);
-						word[u] = 0u;
-						VR_MIP_COUNT(live, need);
-						if (fetched[u] != 0ull) {
-							if (need) word[u] = sample_nearest<BPV, ADDR, LAYOUT>(vol, a, lut, pos);
-						}
-						k += step;
-					} else {
-						fetched[u] = ~0ull;
-						word[u] = sample_nearest<BPV, ADDR, LAYOUT>(vol, a, lut, pos);
-						k += live ? step : 0.0f;
-					}
-					live = live && k <= ky;
-				}
-				__builtin_amdgcn_sched_barrier(0);
-				#pragma unroll
-				for (int u = 0; u < kMipBatch; u++) {
-					if (!kSkip || fetched[u] != 0ull) {     // (lanes that did not fetch hold 0)
-						uint32_t s = voxel_of<BPV, LAYOUT>(word[u]);
-						if (!kSkip) s = counts[u] ? s : 0u;
-						m = s > m ? s : m;
-					}
-				}
-				if (kSkip && m >= stop_at) { VR_MIP_COUNT_REST(); live = false; }
-			}
-		};
-		if (skipping) march(std::true_type()); else march(std::false_type());
-		colour = tf4[(BPV == 1 ? m : (m >> 8)) / VR_TF_RATIO];
-	} else {
-		const f3 A = mk3(dir.x * a.half_x, dir.y * a.half_y, dir.z * a.half_z);
-		const f3 B = mk3(VR_FMA(origin.x, a.half_x, a.off_x), VR_FMA(origin.y, a.half_y, a.off_y), VR_FMA(origin.z, a.half_z, a.off_z));
-		auto widen = [](uint32_t high) { return BPV == 1 ? (float) high : (kQ8 ? (float) ((high + 1u) << 8) : (float) ((high << 8) | 0xffu)); };
-		const float stop_at = widen(volume_max);
-		float m = 0.0f;
-		auto march = [&](auto skip_tag) {
-			constexpr bool kSkip = decltype(skip_tag)::value;
-			while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
-				TriFetch<BPV, LAYOUT> f[kMipBatch];
-				float ks[kMipBatch];
-				uint64_t fetched[kMipBatch];
-				bool counts[kMipBatch];
-				#pragma unroll
-				for (int u = 0; u < kMipBatch; u++) {
-					ks[u] = k;
-					counts[u] = live;
-					if constexpr (kSkip) {
-						const bool need = live && widen(mip_bound_lds[bound_index(march_point<SAMPLING>(origin, dir, k))]) > m;
-						f[u].w0 = f[u].w1 = f[u].w2 = f[u].w3 = 0u; f[u].q = 0ull; f[u].q2 = 0ull; f[u].o = (u32x4) (0u);
-						fetched[u] = __builtin_amdgcn_ballot_w64(need);
-						VR_MIP_COUNT(live, need);
-						if (fetched[u] != 0ull) {
-							if (need) f[u] = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z), true);
-						}
-						k += step;
-					} else {
-						fetched[u] = ~0ull;
-						f[u] = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z), true);
-						k += live ? step : 0.0f;
-					}
-					live = live && k <= ky;
-				}
-				__builtin_amdgcn_sched_barrier(0);
-				#pragma unroll
-				for (int u = 0; u < kMipBatch; u++) {
-					if (!kSkip || fetched[u] != 0ull) {     // (lanes that did not fetch resolve zeros to 0: m >= 0 keeps them unchanged)
-						const float raw = tri_resolve<BPV, LAYOUT, kQ8>(f[u], a, VR_FMA(ks[u], A.x, B.x), VR_FMA(ks[u], A.y, B.y), VR_FMA(ks[u], A.z, B.z));
-						m = ((kSkip || counts[u]) && raw > m) ? raw : m;
-					}
-				}
-				if (kSkip && m >= stop_at) { VR_MIP_COUNT_REST(); live = false; }
-			}
-		};
-		if (skipping) march(std::true_type()); else march(std::false_type());
-		// the filtered lookup of a DVR sample (raymarch_kernel; GPURenderer4.cu:77): entries floor(tb) and floor(tb) + 1, clamp addressing
-		const float tb = __builtin_amdgcn_fmed3f(VR_FMA(m, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
-		const uint32_t i = (uint32_t) (int) tb, i1 = i + 1u < VR_TF_SIZE ? i + 1u : i;
-		const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
-		const f4 c0 = tf4[i], c1 = tf4[i1];
-		colour.x = VR_FMA(w, c1.x - c0.x, c0.x); colour.y = VR_FMA(w, c1.y - c0.y, c0.y);
-		colour.z = VR_FMA(w, c1.z - c0.z, c0.z); colour.w = VR_FMA(w, c1.w - c0.w, c0.w);
-	}
-
-	// -- RaycasterBase.h:44-50 write_color of the entry as it is stored (+ the fused clear: misses store 0)
-	uint32_t rgba = 0;
-	if (hit) {
-		rgba = map_float_int(colour.x, 256) | (map_float_int(colour.y, 256) << 8) |
-		       (map_float_int(colour.z, 256) << 16) | (map_float_int(colour.w, 256) << 24);
-	}
-	*out_px = rgba;
-#ifdef VR_MIP_STATS
-	if (skipping) {
-		atomicAdd((unsigned long long *) (bounds_g + kMipStatsAt), (unsigned long long) stat_samples);
-		atomicAdd((unsigned long long *) (bounds_g + kMipStatsAt + 8u), (unsigned long long) stat_fetches);
-	}
-#endif
-#undef VR_MIP_COUNT
-#undef VR_MIP_COUNT_REST
+	constexpr bool CLIP = false;
+#include "vr_mip_body.inc"
+}
+// ... of a clipped frame (vr_hip_set_clip); a name of its own for the same reason as raymarch_clipped's
+template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
+__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
+void mip_clipped(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
+                 uint32_t *__restrict__ out) {
+	constexpr bool CLIP = true;
+#include "vr_mip_body.inc"
 }
 
 // block maxima of the min/max scan -> the MIP bounds (vr_device.h): one thread per block of the 32^3 grid
@@ -2459,6 +1901,7 @@ RaymarchPlan plan_raymarch(const RayKernelArgs &a, bool have_bricked, uint32_t b
 hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
                            const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
 	if (bricked != nullptr && (args.layout == kLayoutColumn || args.layout == kLayoutVoxCol)) {      // orthogonal view along args.col_axis, full march, 1-byte voxels (launch_frame)
+		if (args.clip_on) return hipErrorInvalidValue;           // the column kernels march the whole cube: launch_frame takes none for a clipped frame
 		RayKernelArgs a = args;
 		tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, 512u, a.tiles_x, a.tiles_y);
 		const dim3 grid(a.tiles_x * a.tiles_y), block(512);
@@ -2496,7 +1939,12 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
 #define VR_PAD_LAYOUTS ((1u << kLayoutRun) | (1u << kLayoutRunY) | (1u << kLayoutRunDual))
 #endif
 		const uint32_t dynamic_lds = ((VR_PAD_LAYOUTS >> LAYOUT) & 1u) && !a.p.esl ? VR_RUN_LDS_PAD : 0;
-		hipLaunchKernelGGL((raymarch_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
+		auto kernel = raymarch_kernel<SAMPLING, BPV, ADDR, LAYOUT>;
+		if (a.clip_on) {                                         // a clipped frame: its own kernels, none of which reads a run copy (launch_frame asks for none)
+			if constexpr (is_run_layout(LAYOUT)) return hipErrorInvalidValue;
+			else kernel = raymarch_clipped<SAMPLING, BPV, ADDR, LAYOUT>;
+		}
+		hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
 		                   a, reads_linear ? linear : bricked, tf, esl, (uint32_t *) out, sched.order, sched.cost);
 		return hipGetLastError();
 	});
@@ -2514,7 +1962,8 @@ hipError_t launch_mip(const RayKernelArgs &args, const void *linear, const void 
 			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
 			// the bound table is dynamic LDS, so that frames which do not skip keep every resident workgroup the address tables allow
 			const uint32_t dynamic_lds = a.p.esl != 0u ? kMipBoundEntries : 0u;
-			hipLaunchKernelGGL((mip_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
+			auto kernel = a.clip_on ? mip_clipped<SAMPLING, BPV, ADDR, LAYOUT> : mip_kernel<SAMPLING, BPV, ADDR, LAYOUT>;
+			hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
 			                   a, reads_linear ? linear : bricked, tf, bounds, (uint32_t *) out);
 			return hipGetLastError();
 		}
@@ -2541,143 +1990,22 @@ hipError_t launch_mip(const RayKernelArgs &args, const void *linear, const void 
 // 32 KiB, and reads it with the same block index.  k advances for every sample; bisection and gradient fetches are never skipped.
 extern __shared__ __attribute__((aligned(16))) uint32_t iso_skip_lds[];      // VR_ESL_VOLUME_SIZE words of dynamic LDS, only for frames that skip
 
+// iso_kernel and iso_clipped (a clipped frame: the segment narrowed by clip_segment — a hit at its first sample is the cut face, k* = the
+// clipped kx, shaded from the field's gradient there) are one body, vr_iso_body.inc, compiled with CLIP = false / true
 template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
 __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
 void iso_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
                 const float level, const uint32_t refine, uint32_t *__restrict__ out, float *__restrict__ depth) {
-	typedef LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)> L;
-	constexpr uint32_t kThreads = L::threads;
-	constexpr bool kQ8 = SAMPLING == VR_SAMPLE_TRILINEAR_Q8;
-	static_assert(SAMPLING != VR_SAMPLE_NEAREST, "a gradient-shaded first hit is defined on the interpolated field");
-	__shared__ __attribute__((aligned(16))) uint32_t lut[L::words];
-	const bool skipping = a.p.esl != 0u;                            // wave-uniform: a kernel argument
-	if constexpr (L::max_dim != 0) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);
-	if (skipping) {
-		// word (z * 32 + y), bit x: the block's dilated bound, widened as mip_kernel widens it, is below the level
-		auto widen = [](uint32_t high) { return BPV == 1 ? (float) high : (kQ8 ? (float) ((high + 1u) << 8) : (float) ((high << 8) | 0xffu)); };
-		const uint4 *src = (const uint4 *) (bounds_g + kMipBoundEntries);
-		for (uint32_t w = threadIdx.x; w < VR_ESL_VOLUME_SIZE; w += kThreads) {
-			const uint4 lo16 = src[2u * w], hi16 = src[2u * w + 1u];
-			const uint32_t bytes[8] = { lo16.x, lo16.y, lo16.z, lo16.w, hi16.x, hi16.y, hi16.z, hi16.w };
-			uint32_t bits = 0u;
-			#pragma unroll
-			for (uint32_t x = 0; x < 32u; x++) bits |= (widen((bytes[x >> 2] >> (8u * (x & 3u))) & 0xffu) < level ? 1u : 0u) << x;
-			iso_skip_lds[w] = bits;
-		}
-	}
-	__syncthreads();
-
-	uint32_t tile_x, tile_y, lx, ly;
-	tile_to_xy(a.tiles_x, a.tiles_y, blockIdx.x, blockIdx.x, tile_x, tile_y);
-	lane_pixel<kThreads>(a, tile_x, tile_y, lx, ly);
-	if (lx >= a.p.out_width || ly >= a.p.out_rows)
-		return;                                     // no barrier below this point
-	const size_t px = (size_t) ly * a.p.out_width + lx;
-
-	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
-	f3 origin = ray.origin, dir = ray.dir;
-	float kx = ray.kx, ky = ray.ky;
-	const float step = a.p.ray_step;
-	const bool alive = ray.alive;
-	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a segment: position 0, never live
-
-	const f3 A = mk3(dir.x * a.half_x, dir.y * a.half_y, dir.z * a.half_z);
-	const f3 B = mk3(VR_FMA(origin.x, a.half_x, a.off_x), VR_FMA(origin.y, a.half_y, a.off_y), VR_FMA(origin.z, a.half_z, a.off_z));
-	auto fetch_at = [&](float xb, float yb, float zb) { return tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, xb, yb, zb, true); };
-	auto value_of = [&](const TriFetch<BPV, LAYOUT> &f, float xb, float yb, float zb) { return tri_resolve<BPV, LAYOUT, kQ8>(f, a, xb, yb, zb); };
-	auto below_level = [&](float k) {
-		const BlockIdx b = block_index(a, march_point<SAMPLING>(origin, dir, k));
-		return ((iso_skip_lds[b.z * VR_ESL_VOLUME_DIMS + b.y] >> (b.x & 31u)) & 1u) != 0u;
-	};
-
-	// -- the march: mip_kernel's two instantiations of the batch, consumed in order; `took` = the lane sampled here (and fetched)
-	float k = kx, lo = kx, hi = kx, k_before = kx;
-	bool live = alive, found = false;
-	auto march = [&](auto skip_tag) {
-		constexpr bool kSkip = decltype(skip_tag)::value;
-		while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
-			TriFetch<BPV, LAYOUT> f[kMipBatch];
-			float ks[kMipBatch];
-			uint64_t fetched[kMipBatch];
-			bool took[kMipBatch];
-			#pragma unroll
-			for (int u = 0; u < kMipBatch; u++) {
-				ks[u] = k;
-				if constexpr (kSkip) {
-					took[u] = live && !below_level(k);
-					f[u].w0 = f[u].w1 = f[u].w2 = f[u].w3 = 0u; f[u].q = 0ull; f[u].q2 = 0ull; f[u].o = (u32x4) (0u);
-					fetched[u] = __builtin_amdgcn_ballot_w64(took[u]);
-					if (fetched[u] != 0ull) {
-						if (took[u]) f[u] = fetch_at(VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z));
-					}
-					k += step;
-				} else {
-					took[u] = live;
-					fetched[u] = ~0ull;
-					f[u] = fetch_at(VR_FMA(k, A.x, B.x), VR_FMA(k, A.y, B.y), VR_FMA(k, A.z, B.z));
-					k += live ? step : 0.0f;
-				}
-				live = live && k <= ky;
-			}
-			__builtin_amdgcn_sched_barrier(0);
-			#pragma unroll
-			for (int u = 0; u < kMipBatch; u++) {
-				if (!kSkip || fetched[u] != 0ull) {     // (a lane that did not fetch resolves zeros: `took` keeps it out)
-					const float raw = value_of(f[u], VR_FMA(ks[u], A.x, B.x), VR_FMA(ks[u], A.y, B.y), VR_FMA(ks[u], A.z, B.z));
-					if (took[u] && !found && raw >= level) { found = true; hi = ks[u]; lo = u == 0 ? k_before : ks[u > 0 ? u - 1 : 0]; }
-				}
-			}
-			k_before = ks[kMipBatch - 1];
-			live = live && !found;
-		}
-	};
-	if (skipping) march(std::true_type()); else march(std::false_type());
-
-	// -- after the loop: bisection, then the gradient, for the waves that hold a surface pixel
-	float shade = 1.0f;
-	if (__builtin_amdgcn_ballot_w64(found) != 0ull) {
-		for (uint32_t r = 0; r < refine; r++) {
-			const float mid = 0.5f * (lo + hi);
-			const float xb = VR_FMA(mid, A.x, B.x), yb = VR_FMA(mid, A.y, B.y), zb = VR_FMA(mid, A.z, B.z);
-			const bool reached = value_of(fetch_at(xb, yb, zb), xb, yb, zb) >= level;
-			hi = reached ? mid : hi;
-			lo = reached ? lo : mid;
-		}
-		if (!(a.p.light_kd <= 0.01f)) {
-			const float xb = VR_FMA(hi, A.x, B.x), yb = VR_FMA(hi, A.y, B.y), zb = VR_FMA(hi, A.z, B.z);
-			const TriFetch<BPV, LAYOUT> fxp = fetch_at(xb + 1.0f, yb, zb), fxm = fetch_at(xb - 1.0f, yb, zb);
-			const TriFetch<BPV, LAYOUT> fyp = fetch_at(xb, yb + 1.0f, zb), fym = fetch_at(xb, yb - 1.0f, zb);
-			const TriFetch<BPV, LAYOUT> fzp = fetch_at(xb, yb, zb + 1.0f), fzm = fetch_at(xb, yb, zb - 1.0f);
-			__builtin_amdgcn_sched_barrier(0);
-			const float gx = (value_of(fxp, xb + 1.0f, yb, zb) - value_of(fxm, xb - 1.0f, yb, zb)) * a.half_x;
-			const float gy = (value_of(fyp, xb, yb + 1.0f, zb) - value_of(fym, xb, yb - 1.0f, zb)) * a.half_y;
-			const float gz = (value_of(fzp, xb, yb, zb + 1.0f) - value_of(fzm, xb, yb, zb - 1.0f)) * a.half_z;
-			const float gg = VR_FMA(gz, gz, VR_FMA(gy, gy, gx * gx));
-			float s = 0.0f;
-			if (gg > 0.0f) {
-				const f3 pt = march_point<SAMPLING>(origin, dir, hi);
-				const f3 dl = mk3(a.p.view.light_pos[0] - pt.x, a.p.view.light_pos[1] - pt.y, a.p.view.light_pos[2] - pt.z);
-				const float il = rsqrt_nr(VR_FMA(dl.z, dl.z, VR_FMA(dl.y, dl.y, dl.x * dl.x)));
-				const float dot = VR_FMA(gz, dl.z, VR_FMA(gy, dl.y, gx * dl.x));
-				s = __builtin_fminf(__builtin_fabsf((dot * rsqrt_nr(gg)) * il), 1.0f);      // two-sided: lit alike from inside and outside
-			}
-			shade = VR_FMA(a.p.light_kd, s, 1.0f - a.p.light_kd);
-		}
-	}
-
-	// -- write_color of the level's filtered transfer-function lookup (the arithmetic of mip_kernel's), shaded; misses store 0 and -1
-	uint32_t rgba = 0;
-	if (found) {
-		const f4 *tf4 = (const f4 *) tf_g;
-		const float tb = __builtin_amdgcn_fmed3f(VR_FMA(level, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
-		const uint32_t i = (uint32_t) (int) tb, i1 = i + 1u < VR_TF_SIZE ? i + 1u : i;
-		const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
-		const f4 c0 = tf4[i], c1 = tf4[i1];
-		const float cx = VR_FMA(w, c1.x - c0.x, c0.x), cy = VR_FMA(w, c1.y - c0.y, c0.y), cz = VR_FMA(w, c1.z - c0.z, c0.z), cw = VR_FMA(w, c1.w - c0.w, c0.w);
-		rgba = map_float_int(cx * shade, 256) | (map_float_int(cy * shade, 256) << 8) | (map_float_int(cz * shade, 256) << 16) | (map_float_int(cw, 256) << 24);
-	}
-	out[px] = rgba;
-	if (depth != nullptr) depth[px] = found ? hi : -1.0f;       // (wave-uniform: a kernel argument)
+	constexpr bool CLIP = false;
+#include "vr_iso_body.inc"
+}
+// ... of a clipped frame (vr_hip_set_clip); a name of its own for the same reason as raymarch_clipped's
+template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
+__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
+void iso_clipped(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g, const uint8_t *__restrict__ bounds_g,
+                 const float level, const uint32_t refine, uint32_t *__restrict__ out, float *__restrict__ depth) {
+	constexpr bool CLIP = true;
+#include "vr_iso_body.inc"
 }
 
 hipError_t launch_iso(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf, const uint8_t *bounds,
@@ -2693,7 +2021,8 @@ hipError_t launch_iso(const RayKernelArgs &args, const void *linear, const void 
 			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
 			// the bit table is dynamic LDS: 4 KiB next to the address tables keep every resident workgroup frames without skipping have
 			const uint32_t dynamic_lds = a.p.esl != 0u ? VR_ESL_VOLUME_SIZE * 4u : 0u;
-			hipLaunchKernelGGL((iso_kernel<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
+			auto kernel = a.clip_on ? iso_clipped<SAMPLING, BPV, ADDR, LAYOUT> : iso_kernel<SAMPLING, BPV, ADDR, LAYOUT>;
+			hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
 			                   a, reads_linear ? linear : bricked, tf, bounds, level, refine, (uint32_t *) out_rgba, (float *) out_depth);
 			return hipGetLastError();
 		}

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib
+from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip
 
 
 class HipRenderer:
@@ -90,6 +90,15 @@ class HipRenderer:
     def set_tile_scheduling(self, mode=1):
         """0: tile = workgroup id; 1 (default): measured-cost order for frames with ESL / ERT on (most expensive tiles first); speed only."""
         self._check(self._L.vr_hip_set_tile_scheduling(self._ctx, int(mode)), "set_tile_scheduling")
+
+    def set_clip(self, box_min=None, box_max=None, plane=None):
+        """vr_hip_set_clip: every later composite, MIP and isosurface frame is cropped to the box [box_min, box_max] (model space: the cube
+        is [-1,1]^3; missing = the whole cube) and cut by the plane (nx, ny, nz, d), keeping nx*x + ny*y + nz*z + d >= 0 (missing = none)."""
+        self._check(self._L.vr_hip_set_clip(self._ctx, C.byref(make_clip(box_min, box_max, plane))), "set_clip")
+
+    def clear_clip(self):
+        """Clipping off (the default)."""
+        self._check(self._L.vr_hip_set_clip(self._ctx, None), "clear_clip")
 
     def last_launch(self):
         """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
@@ -260,6 +269,13 @@ class MultiRenderer:
         tf = np.ascontiguousarray(tf_premult, dtype=np.float32)
         esl = np.ascontiguousarray(esl_bits, dtype=np.uint32)
         self._check(self._L.vr_hip_multi_set_transfer_fn(self._m, tf.ctypes.data, esl.ctypes.data), "set_transfer_fn")
+
+    def set_clip(self, box_min=None, box_max=None, plane=None):
+        """vr_hip_multi_set_clip: HipRenderer.set_clip on every device's context."""
+        self._check(self._L.vr_hip_multi_set_clip(self._m, C.byref(make_clip(box_min, box_max, plane))), "set_clip")
+
+    def clear_clip(self):
+        self._check(self._L.vr_hip_multi_set_clip(self._m, None), "clear_clip")
 
     def set_volume(self, voxels):
         v = np.ascontiguousarray(voxels)
