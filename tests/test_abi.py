@@ -84,6 +84,13 @@ def test_hot_kernels_keep_eight_waves_per_simd(vr):
     if not os.path.exists(log):
         subprocess.check_call(["make", "-B", "-C", csrc])
     text = open(log).read()
+    # the log is the remarks of every translation unit, concatenated at the link: a kernel instantiated in two units, or a stale piece of
+    # log, shows as a name that is there twice.  266 kernels of the vr_*.hip units (composite march 42 + 36 clipped, MIP 36 + 36,
+    # isosurface 24 + 24, column marches 42, copy builders 15, tile order / feeders / generator 11) + the 3 of vr_multi.cpp.  The count is that
+    # of the default flags (a `make EXTRA=...` in place writes this log too)
+    names = re.findall(r"Function Name: (\S+)", text)
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(names) == 266 + 3, len(names)
     found = 0
     for m in re.finditer(r"Function Name: (\S*raymarch_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d)E\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?"
                          r"ScratchSize \[bytes/lane\]: (\d+)", text, flags=re.S):

@@ -1,4 +1,4 @@
-"""Every brick-copy builder (vr_kernels.hip brick_strip_kernel: quad bricks per chunk plane, voxel bricks, oct bricks, run bricks
+"""Every brick-copy builder (vr_builders.hip brick_strip_kernel: quad bricks per chunk plane, voxel bricks, oct bricks, run bricks
 along z / y) against a host-side numpy construction of the layout vr_device.h defines, byte for byte — power-of-two and ragged
 edges, 1- and 2-byte voxels.  The images only ever read elements inside the volume; this test also pins the zero fill outside it
 and the clamped +1 neighbours at the upper faces."""

@@ -1,4 +1,5 @@
-// vr_device.h — launch interface between the C ABI (vr_hip_api.cpp) and the gfx950 kernels (vr_kernels.hip).
+// vr_device.h — launch interface between the C ABI (vr_hip_api.cpp) and the gfx950 kernel units (vr_raymarch.hip, vr_project.hip,
+// vr_kernels.hip, vr_schedule.hip, vr_builders.hip; what they share among themselves is vr_march.h).
 // Internal to libvr_hip.so; the public boundary is include/vr_hip.h.
 #pragma once
 
@@ -90,7 +91,7 @@ struct RayKernelArgs {
 		                               // quad-element copy at alt_copy (voxcol_pairs_kernel: nw is then the voxel windows')
 	} col_shade;
 	// vr_hip_set_clip (include/vr_hip.h vr_clip): the crop box and the kept half-space of a clipped frame.  Read by the
-	// *_clipped kernels only (vr_kernels.hip clip_segment) — the kernels of unclipped frames never look at these words; clip_on is for the host
+	// *_clipped kernels only (vr_march.h clip_segment) — the kernels of unclipped frames never look at these words; clip_on is for the host
 	uint32_t clip_on;
 	float    clip_min[3], clip_max[3], clip_plane[4];
 #ifdef VR_BOUNDS_CHECK
@@ -109,7 +110,7 @@ struct RayKernelArgs {
 #ifndef VR_TILE_ORDER
 #define VR_TILE_ORDER 8
 #endif
-// Which tiles of an 8x8-tile block share an XCD (vr_kernels.hip tile_to_xy, measurements there): 5 = the tiles of a block are numbered
+// Which tiles of an 8x8-tile block share an XCD (vr_march.h tile_to_xy, measurements there): 5 = the tiles of a block are numbered
 // column by column, so that in workgroup order XCD x renders ROW x of every block.
 #ifndef VR_XCD_MODE
 #define VR_XCD_MODE 5
@@ -130,7 +131,7 @@ inline void tile_number_to_xy(uint32_t tile, uint32_t tiles_x, uint32_t tiles_y,
 	else { rest -= right_n; *y = full_rows * B + rest / tiles_x; *x = rest % tiles_x; }
 }
 
-// measured-cost launch order of a frame (vr_kernels.hip tile_order_kernel): order = workgroup id -> tile number or NULL (identity);
+// measured-cost launch order of a frame (vr_schedule.hip tile_order_kernel): order = workgroup id -> tile number or NULL (identity);
 // cost = per tile, the longest wave of the tile in 64-cycle units, or NULL (not recorded)
 struct TileSchedule { const uint32_t *order = nullptr; uint32_t *cost = nullptr; };
 
@@ -306,6 +307,9 @@ inline uint64_t bricked_elems(uint32_t dim_x, uint32_t dim_y, uint32_t dim_z) {
 hipError_t launch_raymarch(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
                            const float *tf_premult /* 128 x float4 */, const uint32_t *esl_bits /* 1024 */,
                            void *out_rgba, TileSchedule sched, hipStream_t stream);
+// the column kernels' frame (a.layout kLayoutColumn / kLayoutVoxCol, `copy` = those column windows; a clipped frame is
+// hipErrorInvalidValue): launch_raymarch hands it over, vr_kernels.hip launches it
+hipError_t launch_colmarch(const RayKernelArgs &a, const void *copy, const float *tf_premult, void *out_rgba, hipStream_t stream);
 
 // what launch_raymarch will do with these arguments: whether the variant reads the LINEAR array (refused once that was released),
 // and its grid of workgroup tiles (32x16 pixels, 32x32 for the 64-bit address tables)

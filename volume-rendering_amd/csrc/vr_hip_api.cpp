@@ -1,5 +1,5 @@
 // vr_hip_api.cpp — the C ABI of include/vr_hip.h: one opaque context per GPU that owns the device copies of the
-// volume / transfer function / ESL bit-volume / framebuffer and launches the gfx950 kernels of vr_kernels.hip.
+// volume / transfer function / ESL bit-volume / framebuffer and launches the gfx950 kernels of the units behind vr_device.h.
 //
 // It replaces the device management the reference spreads over GPURenderer1.cu:17-28,65-112, GPURenderer23.cu:55-81
 // and GPURenderer4.cu:89-153 (static globals, cudaMalloc/cudaMemcpy per set_*, cuda_safe_call -> exit).  Differences
@@ -72,7 +72,7 @@ struct vr_ctx {
 	                  uint32_t dual_state = 0;
 	                  hipEvent_t order_ready = nullptr; hipStream_t order_stream = nullptr; };
 	MapEntry map_cache[32]; uint32_t map_cached = 0, map_next = 0;      // (8 benchmark views x the two row slices of vr_hip_render, and the whole frames beside them)
-	// Measured-cost launch orders (vr_kernels.hip tile_order_kernel), keyed by what the cost of a tile DEPENDS on — sampling mode,
+	// Measured-cost launch orders (vr_schedule.hip tile_order_kernel), keyed by what the cost of a tile DEPENDS on — sampling mode,
 	// leaping / termination on or off, projection, the view's major axis, the band partition, the tile grid and the copy read — not by
 	// the byte image of the parameters: a camera that moves keeps its entry, every frame launches its tiles in the order the most recent
 	// FINISHED recording gives and records its own costs for the next one; a frame repeated with identical parameters stops recording
@@ -445,7 +445,7 @@ const void *resident_fallback(const vr_ctx *c, uint32_t sampling, bool run_copie
 	return nullptr;
 }
 
-// In-cube sample coordinates are exact to ~2^-23 * (1 + 2 max|origin|) * N/2 texels; the unclamped fetch (vr_kernels.hip)
+// In-cube sample coordinates are exact to ~2^-23 * (1 + 2 max|origin|) * N/2 texels; the unclamped fetch (vr_march.h)
 // needs them inside (-1, N), i.e. an error below 1/2.  True with a factor-4 margin.
 float max_abs_origin(const vr_params *p) { return std::fmax(std::fabs(p->view.origin[0]), std::fmax(std::fabs(p->view.origin[1]), std::fabs(p->view.origin[2]))); }
 bool fetch_coordinates_exact(const vr_ctx *c, const vr_params *p) { return (1.0f + 2.0f * max_abs_origin(p)) * (float) max_dim_of(c) < 1048576.0f; }

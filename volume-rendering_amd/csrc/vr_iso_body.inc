@@ -1,4 +1,4 @@
-// vr_iso_body.inc — the statements of iso_kernel and iso_clipped (vr_kernels.hip, which includes this text inside both with `constexpr bool CLIP`
+// vr_iso_body.inc — the statements of iso_kernel and iso_clipped (vr_project.hip, which includes this text inside both with `constexpr bool CLIP`
 // set): a, vol, tf_g, bounds_g, level, refine, out, depth are the kernel's parameters.
 	typedef LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)> L;
 	constexpr uint32_t kThreads = L::threads;

@@ -1,4 +1,4 @@
-// vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_kernels.hip, which includes this text inside both with
+// vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
 // `constexpr bool CLIP` set): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
