@@ -22,7 +22,7 @@ namespace vr {
 //     fetches from each lane's true column.
 // Waves whose live lanes do not share kx and the coordinate along m (none on pose (0,0,0) and (90,0,0), 256 of 65536 on (180,90,0)),
 // whose columns would flip by more than one cell, or whose lateral spread leaves the 32-bit offset range, march per lane with explicit
-// fetches from the same copy (exact, unpipelined).  Arithmetic per composited sample is the general kernel's, expression by expression.
+// fetches from the same copy (exact; pipelined: col_lane_march).  Arithmetic per composited sample is the general kernel's, expression by expression.
 //
 // Three kernels march this way: colmarch_kernel (TRILINEAR, quad-element windows), colmarch_nearest_kernel (NEAREST, voxel windows)
 // and voxcol_tri_kernel (TRILINEAR, voxel windows).  What they share is written once, below: the ray of a lane (col_ray_setup), the
@@ -248,6 +248,50 @@ __device__ __forceinline__ void col_for_window_samples(const ColBatch &b, int &p
 	pos = pos < 64 ? pos : 63;
 }
 
+// The per-lane march of the waves that cannot take the column path (live lanes that do not share kx bit for bit — on pose (180,90,0)
+// one row of waves, where origin.x leaves 2.0 by one ulp —, a rectangle above 64 columns, offsets out of range, forced column frames):
+// every lane marches its own k with explicit fetches from its true column.  Exact as before, and software-pipelined: the fetch of sample
+// n + DEPTH is issued before sample n is consumed, so a sample costs its instructions instead of one memory round trip (a fallback wave of
+// the 1025-sample benchmark march took 0.4 ms at one round trip per sample and ended the frame 0.25-0.3 ms after every other wave).
+//   * Two running values instead of a ring of k's: `k` (the sample consumed) and k_issue (the sample fetched) go through the same
+//     sequential k += step from the same start, so every k keeps the bits the reference's loop gives it.
+//   * issue(kk, slot) forms the address of the sample at kk as the unpipelined fetch did and starts ONE managed load (vr_march.h:
+//     the compiler does not see it, or it would wait for everything at the loop's back edge) into the slot's own registers;
+//     consume(slot) is the kernel's sample() on what landed there.  The loop is written once per slot, rotated: no register copies.
+//     Loads the compiler issues inside consume (the shading fetch) only add to the counter: managed_wait<DEPTH> then waits for more.
+//   * Fetches run DEPTH samples past a lane's ky, and from kx on for lanes without a segment (they did before, too: every lane of a wave
+//     fetches for as long as one lane is live).  Any position is in bounds: col_pair_address clamps its three indices with v_med3 and
+//     colmarch_nearest_kernel's voxel_address with map_float_int (float -> int saturates, NaN gives 0), and the bounds-checked build
+//     holds both addresses against the copy (VR_BC_POINTER inside them) like every other managed load.
+#ifndef VR_COL_LANE_DEPTH
+#define VR_COL_LANE_DEPTH 6
+#endif
+constexpr int kColLaneDepth = VR_COL_LANE_DEPTH;
+template <int DEPTH, class Slot, class Issue, class Consume>
+__device__ __forceinline__ void col_lane_march(float &k, float step, const float &ky, uint64_t &live, Issue issue, Consume consume) {
+	static_assert(DEPTH >= 1 && DEPTH <= 16, "one load per slot: vmcnt(DEPTH)");
+	Slot slot[DEPTH + 1];
+	slot[DEPTH] = 0;
+	float k_issue = k;
+	static_for<0, DEPTH>([&](auto j) { issue(k_issue, slot[j.value]); k_issue += step; });
+	while (live != 0ull) {
+		static_for<0, DEPTH + 1>([&](auto jc) {
+			constexpr int c = decltype(jc)::value, n = (c + DEPTH) % (DEPTH + 1);
+			if (live != 0ull) {
+				issue(k_issue, slot[n]); k_issue += step;
+				__builtin_amdgcn_sched_barrier(0);
+				pin(slot[c]); managed_wait<DEPTH>(); pin(slot[c]);
+				consume(slot[c]);
+				k += step;
+				live &= __builtin_amdgcn_fcmpf(k, ky, kFcmpOLE);
+			}
+		});
+	}
+	static_for<0, DEPTH + 1>([&](auto j) { pin(slot[j.value]); });      // nothing in flight into registers the kernel releases (col_drain)
+	managed_wait<0>();
+	static_for<0, DEPTH + 1>([&](auto j) { pin(slot[j.value]); });
+}
+
 // Column flips.  A lane's lateral cell changes at the smallest float t in (kx, ky] with cell(t) != cell(kx): bisection over the
 // positive float bit patterns, once per ray; returns t's bits (kx's for a lane that does not flip).
 template <class Cell>
@@ -459,15 +503,9 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 	auto coords = [&](ColConstArgs q, float kk, float &xb, float &yb, float &zb) {          // fma(k, A, B) with A = direction * N/2 (col_sample: the same fp32 products, formed by the host)
 		xb = VR_FMA(kk, q->col_sample.ax, B.x); yb = VR_FMA(kk, q->col_sample.ay, B.y); zb = VR_FMA(kk, q->col_sample.az, B.z);
 	};
-	auto fetch_at = [&](float kk, uint32_t &w0, uint32_t &w1) {                           // the element pair of the sample at kk, from each lane's true column
-		ColConstArgs q = col_dense_args();
-		float xb, yb, zb;
-		coords(q, kk, xb, yb, zb);
-		const uint2 both = *(const uint2 *) col_pair_address<M>(a, ((ColConstKernelArguments) q)->copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z, q->col_shade.nbu, q->col_shade.nw, xb, yb, zb);
-		w0 = both.x; w1 = both.y;
-	};
-	// the same as a MANAGED gather (the compiler does not see it: a load it knows to be in flight across the window loop's back edge makes
-	// it put s_waitcnt vmcnt(0) in front of every window gather, and the prefetch pipeline is gone): wait with managed_wait<0>() before use
+	// the element pair of the sample at kk, from each lane's true column, as a MANAGED gather (the compiler does not see it: a load it knows
+	// to be in flight across the window loop's back edge makes it put s_waitcnt vmcnt(0) in front of every window gather, and the prefetch
+	// pipeline is gone): wait with managed_wait<>() before use
 	auto fetch_at_managed = [&](float kk, uint64_t &both) {
 		ColConstArgs q = col_dense_args();
 		float xb, yb, zb;
@@ -493,16 +531,13 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 	const float Bm_l = wv.cm_l;
 
 	const bool has_flips = (wv.flips_u | wv.flips_v) != 0ull;
-	// per-lane march with explicit fetches (exact, unpipelined): the few waves that straddle two kx values, and forced testing
+	// per-lane march with explicit fetches (exact, pipelined: col_lane_march): the few waves that straddle two kx values, and forced testing
 	auto per_lane_march = [&]() {
-		while (live != 0ull) {
-			uint32_t w0, w1;
-			fetch_at(k, w0, w1);
-			sample(w0, w1);
-			k += ray.step;
-			live &= __builtin_amdgcn_fcmpf(k, ray.ky, kFcmpOLE);
-		}
+		col_lane_march<kColLaneDepth, uint64_t>(k, ray.step, ray.ky, live,
+			[&](float kk, uint64_t &both) { fetch_at_managed(kk, both); },
+			[&](uint64_t both) { sample((uint32_t) both, (uint32_t) (both >> 32)); });
 	};
+	bool lane_march = !ok;
 	if (ok) {
 		const uint32_t voff0 = (uint32_t) (rel0 + (1ll << 30));
 		const uint64_t s_base = col_scalar_base(copy, ref);
@@ -523,7 +558,7 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 		int pos = 0;                                                        // next sample of the batch
 		int cur = col_first_window(batch, nw);                              // the window being consumed
 		int guard = col_window_budget(dsign, nw, cur, kColSlots);
-		if (!ev.ok || (has_flips && !FLIPS)) per_lane_march();
+		if (!ev.ok || (has_flips && !FLIPS)) lane_march = true;
 		else {
 			ColFrontier<M, kColCells, kColDepth, FLIPS> front;
 			front.start(voff0, cur, dsign, ev);
@@ -566,7 +601,8 @@ void colmarch_kernel(const RayKernelArgs a, const uint8_t *__restrict__ copy, co
 			}
 			col_drain(slot);
 		}
-	} else per_lane_march();
+	}
+	if (lane_march) per_lane_march();                                   // (one call site: its inlined body is DEPTH + 1 samples long)
 	col_store(ray, acc);
 }
 
@@ -683,15 +719,12 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 	// the far face, folded onto Nm - 1 like map_float_int does)
 	auto cell_m = [&](float kk) { const int c = (int) (((om_l + dm * kk) + 1.0f) * half_m); return c == (int) dim_m ? (int) dim_m - 1 : c; };
 	const bool has_flips = (wv.flips_u | wv.flips_v) != 0ull;
-	auto per_lane_march = [&]() {                                        // exact, unpipelined: waves that straddle two kx values, forced testing
-		while (live != 0ull) {
-			ColConstArgs q = col_dense_args();
-			const uint32_t s = *voxel_address_at(q, position(q, k));
-			sample(s);
-			k += ray.step;
-			live &= __builtin_amdgcn_fcmpf(k, ray.ky, kFcmpOLE);
-		}
+	auto per_lane_march = [&]() {                                        // exact, pipelined (col_lane_march): waves that straddle two kx values, forced testing
+		col_lane_march<kColLaneDepth, uint32_t>(k, ray.step, ray.ky, live,
+			[&](float kk, uint32_t &s) { ColConstArgs q = col_dense_args(); managed_load8_at(s, (uint64_t) (uintptr_t) voxel_address_at(q, position(q, kk))); },
+			[&](uint32_t s) { sample(s); });
 	};
+	bool lane_march = !ok;
 	if (ok) {
 		const uint32_t voff0 = (uint32_t) (rel0 + (1ll << 30));
 		const uint64_t s_base = col_scalar_base(copy, ref);
@@ -709,7 +742,7 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 		int pos = 0;
 		int cur = col_first_window(batch, nw);
 		int guard = col_window_budget(dsign, nw, cur, kColSlots);
-		if (!ev.ok || (has_flips && !FLIPS)) per_lane_march();
+		if (!ev.ok || (has_flips && !FLIPS)) lane_march = true;
 		else {
 			ColFrontier<M, kColVoxCells, kColDepth, FLIPS> front;
 			front.start(voff0, cur, dsign, ev);
@@ -753,7 +786,8 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 			}
 			col_drain(slot);
 		}
-	} else per_lane_march();
+	}
+	if (lane_march) per_lane_march();                                   // (one call site: its inlined body is DEPTH + 1 samples long)
 	col_store(ray, acc);
 }
 
@@ -879,7 +913,21 @@ __device__ __forceinline__ void voxcol_march(const RayKernelArgs &a, const uint8
 	const int64_t rel = (int64_t) col_lateral_offset64((uint32_t) own_u, (uint32_t) own_v, stride_u, stride_v) - ref;
 	ok = ok && __builtin_amdgcn_ballot_w64(rel < 0 || rel >= (1ll << 28)) == 0ull;
 
-	auto per_lane_march = [&]() {                                        // exact, unpipelined: waves that straddle two kx values, or too many columns
+	// exact: waves that straddle two kx values, or too many columns.  PAIRS: pipelined (col_lane_march), the element pair as one managed
+	// 8-byte load.  Without PAIRS (vr_hip_set_column_copy(2)) a sample is eight byte loads: 8 (DEPTH + 1) slot registers (40 at
+	// depth 4) beside the ~30 a sample keeps live are past the 64 VGPRs of these kernels, so that body stays unpipelined
+	auto per_lane_march = [&]() {
+		if constexpr (PAIRS) {
+			col_lane_march<kColLaneDepth, uint64_t>(k, ray.step, ray.ky, live,
+				[&](float kk, uint64_t &both) {
+					ColConstArgs q = col_dense_args();
+					const float xb = VR_FMA(kk, q->col_sample.ax, B.x), yb = VR_FMA(kk, q->col_sample.ay, B.y), zb = VR_FMA(kk, q->col_sample.az, B.z);
+					managed_load64(both, (uint64_t) (uintptr_t) col_pair_address<M>(a, (const uint8_t *) (uintptr_t) q->alt_copy, q->col_sample.max_x, q->col_sample.max_y, q->col_sample.max_z,
+					                                                                q->col_shade.nbu, q->col_shade.nwq, xb, yb, zb));
+				},
+				[&](uint64_t both) { sample((uint32_t) both, (uint32_t) (both >> 32)); });
+			return;
+		}
 		while (live != 0ull) {
 			uint32_t w0, w1;
 			fetch_at(k, w0, w1);
