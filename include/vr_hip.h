@@ -314,6 +314,58 @@ typedef struct vr_clip {
 } vr_clip;
 int vr_hip_set_clip(vr_ctx *ctx, const vr_clip *clip);       /* NULL = clipping off (the default) */
 
+/* ---- light-source shadows for composite frames: a light grid and one more filtered fetch per dense sample.  No reference counterpart. ----
+ * The reference's lighting (Raycaster::shade) is one extra sample 0.01 units towards view.light_pos: a local gradient cue.  A shadow makes the
+ * dense part of the volume darken what lies behind it as seen from the light.  It is context state, like the clip: NULL switches it off, which
+ * is the default; without a shadow, or with strength 0, every frame is what it was, byte for byte.  vr_params and every other struct keep
+ * their size and layout.
+ * Shadow volume.  S^3 bytes q (S = dims), x fastest, built on the context's stream — synchronous, like a brick copy — by the first composite
+ * frame, or vr_hip_download_shadow, that finds it missing or stale.  It goes stale on a vr_hip_set_shadow whose struct differs from the
+ * current one in more than `strength` (q does not depend on it: a change of the strength alone keeps the grid), on vr_hip_set_volume* / vr_hip_generate_volume, on vr_hip_set_transfer_fn, and on a vr_hip_set_clip that differs from the
+ * current clip.  Per node (i, j, k):
+ *  1. Position.  n = fma((float) i, 2.0f / (float) (S - 1), -1.0f) per axis.
+ *  2. Light vector.  d = light_pos - n, len2 = fma(d.z, d.z, fma(d.y, d.y, d.x * d.x)).  If !(len2 > 0) then T = 1.  Otherwise
+ *     il = rsqrt_nr(len2) (the Newton reciprocal square root of the TRILINEAR mode's light vector), u = d * il (three plain multiplies),
+ *     dist = len2 * il.
+ *  3. Segment.  intersect(n, u) exactly as for a view ray (exact zeros of u replaced by 0.00001f, kx = flmax(kx, 0)); a miss gives T = 1.
+ *     On a hit, if a clip is set, steps 1-3 of the clip contract are applied to (n, u, kx, ky); a miss there also gives T = 1.
+ *     t_end = flmin(ky, dist).
+ *  4. March.  T = 1; t = flmax(kx, 0) + step (one plain IEEE add; kx is 0 without a clip).  while (t <= t_end): raw = the TRILINEAR (or _Q8,
+ *     by `sampling`) interpolated RAW value at texel coordinates fma(t, A, B) with A = u * half and B = fma(n, half, half - 0.5f) — the
+ *     composite's own A and B, built from the node instead of the ray origin; a = the .w of the linearly filtered transfer-function lookup of
+ *     raw with the arithmetic of a composited sample's lookup (_Q8: rounded weight); T = T * (1.0f - a); if (T < cutoff) { T = 0; break; }
+ *     t += step.  The loop also carries an explicit bound of ceil(2 sqrt(3) / step) + 2 steps, which cannot bind for accepted parameters.
+ *     NOTHING is opacity-corrected for step != ray_step (that takes a powf, which CPU and GPU do not share bit for bit): for shadows as
+ *     dense as the frame sees them, choose step = ray_step.
+ *  5. Store.  q = (uint8_t) (T * 255.0f + 0.5f), product and sum rounded separately.
+ * Shadowed composite frame.  vr_hip_render / vr_hip_render_device (and vr_hip_multi_* through the per-device contexts) composite as before
+ * with one addition: for a sample whose looked-up colour has c.w > 0.05f — whatever light_kd is — the colour is scaled AFTER the diffuse
+ * term is added and BEFORE the sample is accumulated: c.xyz *= f with f = fma(strength * (1.0f / 255.0f), Tq, 1.0f - strength).  Tq is the
+ * trilinear interpolation of q at the sample's model-space point pt = march_point(origin, dir, k), the point the lighting already forms; per
+ * axis v = fmed3(fma(pt, hs, hs), 0, S - 1) with hs = 0.5f * (S - 1), i = min((uint32_t) v, S - 2), w = v - (float) i; lerps fma(w, b - a, a)
+ * along x, then y, then z; full fp32 weights in both sampling modes.  Alpha, leaping, the transparent-sample shortcut and early termination
+ * see the same alphas and are untouched.
+ * Other behaviour.  VR_SAMPLE_NEAREST composite frames under a shadow return VR_ERR_INVALID (the builder and the factor are defined on the
+ * interpolated field: the isosurface's precedent).  MIP and isosurface frames IGNORE the shadow (shadowed isosurfaces are a follow-up).  A
+ * shadowed frame reads what a clipped frame reads — the linear array, quad bricks with the per-view plane, or oct bricks —, never a run copy
+ * or a column window; vr_launch_info::shadowed tells.  Setting or changing the shadow — but for its strength alone — forgets the cached
+ * tile mappings and recorded orders, as vr_hip_set_clip does.  light_pos is independent of view.light_pos (the wrappers set both).
+ * Errors.  VR_ERR_INVALID for a non-finite member, dims outside 2..256, step < 1/4096, strength outside [0,1], cutoff outside [0,1), a
+ * sampling other than VR_SAMPLE_TRILINEAR / _Q8.  vr_hip_download_shadow: VR_ERR_NOT_READY without a shadow, volume or transfer function,
+ * VR_ERR_INVALID for a short buffer, or a NULL one with a capacity (NULL with capacity 0 only reports *dims_out).  vr_hip_shadow_builds counts the builds of the context (testing aid: an identical
+ * vr_hip_set_shadow does not rebuild) and reports the hipEvent time of the last one. */
+typedef struct vr_shadow {
+	float    light_pos[3];  /* model space; the cube is [-1,1]^3.  Independent of view.light_pos (the wrappers set both) */
+	uint32_t dims;          /* S: nodes per edge of the light grid, 2..256 */
+	float    step;          /* march step towards the light, in model units; finite, >= 1/4096 */
+	float    strength;      /* 0..1: 0 = frames equal unshadowed frames byte for byte */
+	float    cutoff;        /* 0 <= cutoff < 1: a light ray whose transmittance falls below it is black */
+	uint32_t sampling;      /* VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8: how the builder samples the volume */
+} vr_shadow;
+int vr_hip_set_shadow(vr_ctx *ctx, const vr_shadow *shadow);      /* NULL = off (the default) */
+int vr_hip_download_shadow(vr_ctx *ctx, uint8_t *host_out, uint64_t capacity, uint32_t *dims_out); /* S^3 bytes, x fastest; builds if stale */
+int vr_hip_shadow_builds(vr_ctx *ctx, uint64_t *builds_out, float *last_build_ms_out);              /* either may be NULL */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {
@@ -330,6 +382,7 @@ typedef struct vr_launch_info {
 	                           quad-element windows (VR_COPY_COL_*); vr_hip_set_column_copy */
 	uint32_t column_shade_pairs; /* column_voxels = 1: 1 = the shading samples were fetched from the quad-element windows (one 8-byte load
 	                           each), 0 = from the voxel windows (eight byte loads: unlit frames, mode 2, or that copy could not be had) */
+	uint32_t shadowed;      /* 1: a shadowed composite frame (vr_hip_set_shadow; layout is then 0, 1 or 5) */
 } vr_launch_info;
 int vr_hip_last_launch(vr_ctx *ctx, vr_launch_info *out);
 
@@ -380,6 +433,7 @@ const char *vr_hip_multi_transport(const vr_multi *m);             /* "rccl" | "
 int  vr_hip_multi_set_window(vr_multi *m, uint32_t width, uint32_t height);
 int  vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf_premult_rgba, const uint32_t *esl_bits);
 int  vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip);      /* vr_hip_set_clip on every device's context */
+int  vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow); /* vr_hip_set_shadow on every device's context */
 int  vr_hip_multi_set_volume(vr_multi *m, const void *host_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);
 int  vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bytes_per_voxel);
 int  vr_hip_multi_render(vr_multi *m, const vr_params *params, uint8_t *host_rgba);           /* whole frame -> host buffer */

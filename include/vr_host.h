@@ -65,6 +65,10 @@ int vr_host_render_frame(int device, uint32_t sampling, const vr_view *view, uin
  * to vr_hip_set_clip, or with a device list to vr_hip_multi_set_clip (include/vr_hip.h has the contract).  NULL = none (the default).
  * Process-global like the rest of this file; an invalid clip makes vr_host_render_frame return 1. */
 void vr_host_set_clip(const vr_clip *clip);
+/* The shadow vr_host_render_frame hands its renderer before the frame: volr::HipRenderer::set_shadow(const vr_shadow *), which forwards to
+ * vr_hip_set_shadow, or with a device list to vr_hip_multi_set_shadow (include/vr_hip.h has the contract).  NULL = none (the default); an
+ * invalid shadow, or a NEAREST frame under a shadow, makes vr_host_render_frame return 1. */
+void vr_host_set_shadow(const vr_shadow *shadow);
 
 #ifdef __cplusplus
 }

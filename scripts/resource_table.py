@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""SGPR / VGPR / occupancy / spills of every kernel in the last build (csrc/resource_usage.log)."""
+"""SGPR / VGPR / occupancy / spills of every kernel in the last build (csrc/resource_usage.log and, for the shadow unit, resource_usage_shadow.log)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-log = open(os.path.join(ROOT, "volume-rendering_amd", "csrc", "resource_usage.log")).read()
+csrc = os.path.join(ROOT, "volume-rendering_amd", "csrc")
+log = open(os.path.join(csrc, "resource_usage.log")).read()
+if os.path.exists(os.path.join(csrc, "resource_usage_shadow.log")):         # the shadow unit's own log (csrc/Makefile)
+    log += open(os.path.join(csrc, "resource_usage_shadow.log")).read()
 pat = sys.argv[1] if len(sys.argv) > 1 else ""
 for b in re.split(r"remark: Function Name: ", log)[1:]:
     name = b.split(" ")[0]

@@ -68,6 +68,21 @@ def make_clip(box_min=None, box_max=None, plane=None):
     return clip
 
 
+class VrShadow(C.Structure):
+    """vr_shadow: the light in model space, the nodes per edge of the light grid, the march step towards the light, strength 0..1, the
+    transmittance below which a light ray is black, and how the builder samples the volume (SAMPLE_TRILINEAR / SAMPLE_TRILINEAR_Q8)"""
+    _fields_ = [("light_pos", C.c_float * 3), ("dims", C.c_uint32), ("step", C.c_float), ("strength", C.c_float), ("cutoff", C.c_float),
+                ("sampling", C.c_uint32)]
+
+
+def make_shadow(light_pos, dims=128, step=0.01, strength=1.0, cutoff=1.0 / 256.0, sampling=SAMPLE_TRILINEAR):
+    sh = VrShadow()
+    for i in range(3):
+        sh.light_pos[i] = float(light_pos[i])
+    sh.dims, sh.step, sh.strength, sh.cutoff, sh.sampling = int(dims), float(step), float(strength), float(cutoff), int(sampling)
+    return sh
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -83,7 +98,7 @@ class VrTiming(C.Structure):
 
 class VrLaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("layout", "brick_plane", "lane_map", "phase_x", "phase_y", "clamp_fetch", "tiles_x", "tiles_y",
-                                          "ordered", "straddle_permille", "column_voxels", "column_shade_pairs")]
+                                          "ordered", "straddle_permille", "column_voxels", "column_shade_pairs", "shadowed")]
 
 
 def library_path():
@@ -127,6 +142,9 @@ def lib():
         "vr_hip_set_column_copy": (C.c_int, [vp, u32]),
         "vr_hip_set_tile_scheduling": (C.c_int, [vp, u32]),
         "vr_hip_set_clip": (C.c_int, [vp, P(VrClip)]),
+        "vr_hip_set_shadow": (C.c_int, [vp, P(VrShadow)]),
+        "vr_hip_download_shadow": (C.c_int, [vp, vp, u64, P(u32)]),
+        "vr_hip_shadow_builds": (C.c_int, [vp, P(u64), f32p]),
         "vr_hip_last_launch": (C.c_int, [vp, P(VrLaunchInfo)]),
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
         "vr_hip_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -155,6 +173,7 @@ def lib():
         "vr_hip_multi_set_window": (C.c_int, [vp, u32, u32]),
         "vr_hip_multi_set_transfer_fn": (C.c_int, [vp, vp, vp]),
         "vr_hip_multi_set_clip": (C.c_int, [vp, P(VrClip)]),
+        "vr_hip_multi_set_shadow": (C.c_int, [vp, P(VrShadow)]),
         "vr_hip_multi_set_volume": (C.c_int, [vp, vp, u32, u32, u32, u32]),
         "vr_hip_multi_generate_volume": (C.c_int, [vp, u32, u32, u32, u32]),
         "vr_hip_multi_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -178,6 +197,7 @@ def lib():
         "vr_host_raycaster_get": (C.c_int, [P(VrParams), vp, vp, vp, vp]),
         "vr_host_render_frame": (C.c_int, [C.c_int, u32, P(VrView), vp]),
         "vr_host_set_clip": (None, [P(VrClip)]),
+        "vr_host_set_shadow": (None, [P(VrShadow)]),
         "vr_host_load_model": (C.c_int, [C.c_char_p, P(u32)]),
         "vr_host_set_raw_dims": (None, [u32, u32, u32, u32]),
         "vr_host_model_voxels": (vp, []),

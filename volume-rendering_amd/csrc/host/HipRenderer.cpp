@@ -100,6 +100,14 @@ int HipRenderer::set_clip(const vr_clip *clip) {
 	return rc == 0 ? 0 : 1;
 }
 
+int HipRenderer::set_shadow(const vr_shadow *shadow) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	const int rc = multi_ ? vr_hip_multi_set_shadow(multi_, shadow) : vr_hip_set_shadow(ctx_, shadow);
+	return rc == 0 ? 0 : 1;
+}
+
 int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 	if (!ok() || buffer == nullptr)
 		return 1;

@@ -97,6 +97,9 @@ class HipRenderer : public Renderer {
 		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
 		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.
 		int set_clip(const vr_clip *clip);
+		// Light-source shadows of every later COMPOSITE frame of this renderer (vr_hip_set_shadow / vr_hip_multi_set_shadow: a light grid
+		// marched towards shadow->light_pos, one more filtered fetch per dense sample); set_mip and set_iso frames ignore it.  NULL = off.
+		int set_shadow(const vr_shadow *shadow);
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:

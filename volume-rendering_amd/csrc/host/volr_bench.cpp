@@ -4,7 +4,8 @@
 //
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
-//              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-o <frame.ppm>]
+//              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
+//              [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,6 +45,8 @@ void print_usage() {
 	       "         trilinear renderer (-r 1; renderer 0 keeps compositing in benchmark mode); single device, excludes -mip\n"
 	       "  -clip-box <x0> <y0> <z0> <x1> <y1> <z1> : crop every frame to this box (model space: the volume is [-1,1]^3)\n"
 	       "  -clip-plane <nx> <ny> <nz> <d> : keep the half-space nx*x + ny*y + nz*z + d >= 0; both work with the composite, -mip and -iso\n"
+	       "  -shadow <S> [-shadow-strength <s>] [-shadow-step <t>] : light-source shadows for the composite of the trilinear renderer (-r 1): a light\n"
+	       "         grid of S^3 nodes (2..256) marched towards the view's light; strength 0..1 (default 1), step in model units (default: the ray step)\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -248,6 +251,8 @@ int main(int argc, char **argv) {
 	int iso_refine = 4;
 	bool clip_box = false, clip_plane = false;
 	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+	int shadow_dims = 0;
+	float shadow_strength = 1.0f, shadow_step = 0.0f;
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
 	ViewBase::reset();
 	for (int i = 1; i < argc; i++) {
@@ -291,6 +296,9 @@ int main(int argc, char **argv) {
 			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
 		}
 		else if (strcmp(arg, "-clip-plane") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) clip.plane[k] = (float) atof(argv[++i]); clip_plane = true; } }
+		else if (strcmp(arg, "-shadow") == 0) { if (need(1)) shadow_dims = atoi(argv[++i]); }
+		else if (strcmp(arg, "-shadow-strength") == 0) { if (need(1)) shadow_strength = (float) atof(argv[++i]); }
+		else if (strcmp(arg, "-shadow-step") == 0) { if (need(1)) shadow_step = (float) atof(argv[++i]); }
 		else if (strcmp(arg, "-pose") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) pose[k] = (float) atof(argv[++i]); have_pose = true; } }
 		else if (strcmp(arg, "-o") == 0) { if (need(1)) out_ppm = argv[++i]; }
 		else printf("Warning: unknown argument: %s\n", arg);
@@ -341,12 +349,26 @@ int main(int argc, char **argv) {
 	}
 
 	int rc = EXIT_SUCCESS;
+	if (!benchmark_mode) {
+		if (persp) ViewBase::toggle_perspective(0);
+		ViewBase::set_camera_position(make_float3(pose[0], pose[1], pose[2]), have_pose ? pose[3] : 3.0f);
+	}
+	if (shadow_dims != 0) {
+		// the light is the view's (benchmark mode: the start view's — the reference's benchmark moves the camera, not the light); the
+		// trilinear renderer only: the light grid and its factor are defined on the interpolated field
+		if (mip || iso) { printf("Error: -shadow works with the composite (drop -mip / -iso)\n"); return EXIT_FAILURE; }
+		if (!benchmark_mode && renderer_id != 1) { printf("Error: -shadow needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
+		vr_shadow sh;
+		sh.light_pos[0] = ViewBase::view.light_pos.x; sh.light_pos[1] = ViewBase::view.light_pos.y; sh.light_pos[2] = ViewBase::view.light_pos.z;
+		sh.dims = (uint32_t) shadow_dims; sh.step = shadow_step > 0.0f ? shadow_step : RaycasterBase::raycaster.ray_step;
+		sh.strength = shadow_strength; sh.cutoff = 1.0f / 256.0f; sh.sampling = VR_SAMPLE_TRILINEAR;
+		if (renderers[1]->set_shadow(&sh) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
+		printf("Shadow: %d^3 nodes, light (%g, %g, %g), step %g, strength %g\n", shadow_dims, sh.light_pos[0], sh.light_pos[1], sh.light_pos[2], sh.step, sh.strength);
+	}
 	if (benchmark_mode) {
 		benchmark();
 		print_profiler();
 	} else {
-		if (persp) ViewBase::toggle_perspective(0);
-		ViewBase::set_camera_position(make_float3(pose[0], pose[1], pose[2]), have_pose ? pose[3] : 3.0f);
 		draw_volume();
 		printf("%s: %dx%d frame in %.2f ms\n", renderers[renderer_id]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);
 		if (!out_ppm.empty() && write_ppm(out_ppm.c_str()) != 0) { printf("Error: cannot write %s\n", out_ppm.c_str()); rc = EXIT_FAILURE; }

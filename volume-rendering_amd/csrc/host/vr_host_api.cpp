@@ -36,6 +36,8 @@ const float kBenchPoses[4][3] = { { 0, 0, 0 }, { -45, -45, 0 }, { 90, 0, 0 }, { 
 
 bool host_clip_on = false;          // vr_host_set_clip: what vr_host_render_frame hands its renderer
 vr_clip host_clip;
+bool host_shadow_on = false;        // vr_host_set_shadow: likewise
+vr_shadow host_shadow;
 
 }  // namespace
 
@@ -128,12 +130,18 @@ void vr_host_set_clip(const vr_clip *clip) {
 	if (clip != nullptr) host_clip = *clip;
 }
 
+void vr_host_set_shadow(const vr_shadow *shadow) {
+	host_shadow_on = shadow != nullptr;
+	if (shadow != nullptr) host_shadow = *shadow;
+}
+
 int vr_host_render_frame(int device, uint32_t sampling, const vr_view *view, uint8_t *host_rgba) {
 	if (view == nullptr) return 1;
 	RaycasterBase::set_view(view_from_c(*view));                                  // VolR.cpp:107
 	HipRenderer renderer(RaycasterBase::raycaster, device, (vr_sampling) sampling);
 	if (!renderer.ok()) return 1;
 	if (host_clip_on && renderer.set_clip(&host_clip) != 0) return 1;
+	if (host_shadow_on && renderer.set_shadow(&host_shadow) != 0) return 1;
 	return renderer.render_volume((uchar4 *) host_rgba, RaycasterBase::raycaster);  // VolR.cpp:110
 }
 

@@ -94,6 +94,17 @@ struct RayKernelArgs {
 	// *_clipped kernels only (vr_march.h clip_segment) — the kernels of unclipped frames never look at these words; clip_on is for the host
 	uint32_t clip_on;
 	float    clip_min[3], clip_max[3], clip_plane[4];
+	// vr_hip_set_shadow (include/vr_hip.h vr_shadow): the light grid a shadowed composite frame scales its dense samples
+	// by.  Read by the raymarch_shadowed kernels only, through the laundered kernel-argument pointer like the clip words; shadow_on is for the
+	// host.  Such a frame always runs clip_segment: without a clip the host fills the identity clip above, which changes no bit.
+	uint32_t shadow_on;
+	uint32_t shadow_last;              // S - 2: the highest cell index per axis
+	float    shadow_hs;                // 0.5f * (S - 1): node coordinate = fma(pt, hs, hs)
+	float    shadow_max;               // (float) (S - 1)
+	float    shadow_scale;             // strength * (1.0f / 255.0f)
+	float    shadow_base;              // 1.0f - strength
+	uint32_t shadow_row, shadow_slab;  // S, S * S: byte strides of the plain array along y and z
+	uint64_t shadow_q;                 // the S^3 bytes q, x fastest
 #ifdef VR_BOUNDS_CHECK
 	// `make EXTRA=-DVR_BOUNDS_CHECK` (debug build, not the product): every gather address of the march is held against the array it must
 	// lie in, every address-table index against its padded table, the tile-cost slot against its buffer; the first violation is recorded
@@ -347,6 +358,25 @@ hipError_t launch_mip(const RayKernelArgs &a, const void *linear, const void *br
 // TRILINEAR bound (the second half of `bounds`) is below `level`.  out_depth (out_width * out_rows floats, laid out like out_rgba) may be NULL.
 hipError_t launch_iso(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                       const uint8_t *bounds, float level, uint32_t refine, void *out_rgba, void *out_depth, hipStream_t stream);
+
+// ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
+// What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
+struct ShadowBuildArgs {
+	float    light[3];
+	uint32_t dims;                     // S
+	float    node_scale;               // 2.0f / (float) (S - 1): node position = fma((float) i, node_scale, -1.0f)
+	float    step, cutoff;
+	uint32_t q8;                       // 1: VR_SAMPLE_TRILINEAR_Q8 weights (volume and transfer function)
+	uint32_t max_steps;                // ceil(2 sqrt(3) / step) + 2: the explicit bound of the march, never binding
+	uint32_t clip_on;                  // 1: the light ray's segment is narrowed by the clip words of RayKernelArgs (clip_segment)
+};
+// Builds q[S^3] (x fastest) on `stream`.  `a`: volume_args with layout one of kLayoutLinear / kLayoutBricked (plane (x,y)) / kLayoutOct and
+// a.p.sampling TRILINEAR — the copy a TRILINEAR MIP frame along z reads; the selector of launch_raymarch picks the addressing path.
+hipError_t launch_shadow_build(const RayKernelArgs &a, const ShadowBuildArgs &s, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
+                               const float *tf_premult, uint8_t *q_out, hipStream_t stream);
+// the shadowed composite frame (a.shadow_on): launch_raymarch hands it over, vr_shadow.hip launches raymarch_shadowed
+hipError_t launch_raymarch_shadowed(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                    const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);

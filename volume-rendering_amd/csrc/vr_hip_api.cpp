@@ -103,6 +103,11 @@ struct vr_ctx {
 	float *iso_depth = nullptr; size_t iso_depth_bytes = 0;
 	// clip region (vr_hip_set_clip): narrows the segment of every ray of every later frame; such frames run the *_clipped kernels
 	bool clip_on = false; vr_clip clip = {};
+	// light-source shadows (vr_hip_set_shadow): the S^3 bytes q of the light grid, built on the context's stream by the first composite frame
+	// or download that finds them missing or stale (shadow_ready false: a changed shadow, volume, transfer function or clip)
+	bool shadow_on = false; vr_shadow shadow = {};
+	uint8_t *shadow_q = nullptr; uint64_t shadow_q_bytes = 0; bool shadow_ready = false;
+	uint64_t shadow_builds = 0; float shadow_build_ms = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -380,6 +385,10 @@ void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 		a.clip_on = 1u;
 		for (int i = 0; i < 3; i++) { a.clip_min[i] = c->clip.box_min[i]; a.clip_max[i] = c->clip.box_max[i]; }
 		for (int i = 0; i < 4; i++) a.clip_plane[i] = c->clip.plane[i];
+	} else {
+		// the identity clip, which changes no bit of a segment by contract: what the kernels that always run clip_segment read when no clip
+		// is set (raymarch_shadowed); clip_on stays 0 and every other kernel ignores these words
+		for (int i = 0; i < 3; i++) { a.clip_min[i] = -1.0f; a.clip_max[i] = 1.0f; }
 	}
 }
 
@@ -541,9 +550,25 @@ int launch_timed(vr_ctx *c, RayKernelArgs &a, const vr_params *p, const Raymarch
 	return VR_OK;
 }
 
+int build_shadow(vr_ctx *c);
+
 int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	// A shadowed frame (vr_hip_set_shadow): the light grid first, on the context's stream and synchronous like a brick copy's first use
+	const bool shadow = c->shadow_on;
+	if (shadow) {
+		if (p->sampling == VR_SAMPLE_NEAREST)
+			return fail(c, VR_ERR_INVALID, "a shadow is set: the light grid and its factor are defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+			                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_shadow(ctx, NULL) switches the shadow off)");
+		if (const int rc = build_shadow(c)) return rc;
+	}
 	RayKernelArgs a;
 	volume_args(c, p, a);
+	if (shadow) {
+		const uint32_t S = c->shadow.dims;
+		a.shadow_on = 1u; a.shadow_last = S - 2u; a.shadow_hs = 0.5f * (float) (S - 1u); a.shadow_max = (float) (S - 1u);
+		a.shadow_scale = c->shadow.strength * (1.0f / 255.0f); a.shadow_base = 1.0f - c->shadow.strength;
+		a.shadow_row = S; a.shadow_slab = S * S; a.shadow_q = (uint64_t) (uintptr_t) c->shadow_q;
+	}
 	const float half[3] = { a.half_x, a.half_y, a.half_z };
 	const ViewAxis va = view_axis(p, half);
 	{   // largest power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below: raw < P implies a transparent sample
@@ -583,7 +608,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		a.near_scaled = (pow2(c->dim[0]) && pow2(c->dim[1]) && pow2(c->dim[2]) && !(c->force_clamp_fetch & 2u)) ? 1u : 0u;
 	}
 	a.force_wide = c->force_wide;
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on;
+	// (a shadowed frame reads what a clipped frame reads: its kernels are the clipped ones with one more fetch per dense sample)
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
 	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
@@ -904,7 +930,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// when it shades from the quad-element windows)
 	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
 	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u,
-	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u };
+	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u, shadow ? 1u : 0u };
 
 	uint64_t frame_seq = 0;
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
@@ -1027,6 +1053,7 @@ int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	free_bricks(c);
 	forget_tile_mappings(c);                     // cached tile mappings belong to the previous volume
 	c->mip_mapped = 0; c->mip_map_next = 0; c->mip_bounds_ready = false;       // ... and so do the block maxima of the MIP frames
+	c->shadow_ready = false;                     // ... and the light grid of a shadow
 	c->dim[0] = c->dim[1] = c->dim[2] = 0;
 	const uint64_t elems = (uint64_t) x * y * z;
 	const uint64_t slack = volume_tail_slack(x, y);
@@ -1120,7 +1147,7 @@ int launch_full_march_frame(vr_ctx *c, const vr_params *p, hipStream_t stream, c
 	if (plan.reads_linear && c->vol == nullptr)
 		return fail(c, VR_ERR_NOT_READY, (std::string("this ") + what + " frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                  "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again").c_str());
-	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u };
+	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u, 0u };
 	uint64_t frame_seq = 0;
 	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch(a, brick_copy, a.p.esl ? c->mip_bounds : nullptr); });
 }
@@ -1136,6 +1163,61 @@ int launch_iso_frame(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev
 	return launch_full_march_frame(c, p, stream, "isosurface", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
 		return launch_iso(a, c->vol, brick_copy, c->bpv, c->tf, bounds, iso->level, iso->refine, dev_rgba, dev_depth, stream);
 	});
+}
+
+// The light grid of a shadow (include/vr_hip.h vr_hip_set_shadow): S^3 bytes built by shadow_build_kernel from the copy a TRILINEAR MIP frame
+// along z reads — the quad bricks of plane (x,y), the oct bricks for 2-byte voxels, the linear array under VR_LAYOUT_LINEAR — on the context's
+// stream, synchronous like a brick copy's first use.  Waits for the context's frames first: one of them may still read the bytes it rewrites.
+int build_shadow(vr_ctx *c) {
+	if (c->shadow_ready) return VR_OK;
+	const vr_shadow &sh = c->shadow;
+	const uint64_t bytes = (uint64_t) sh.dims * sh.dims * sh.dims;
+	VR_TRY(c, drain(c));
+	if (c->shadow_q_bytes < bytes) {
+		if (c->shadow_q) { (void) hipFree(c->shadow_q); c->shadow_q = nullptr; c->shadow_q_bytes = 0; }
+		VR_TRY(c, hipMalloc((void **) &c->shadow_q, bytes));
+		c->shadow_q_bytes = bytes;
+	}
+	vr_params p;
+	memset(&p, 0, sizeof p);
+	p.sampling = VR_SAMPLE_TRILINEAR;            // (the selector's row; the builder takes Q8 as a flag)
+	RayKernelArgs a;
+	volume_args(c, &p, a);
+	a.force_wide = c->force_wide;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED;
+	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
+	a.brick_plane = kPlaneXY;
+	if (bricked && c->bpv == 2 && copy_possible(c, kCopyOct) && c->brick_plane_force < 0 && c->force_wide != 1) a.layout = kLayoutOct;
+	const void *brick_copy = nullptr;
+	if (a.layout != kLayoutLinear) {
+		brick_copy = copy_for(c, copy_kind_of(a, p.sampling));
+		if (brick_copy == nullptr) { a.layout = kLayoutBricked; brick_copy = copy_for(c, kCopyQuadXY); }
+		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p.sampling, false, a.layout);
+	}
+	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
+	if (plan.reads_linear && c->vol == nullptr)
+		return fail(c, VR_ERR_NOT_READY, "the light grid of the shadow needs the linear array, which was released (vr_hip_release_linear_copy), and no resident brick copy serves it");
+	ShadowBuildArgs s;
+	memset(&s, 0, sizeof s);
+	for (int i = 0; i < 3; i++) s.light[i] = sh.light_pos[i];
+	s.dims = sh.dims; s.node_scale = 2.0f / (float) (sh.dims - 1u);
+	s.step = sh.step; s.cutoff = sh.cutoff; s.q8 = sh.sampling == VR_SAMPLE_TRILINEAR_Q8 ? 1u : 0u;
+	s.max_steps = (uint32_t) std::ceil(2.0 * std::sqrt(3.0) / (double) sh.step) + 2u;
+	s.clip_on = c->clip_on ? 1u : 0u;
+#ifdef VR_BOUNDS_CHECK
+	VR_TRY(c, bounds_check_arm(c, a, &p, plan, brick_copy, 0u));
+#endif
+	VR_TRY(c, hipEventRecord(c->aux_start, c->stream));
+	VR_TRY(c, launch_shadow_build(a, s, c->vol, brick_copy, c->bpv, c->tf, c->shadow_q, c->stream));
+	VR_TRY(c, hipEventRecord(c->aux_stop, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+#ifdef VR_BOUNDS_CHECK
+	{ const int bc = bounds_check_verdict(c, c->stream, a.layout); if (bc) return bc; }
+#endif
+	(void) hipEventElapsedTime(&c->shadow_build_ms, c->aux_start, c->aux_stop);
+	c->shadow_builds++;
+	c->shadow_ready = true;
+	return VR_OK;
 }
 
 // what the two isosurface entry points check beyond render_preamble
@@ -1237,6 +1319,7 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->minmax) (void) hipFree(c->minmax);
 	if (c->mip_bounds) (void) hipFree(c->mip_bounds);
 	if (c->iso_depth) (void) hipFree(c->iso_depth);
+	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
 	if (c->stream) (void) hipStreamDestroy(c->stream);
@@ -1277,6 +1360,7 @@ int vr_hip_set_transfer_fn(vr_ctx *c, const float *tf, const uint32_t *esl) {
 		zero++;
 	c->tf_zero_below = (float) zero;
 	c->tf_set = true;
+	c->shadow_ready = false;                     // the light grid holds transmittances under the old transfer function
 	forget_recorded_orders(c);                   // they describe ray lengths under the old transfer function (placement only; nothing is in flight here: drained above)
 	return VR_OK;
 }
@@ -1381,8 +1465,58 @@ int vr_hip_set_clip(vr_ctx *c, const vr_clip *clip) {
 	// give the same image — but it describes other ray lengths and must not be mistaken for this clip's.  (Buffers of frames in flight stay.)
 	c->clip_on = on;
 	if (on) c->clip = *clip;
+	c->shadow_ready = false;                     // light rays are clipped too
 	forget_tile_mappings(c);
 	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_set_shadow(vr_ctx *c, const vr_shadow *sh) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (sh != nullptr) {
+		if (!finite3(sh->light_pos) || !std::isfinite(sh->step) || !std::isfinite(sh->strength) || !std::isfinite(sh->cutoff))
+			return fail(c, VR_ERR_INVALID, "shadow members must be finite");
+		if (sh->dims < 2u || sh->dims > 256u) return fail(c, VR_ERR_INVALID, "shadow dims must be in 2..256");
+		if (!(sh->step >= 1.0f / 4096.0f)) return fail(c, VR_ERR_INVALID, "shadow step must be >= 1/4096");
+		if (!(sh->strength >= 0.0f && sh->strength <= 1.0f)) return fail(c, VR_ERR_INVALID, "shadow strength must be in 0..1");
+		if (!(sh->cutoff >= 0.0f && sh->cutoff < 1.0f)) return fail(c, VR_ERR_INVALID, "shadow cutoff must be in [0, 1)");
+		if (sh->sampling != VR_SAMPLE_TRILINEAR && sh->sampling != VR_SAMPLE_TRILINEAR_Q8)
+			return fail(c, VR_ERR_INVALID, "shadow sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	}
+	const bool on = sh != nullptr;
+	if (on == c->shadow_on && (!on || memcmp(&c->shadow, sh, sizeof *sh) == 0)) return VR_OK;      // the same shadow: the light grid stays
+	if (on && c->shadow_on) {                    // the strength alone: the grid does not depend on it, and the frames read the same copies
+		vr_shadow same_grid = *sh;
+		same_grid.strength = c->shadow.strength;
+		if (memcmp(&c->shadow, &same_grid, sizeof same_grid) == 0) { c->shadow.strength = sh->strength; return VR_OK; }
+	}
+	c->shadow_on = on;
+	if (on) c->shadow = *sh;
+	c->shadow_ready = false;
+	forget_tile_mappings(c);                     // as for a clip: the caches are keyed by vr_params alone, and a shadowed frame reads other copies
+	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_download_shadow(vr_ctx *c, uint8_t *host_out, uint64_t capacity, uint32_t *dims_out) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (!c->shadow_on) return fail(c, VR_ERR_NOT_READY, "no shadow is set (vr_hip_set_shadow)");
+	if (const int rc = ready(c)) return rc;
+	const uint64_t bytes = (uint64_t) c->shadow.dims * c->shadow.dims * c->shadow.dims;
+	if (dims_out) *dims_out = c->shadow.dims;
+	if (host_out == nullptr && capacity == 0) return VR_OK;      // size query: only *dims_out
+	if (host_out == nullptr || capacity < bytes) return fail(c, VR_ERR_INVALID, "shadow buffer is NULL or smaller than dims^3 bytes");
+	VR_TRY(c, hipSetDevice(c->device));
+	if (const int rc = build_shadow(c)) return rc;
+	VR_TRY(c, hipMemcpyAsync(host_out, c->shadow_q, bytes, hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	return VR_OK;
+}
+
+int vr_hip_shadow_builds(vr_ctx *c, uint64_t *builds_out, float *last_build_ms_out) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (builds_out) *builds_out = c->shadow_builds;
+	if (last_build_ms_out) *last_build_ms_out = c->shadow_build_ms;
 	return VR_OK;
 }
 

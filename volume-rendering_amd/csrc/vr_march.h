@@ -403,6 +403,12 @@ __device__ __forceinline__ float select_lanes(uint64_t mask, float x) {
 	asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(mask));
 	return r;
 }
+// x where the wave mask has the lane's bit set, `other` elsewhere
+__device__ __forceinline__ float select_lanes_else(uint64_t mask, float x, float other) {
+	float r;
+	asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(other), "v"(x), "s"(mask));
+	return r;
+}
 enum : int { kFcmpOGT = 2, kFcmpOGE = 3, kFcmpOLE = 5, kFcmpUNE = 14, kIcmpNE = 33, kIcmpSGT = 38 };   // LLVM fcmp / icmp predicate codes for __builtin_amdgcn_fcmpf / sicmp
 
 // Exact saturation shortcut, decided per wave.  A sample is composited with weight t = 1 - acc.w (CPURenderer.cpp:34); once a
@@ -683,6 +689,41 @@ __device__ __forceinline__ bool clip_segment(f3 origin, f3 dir, float &kx, float
 	else if (dn < 0) ky = flmin(ky, -on / dn);
 	else kept = on >= 0;                            // the ray runs inside the plane's direction (no plane: 0 >= 0)
 	return kept && (kx < ky) && (ky > 0);
+}
+
+// -- the factor of a shadowed composite frame (include/vr_hip.h vr_hip_set_shadow) for the sample at model-space point
+//    pt: f = fma(strength / 255, Tq, 1 - strength), Tq the trilinear interpolation of the light grid's bytes q at pt — node coordinate
+//    fmed3(fma(pt, hs, hs), 0, S - 1), cell min((uint32_t) v, S - 2), weight v - cell, lerps along x, then y, then z, full fp32 weights in
+//    both sampling modes.  The cell index is at most S - 2 whatever pt is (a NaN converts to 0), so the eight byte loads stay inside the S^3
+//    bytes for every lane, live or not.  The constants come through the laundered kernel-argument pointer, as in clip_segment: only the few
+//    samples that are dense get here, and nothing of the grid occupies a scalar register across the march.
+__device__ __forceinline__ float shadow_factor(f3 pt) {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	const float hs = a->shadow_hs, top = a->shadow_max;
+	const uint32_t last = a->shadow_last, row = a->shadow_row, slab = a->shadow_slab;
+	float vx = __builtin_amdgcn_fmed3f(VR_FMA(pt.x, hs, hs), 0.0f, top);
+	float vy = __builtin_amdgcn_fmed3f(VR_FMA(pt.y, hs, hs), 0.0f, top);
+	float vz = __builtin_amdgcn_fmed3f(VR_FMA(pt.z, hs, hs), 0.0f, top);
+	auto cell = [&](float v) { const uint32_t i = (uint32_t) v; return i < last ? i : last; };
+	// Register diet (the dense block sits inside the march's prefetch pipeline, whose fetch slots stay live): the three node coordinates and
+	// one offset cross the loads, the cells and weights are formed again from the coordinates behind them, one slab's four bytes at a time
+	uint32_t off = (cell(vz) * slab + cell(vy) * row) + cell(vx);
+	asm volatile("" : "+v"(off), "+v"(vx), "+v"(vy), "+v"(vz));
+	const uint8_t *q = (const uint8_t *) (uintptr_t) a->shadow_q + off;
+	uint32_t b0 = q[0], b1 = q[1], b2 = q[row], b3 = q[row + 1u];
+	asm volatile("" : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
+	const float wx = vx - (float) cell(vx);
+	float c00 = lerp((float) b0, (float) b1, wx), c10 = lerp((float) b2, (float) b3, wx);
+	asm volatile("" : "+v"(c00), "+v"(c10));
+	const uint8_t *q1 = q + slab;
+	uint32_t b4 = q1[0], b5 = q1[1], b6 = q1[row], b7 = q1[row + 1u];
+	asm volatile("" : "+v"(b4), "+v"(b5), "+v"(b6), "+v"(b7));
+	const float c01 = lerp((float) b4, (float) b5, wx), c11 = lerp((float) b6, (float) b7, wx);
+	const float wy = vy - (float) cell(vy), wz = vz - (float) cell(vz);
+	const float tq = lerp(lerp(c00, c10, wy), lerp(c01, c11, wy), wz);
+	return VR_FMA(a->shadow_scale, tq, a->shadow_base);
 }
 
 // -- the address tables of the quad / voxel / oct bricks into LDS; no barrier.  Entry j of a table belongs to cell

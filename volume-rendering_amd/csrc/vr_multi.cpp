@@ -349,6 +349,12 @@ int vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf, const uint32_t *e
 	return VR_OK;
 }
 
+int vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow) {
+	if (m == nullptr) return VR_ERR_INVALID;
+	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_shadow(m->ctx[r], shadow)); if (rc) return rc; }
+	return VR_OK;
+}
+
 int vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip) {
 	if (m == nullptr) return VR_ERR_INVALID;
 	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_clip(m->ctx[r], clip)); if (rc) return rc; }

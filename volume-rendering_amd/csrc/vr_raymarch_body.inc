@@ -1,5 +1,6 @@
 // vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
-// `constexpr bool CLIP` set): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
+// `constexpr bool CLIP` and `SHADOW` set) and of raymarch_shadowed (vr_shadow.hip): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the
+// kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
 	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live
@@ -322,7 +323,9 @@
 			// (the clipped linear-array kernels as well: a slot of theirs holds four words whatever the voxel size — their unclipped twins for 1-byte
 			// voxels, not on any default path, take 72-74 VGPRs)
 			constexpr bool kFourWordSlots = BPV == 2 || (CLIP && LAYOUT == kLayoutLinear);
-			constexpr int kDepth = is_run_layout(LAYOUT) ? kRunDepth : (!kFourWordSlots ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth)), kSlots = kDepth + 1;
+			// (a shadowed frame: one sample less ahead — with the factor fetch of its dense block the full depth takes 66-69 VGPRs, 7 waves per SIMD)
+			constexpr int kFullDepth = is_run_layout(LAYOUT) ? kRunDepth : (!kFourWordSlots ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth));
+			constexpr int kDepth = SHADOW && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
 			TriFetch<BPV, LAYOUT> f[kSlots]; float ks[kSlots];
 			ks[0] = kx;
 			f[kSlots - 1].w0 = f[kSlots - 1].w1 = f[kSlots - 1].w2 = f[kSlots - 1].w3 = 0; f[kSlots - 1].q = 0; f[kSlots - 1].q2 = 0; f[kSlots - 1].o = (u32x4) (0u);
@@ -412,6 +415,13 @@
 						const float raw_l = tri_resolve<BPV, LAYOUT, kQ8>(lf, a, lx, ly, lz, along_y);
 						const float diffuse = select_lanes(shaded, (raw_l - raw) * a.kd_scaled);       // 0 for lanes that are not shaded
 						c.x += diffuse; c.y += diffuse; c.z += diffuse;
+					}
+					if constexpr (SHADOW) {                                                            // vr_hip_set_shadow: dense samples are scaled by the light grid, lit or not
+						const uint64_t dense = __builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live;
+						if (dense != 0ull) {
+							const float f = select_lanes_else(dense, shadow_factor(march_point<SAMPLING>(origin, dir, kx)), 1.0f);      // x * 1 == x: other lanes unchanged
+							c.x *= f; c.y *= f; c.z *= f;
+						}
 					}
 					const float t = select_lanes(live, 1 - acc.w);                                     // finished lanes: weight 0
 					acc.x = VR_FMA(c.x, t, acc.x); acc.y = VR_FMA(c.y, t, acc.y);

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip
+from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_shadow
 
 
 class HipRenderer:
@@ -21,6 +21,7 @@ class HipRenderer:
         self.device = int(device)
         self.dims = None
         self.bytes_per_voxel = None
+        self._shadow = None              # set_shadow(step=None): the arguments, until a frame's ray_step resolves the step
 
     # -- lifetime
     def close(self):
@@ -100,9 +101,54 @@ class HipRenderer:
         """Clipping off (the default)."""
         self._check(self._L.vr_hip_set_clip(self._ctx, None), "clear_clip")
 
+    def set_shadow(self, light_pos, dims=128, step=None, strength=1.0, cutoff=1.0 / 256.0, sampling=1):
+        """vr_hip_set_shadow: every later COMPOSITE frame darkens its dense samples by what lies between them and the light at `light_pos`
+        (model space: the cube is [-1,1]^3).  dims = nodes per edge of the light grid (2..256); step = the march step towards the light, None =
+        the ray_step of the NEXT composite frame (resolved once, at that frame: shadows as dense as it sees them; later frames with another
+        ray_step keep that step — call set_shadow again to follow them; until then download_shadow needs its ray_step argument); strength 0..1 (0 = unshadowed bytes);
+        cutoff = the transmittance below which a light ray is black; sampling = how the builder samples the volume.  The frames must be
+        TRILINEAR / TRILINEAR_Q8; MIP and isosurface frames ignore the shadow.  The light of the frames' own shading is params.view.light_pos:
+        set it to the same point for a consistent picture."""
+        pending = None
+        if step is None:
+            pending = dict(light_pos=tuple(float(v) for v in light_pos), dims=dims, strength=strength, cutoff=cutoff, sampling=sampling)
+            step = 0.01                  # validated now with a placeholder, set again with the frame's ray_step (an identical struct rebuilds nothing)
+        self._check(self._L.vr_hip_set_shadow(self._ctx, C.byref(make_shadow(light_pos, dims, step, strength, cutoff, sampling))), "set_shadow")
+        self._shadow = pending           # (a refused shadow leaves the one before in place)
+
+    def clear_shadow(self):
+        """Shadows off (the default)."""
+        self._shadow = None
+        self._check(self._L.vr_hip_set_shadow(self._ctx, None), "clear_shadow")
+
+    def _resolve_shadow(self, ray_step):
+        """a set_shadow(step=None) takes this step, once"""
+        if self._shadow is not None:
+            self._check(self._L.vr_hip_set_shadow(self._ctx, C.byref(make_shadow(step=float(ray_step), **self._shadow))), "set_shadow")
+            self._shadow = None
+
+    def download_shadow(self, ray_step=None):
+        """vr_hip_download_shadow: the light grid as a (S, S, S) uint8 array indexed [z, y, x], 255 = fully lit; builds it if stale.  After a
+        set_shadow(step=None) that no frame has resolved yet, ray_step is required and resolves it the way a frame with that ray_step would."""
+        if self._shadow is not None:
+            if ray_step is None:
+                raise VrError(1, "download_shadow: set_shadow(step=None) has no step yet — render a frame first or pass ray_step")
+            self._resolve_shadow(ray_step)
+        dims = C.c_uint32(0)
+        self._check(self._L.vr_hip_download_shadow(self._ctx, None, 0, C.byref(dims)), "download_shadow")       # size query
+        out = np.empty((dims.value,) * 3, dtype=np.uint8)
+        self._check(self._L.vr_hip_download_shadow(self._ctx, out.ctypes.data, out.nbytes, C.byref(dims)), "download_shadow")
+        return out
+
+    def shadow_builds(self):
+        """(number of light-grid builds of this context, hipEvent ms of the last one)"""
+        n, ms = C.c_uint64(0), C.c_float(0)
+        self._check(self._L.vr_hip_shadow_builds(self._ctx, C.byref(n), C.byref(ms)), "shadow_builds")
+        return int(n.value), float(ms.value)
+
     def last_launch(self):
         """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
-        column_voxels, column_shade_pairs)."""
+        column_voxels, column_shade_pairs, shadowed)."""
         info = VrLaunchInfo()
         self._check(self._L.vr_hip_last_launch(self._ctx, C.byref(info)), "last_launch")
         return {n: int(getattr(info, n)) for n, _ in VrLaunchInfo._fields_}
@@ -132,11 +178,13 @@ class HipRenderer:
     def render_volume(self, params):
         """Host-buffer flavour (reference renderer ids 0-2): returns an (out_rows, out_width, 4) uint8 array."""
         out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        self._resolve_shadow(params.ray_step)
         self._check(self._L.vr_hip_render(self._ctx, C.byref(params), out.ctypes.data), "render_volume")
         return out
 
     def render_volume_device(self, params, dev_ptr, stream=None):
         """Device-buffer flavour (ids 3-4): asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
+        self._resolve_shadow(params.ray_step)
         self._check(self._L.vr_hip_render_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
                                                  C.c_void_p(stream) if stream else None), "render_volume_device")
 
@@ -242,6 +290,7 @@ class MultiRenderer:
                 self._m = C.c_void_p()
             raise VrError(rc, msg)
         self.devices = list(devices)
+        self._shadow = None
 
     def close(self):
         if self._m:
@@ -277,6 +326,25 @@ class MultiRenderer:
     def clear_clip(self):
         self._check(self._L.vr_hip_multi_set_clip(self._m, None), "clear_clip")
 
+    def set_shadow(self, light_pos, dims=128, step=None, strength=1.0, cutoff=1.0 / 256.0, sampling=1):
+        """vr_hip_multi_set_shadow: HipRenderer.set_shadow on every device's context (every device builds its own light grid); step=None
+        is resolved once, by the next frame's ray_step."""
+        pending = None
+        if step is None:
+            pending = dict(light_pos=tuple(float(v) for v in light_pos), dims=dims, strength=strength, cutoff=cutoff, sampling=sampling)
+            step = 0.01
+        self._check(self._L.vr_hip_multi_set_shadow(self._m, C.byref(make_shadow(light_pos, dims, step, strength, cutoff, sampling))), "set_shadow")
+        self._shadow = pending
+
+    def clear_shadow(self):
+        self._shadow = None
+        self._check(self._L.vr_hip_multi_set_shadow(self._m, None), "clear_shadow")
+
+    def _resolve_shadow(self, ray_step):
+        if self._shadow is not None:
+            self._check(self._L.vr_hip_multi_set_shadow(self._m, C.byref(make_shadow(step=float(ray_step), **self._shadow))), "set_shadow")
+            self._shadow = None
+
     def set_volume(self, voxels):
         v = np.ascontiguousarray(voxels)
         z, y, x = v.shape
@@ -287,15 +355,18 @@ class MultiRenderer:
 
     def render_volume(self, params):
         out = np.empty((params.view.height, params.view.width, 4), dtype=np.uint8)
+        self._resolve_shadow(params.ray_step)
         self._check(self._L.vr_hip_multi_render(self._m, C.byref(params), out.ctypes.data), "render_volume")
         return out
 
     def render_volume_device(self, params, dev_ptr):
+        self._resolve_shadow(params.ray_step)
         self._check(self._L.vr_hip_multi_render_device(self._m, C.byref(params), C.c_void_p(dev_ptr)), "render_volume_device")
 
     def render_volume_device_async(self, params, dev_ptr, consumer_stream=None):
         """Queues a frame (up to THREE in flight: kFrames in vr_multi.cpp; frames in flight must not share `dev_ptr`); `consumer_stream`
         (raw hipStream_t on devices[0]) waits for the assembled frame."""
+        self._resolve_shadow(params.ray_step)
         self._check(self._L.vr_hip_multi_render_device_async(self._m, C.byref(params), C.c_void_p(dev_ptr),
                                                              C.c_void_p(consumer_stream) if consumer_stream else None), "render_volume_device_async")
 
