@@ -366,6 +366,47 @@ int vr_hip_set_shadow(vr_ctx *ctx, const vr_shadow *shadow);      /* NULL = off 
 int vr_hip_download_shadow(vr_ctx *ctx, uint8_t *host_out, uint64_t capacity, uint32_t *dims_out); /* S^3 bytes, x fastest; builds if stale */
 int vr_hip_shadow_builds(vr_ctx *ctx, uint64_t *builds_out, float *last_build_ms_out);              /* either may be NULL */
 
+/* ---- gradient lighting for composite frames: Blinn-Phong from the gradient of the interpolated field.  No reference counterpart. ----
+ * The reference's lighting is a cue — (raw_l - raw) * kd added to all three channels: it has no normal and no highlight, and cannot tell
+ * "facing the light" from "steeper".  A lighting shades every dense sample from the central-difference gradient of the field, the
+ * isosurface's (step 6 there), with an ambient, a two-sided diffuse and a white specular term.  It is context state, like the clip and the
+ * shadow: NULL switches it off, which is the default; without a lighting every frame is what it was, byte for byte.  vr_params and every
+ * other struct keep their size and layout.
+ * Lit composite frame.  vr_hip_render / vr_hip_render_device (and vr_hip_multi_* through the per-device contexts) composite as before with one
+ * replacement: the block that adds the reference's cue is not run and params.light_kd is IGNORED.  For a sample whose looked-up colour has
+ * c.w > 0.05f, with (xb, yb, zb) = fma(k, A, B) the sample's texel coordinates and pt = march_point(origin, dir, k) the model-space point
+ * the march already forms for it:
+ *  1. Gradient.  gx = (v(xb + 1, yb, zb) - v(xb - 1, yb, zb)) * half.x, likewise gy and gz; v is the TRILINEAR (or _Q8, by params.sampling)
+ *     interpolated RAW value with clamp addressing; gg = fma(gz, gz, fma(gy, gy, gx * gx)).  If !(gg > 0) the sample is left as looked up: a
+ *     plateau has no surface to light.
+ *  2. Light.  ig = rsqrt_nr(gg); dl = view.light_pos - pt; ll = fma(dl.z, dl.z, fma(dl.y, dl.y, dl.x * dl.x)).  If !(ll > 0) then
+ *     sd = sp = 0.  Otherwise il = rsqrt_nr(ll), dot = fma(gz, dl.z, fma(gy, dl.y, gx * dl.x)), sd = fminf(fabsf((dot * ig) * il), 1.0f):
+ *     two-sided, as the isosurface is.
+ *  3. Highlight.  iv = rsqrt_nr(fma(dir.z, dir.z, fma(dir.y, dir.y, dir.x * dir.x))) from the pixel's own unnormalised dir;
+ *     h = fma(-dir, iv, dl * il) per axis (the product rounded on its own); hh = fma(h.z, h.z, fma(h.y, h.y, h.x * h.x)).  If !(hh > 0) then
+ *     sp = 0.  Otherwise sp = fminf(fabsf((fma(gz, h.z, fma(gy, h.y, gx * h.x)) * ig) * rsqrt_nr(hh)), 1.0f), then sp = sp * sp repeated
+ *     shininess_log2 times.  There is no powf: CPU and GPU do not share one bit for bit (the shadow builder's reasoning).
+ *  4. Colour.  m = fma(diffuse, sd, ambient); spec = (specular * sp) * c.w — the highlight is white and premultiplied;
+ *     c.x = fma(c.x, m, spec), likewise y and z.  c.w is untouched: leaping, the transparent-sample shortcuts and early termination see the
+ *     same alphas, and the alpha bytes of a lit frame equal the unlit frame's.
+ *  5. Shadow.  The factor of vr_hip_set_shadow, where one is set, scales c.xyz after step 4, as its contract says: the two compose.
+ * Consequences.  { 1, 0, 0, n } gives the bytes of the same frame with light_kd = 0: fma(c, 1, (0 * sp) * c.w) = c.  Samples with
+ * c.w <= 0.05f are never lit, as in the reference.
+ * Other behaviour.  VR_SAMPLE_NEAREST composite frames under a lighting return VR_ERR_INVALID (the isosurface's and the shadow's precedent).
+ * MIP and isosurface frames IGNORE the lighting.  A lit frame reads what a clipped frame reads — the linear array, quad bricks with the
+ * per-view plane, or oct bricks —, never a run copy or a column window: vr_launch_info::layout is then 0, 1 or 5.  Setting a lighting that
+ * differs from the current one forgets the cached tile mappings and recorded orders, as vr_hip_set_shadow does.
+ * Errors.  VR_ERR_INVALID for a non-finite member, a coefficient outside [0, 1], shininess_log2 > 10.  vr_hip_lighting_frames counts the
+ * composite frames this context launched on the gradient-lit kernels (testing aid). */
+typedef struct vr_lighting {
+	float    ambient;         /* ka, 0..1 */
+	float    diffuse;         /* kd, 0..1 */
+	float    specular;        /* ks, 0..1 */
+	uint32_t shininess_log2;  /* n, 0..10: the specular term is raised to the power 2^n by n squarings */
+} vr_lighting;                /* 16 bytes */
+int vr_hip_set_lighting(vr_ctx *ctx, const vr_lighting *lighting);      /* NULL = off (the default): the reference's cue */
+int vr_hip_lighting_frames(vr_ctx *ctx, uint64_t *frames_out);          /* testing aid: composite frames launched on the gradient-lit kernels */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {
@@ -434,6 +475,7 @@ int  vr_hip_multi_set_window(vr_multi *m, uint32_t width, uint32_t height);
 int  vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf_premult_rgba, const uint32_t *esl_bits);
 int  vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip);      /* vr_hip_set_clip on every device's context */
 int  vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow); /* vr_hip_set_shadow on every device's context */
+int  vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting); /* vr_hip_set_lighting on every device's context */
 int  vr_hip_multi_set_volume(vr_multi *m, const void *host_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);
 int  vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bytes_per_voxel);
 int  vr_hip_multi_render(vr_multi *m, const vr_params *params, uint8_t *host_rgba);           /* whole frame -> host buffer */

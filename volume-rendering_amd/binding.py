@@ -83,6 +83,17 @@ def make_shadow(light_pos, dims=128, step=0.01, strength=1.0, cutoff=1.0 / 256.0
     return sh
 
 
+class VrLighting(C.Structure):
+    """vr_lighting: ambient, diffuse and specular coefficients (0..1) and shininess_log2 (0..10: the highlight is raised to the power 2^n)"""
+    _fields_ = [("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("shininess_log2", C.c_uint32)]
+
+
+def make_lighting(ambient=0.25, diffuse=0.65, specular=0.4, shininess_log2=4):
+    if int(shininess_log2) < 0:
+        raise ValueError("shininess_log2 must be in 0..10")
+    return VrLighting(float(ambient), float(diffuse), float(specular), int(shininess_log2))
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -145,6 +156,8 @@ def lib():
         "vr_hip_set_shadow": (C.c_int, [vp, P(VrShadow)]),
         "vr_hip_download_shadow": (C.c_int, [vp, vp, u64, P(u32)]),
         "vr_hip_shadow_builds": (C.c_int, [vp, P(u64), f32p]),
+        "vr_hip_set_lighting": (C.c_int, [vp, P(VrLighting)]),
+        "vr_hip_lighting_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_last_launch": (C.c_int, [vp, P(VrLaunchInfo)]),
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
         "vr_hip_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -174,6 +187,7 @@ def lib():
         "vr_hip_multi_set_transfer_fn": (C.c_int, [vp, vp, vp]),
         "vr_hip_multi_set_clip": (C.c_int, [vp, P(VrClip)]),
         "vr_hip_multi_set_shadow": (C.c_int, [vp, P(VrShadow)]),
+        "vr_hip_multi_set_lighting": (C.c_int, [vp, P(VrLighting)]),
         "vr_hip_multi_set_volume": (C.c_int, [vp, vp, u32, u32, u32, u32]),
         "vr_hip_multi_generate_volume": (C.c_int, [vp, u32, u32, u32, u32]),
         "vr_hip_multi_render": (C.c_int, [vp, P(VrParams), vp]),

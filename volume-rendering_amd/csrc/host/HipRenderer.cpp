@@ -108,6 +108,14 @@ int HipRenderer::set_shadow(const vr_shadow *shadow) {
 	return rc == 0 ? 0 : 1;
 }
 
+int HipRenderer::set_lighting(const vr_lighting *lighting) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	const int rc = multi_ ? vr_hip_multi_set_lighting(multi_, lighting) : vr_hip_set_lighting(ctx_, lighting);
+	return rc == 0 ? 0 : 1;
+}
+
 int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 	if (!ok() || buffer == nullptr)
 		return 1;

@@ -100,6 +100,11 @@ class HipRenderer : public Renderer {
 		// Light-source shadows of every later COMPOSITE frame of this renderer (vr_hip_set_shadow / vr_hip_multi_set_shadow: a light grid
 		// marched towards shadow->light_pos, one more filtered fetch per dense sample); set_mip and set_iso frames ignore it.  NULL = off.
 		int set_shadow(const vr_shadow *shadow);
+		// Gradient lighting of every later COMPOSITE frame of this renderer (vr_hip_set_lighting / vr_hip_multi_set_lighting: Blinn-Phong from
+		// the gradient of the interpolated field in place of the reference's cue; light_kd is then ignored); set_mip and set_iso frames
+		// ignore it.  clear_lighting() = set_lighting(NULL) = off.  0 = ok, 1 = failure (a coefficient outside 0..1, shininess_log2 > 10).
+		int set_lighting(const vr_lighting *lighting);
+		int clear_lighting() { return set_lighting(nullptr); }
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:

@@ -105,6 +105,13 @@ struct RayKernelArgs {
 	float    shadow_base;              // 1.0f - strength
 	uint32_t shadow_row, shadow_slab;  // S, S * S: byte strides of the plain array along y and z
 	uint64_t shadow_q;                 // the S^3 bytes q, x fastest
+	// vr_hip_set_lighting (include/vr_hip.h vr_lighting): the Blinn-Phong constants of a gradient-lit composite frame.
+	// Read by the composite_lit kernels only (vr_light.hip), inside their dense block through the laundered kernel-argument pointer
+	// (vr_march.h light_sample), so nothing of them is live across the march; light_on is for the host.  Such a frame always runs clip_segment
+	// (the identity clip above when none is set) and applies shadow_factor when shadow_on is set: the two compose.
+	uint32_t light_on;
+	float    light_ka, light_kd, light_ks;
+	uint32_t light_n;                  // shininess_log2: the specular term is squared this many times
 #ifdef VR_BOUNDS_CHECK
 	// `make EXTRA=-DVR_BOUNDS_CHECK` (debug build, not the product): every gather address of the march is held against the array it must
 	// lie in, every address-table index against its padded table, the tile-cost slot against its buffer; the first violation is recorded
@@ -377,6 +384,11 @@ hipError_t launch_shadow_build(const RayKernelArgs &a, const ShadowBuildArgs &s,
 // the shadowed composite frame (a.shadow_on): launch_raymarch hands it over, vr_shadow.hip launches raymarch_shadowed
 hipError_t launch_raymarch_shadowed(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                                     const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
+
+// the gradient-lit composite frame (a.light_on; include/vr_hip.h vr_hip_set_lighting): launch_raymarch hands it over,
+// vr_light.hip launches composite_lit
+hipError_t launch_composite_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);

@@ -108,6 +108,9 @@ struct vr_ctx {
 	bool shadow_on = false; vr_shadow shadow = {};
 	uint8_t *shadow_q = nullptr; uint64_t shadow_q_bytes = 0; bool shadow_ready = false;
 	uint64_t shadow_builds = 0; float shadow_build_ms = 0;
+	// gradient lighting (vr_hip_set_lighting): composite frames run the composite_lit kernels; lit_frames counts them (vr_hip_lighting_frames)
+	bool lighting_on = false; vr_lighting lighting = {};
+	uint64_t lit_frames = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -387,7 +390,7 @@ void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 		for (int i = 0; i < 4; i++) a.clip_plane[i] = c->clip.plane[i];
 	} else {
 		// the identity clip, which changes no bit of a segment by contract: what the kernels that always run clip_segment read when no clip
-		// is set (raymarch_shadowed); clip_on stays 0 and every other kernel ignores these words
+		// is set (raymarch_shadowed, composite_lit); clip_on stays 0 and every other kernel ignores these words
 		for (int i = 0; i < 3; i++) { a.clip_min[i] = -1.0f; a.clip_max[i] = 1.0f; }
 	}
 }
@@ -561,8 +564,17 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_shadow(ctx, NULL) switches the shadow off)");
 		if (const int rc = build_shadow(c)) return rc;
 	}
+	// A gradient-lit frame (vr_hip_set_lighting) reads what a clipped frame reads too, and its kernels take the shadow as an argument
+	const bool lighting = c->lighting_on;
+	if (lighting && p->sampling == VR_SAMPLE_NEAREST)
+		return fail(c, VR_ERR_INVALID, "a lighting is set: the gradient is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_lighting(ctx, NULL) switches the lighting off)");
 	RayKernelArgs a;
 	volume_args(c, p, a);
+	if (lighting) {
+		a.light_on = 1u; a.light_ka = c->lighting.ambient; a.light_kd = c->lighting.diffuse; a.light_ks = c->lighting.specular;
+		a.light_n = c->lighting.shininess_log2;
+	}
 	if (shadow) {
 		const uint32_t S = c->shadow.dims;
 		a.shadow_on = 1u; a.shadow_last = S - 2u; a.shadow_hs = 0.5f * (float) (S - 1u); a.shadow_max = (float) (S - 1u);
@@ -609,7 +621,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	}
 	a.force_wide = c->force_wide;
 	// (a shadowed frame reads what a clipped frame reads: its kernels are the clipped ones with one more fetch per dense sample)
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
 	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
@@ -935,6 +947,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	uint64_t frame_seq = 0;
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
 	if (rc) return rc;
+	if (lighting) c->lit_frames++;
 	if (dual_advance) {                          // behind the frame, on its stream
 		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
 		VR_TRY(c, hipEventRecord(hit->order_ready, stream));
@@ -1495,6 +1508,30 @@ int vr_hip_set_shadow(vr_ctx *c, const vr_shadow *sh) {
 	c->shadow_ready = false;
 	forget_tile_mappings(c);                     // as for a clip: the caches are keyed by vr_params alone, and a shadowed frame reads other copies
 	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_set_lighting(vr_ctx *c, const vr_lighting *l) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (l != nullptr) {
+		if (!std::isfinite(l->ambient) || !std::isfinite(l->diffuse) || !std::isfinite(l->specular))
+			return fail(c, VR_ERR_INVALID, "lighting members must be finite");
+		if (!(l->ambient >= 0.0f && l->ambient <= 1.0f) || !(l->diffuse >= 0.0f && l->diffuse <= 1.0f) || !(l->specular >= 0.0f && l->specular <= 1.0f))
+			return fail(c, VR_ERR_INVALID, "lighting ambient, diffuse and specular must be in 0..1");
+		if (l->shininess_log2 > 10u) return fail(c, VR_ERR_INVALID, "lighting shininess_log2 must be in 0..10");
+	}
+	const bool on = l != nullptr;
+	if (on == c->lighting_on && (!on || memcmp(&c->lighting, l, sizeof *l) == 0)) return VR_OK;
+	c->lighting_on = on;
+	if (on) c->lighting = *l;
+	forget_tile_mappings(c);                     // as for a shadow: the caches are keyed by vr_params alone, and a lit frame reads other copies
+	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_lighting_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->lit_frames;
 	return VR_OK;
 }
 

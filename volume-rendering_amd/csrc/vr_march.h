@@ -726,6 +726,81 @@ __device__ __forceinline__ float shadow_factor(f3 pt) {
 	return VR_FMA(a->shadow_scale, tq, a->shadow_base);
 }
 
+// -- the Blinn-Phong term of a gradient-lit composite frame (include/vr_hip.h vr_hip_set_lighting steps 1-4) for the
+//    sample k of the ray (origin, dir) — texel coordinates fma(k, A, B), model-space point march_point(origin, dir, k); `lit` = the wave mask
+//    of the lanes whose looked-up colour is dense.  The gradient is the isosurface's (vr_iso_body.inc): central differences one texel apart of
+//    the interpolated raw value with clamp addressing, so all six fetches are in bounds for every lane, live or not.  Register diet (the dense
+//    block sits inside the march's prefetch pipeline, whose fetch slots stay live): one axis at a time — at most two fetches in flight,
+//    the difference formed, then the next axis.  The constants and the light come through the laundered kernel-argument pointer, as in
+//    clip_segment and shadow_factor: nothing of them occupies a scalar register across the march.  Returns m and spec of step 4 (1 and 0
+//    for the lanes that are not lit): the caller forms c.xyz = fma(c.xyz, m, spec) and leaves c.w alone.
+template <int BPV, int ADDR, int LAYOUT, bool Q8>
+__device__ __forceinline__ void light_sample(const void *vol, const RayKernelArgs &ka, const uint32_t *lut, f3 A, f3 B, f3 origin, f3 dir, float kx,
+                                             uint64_t lit, float cw, float &m_out, float &spec_out) {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	// one axis: the two fetches issued, the texel coordinates formed again from k behind the loads (the same fused multiply-adds, the same
+	// bits) instead of carried across them, the difference scaled; the scheduling barrier keeps the next axis' loads behind this one's use.
+	// Both fetches of an axis are in flight where the registers allow it — 1-byte voxels in quad bricks behind address tables, the default
+	// path —, one after the other elsewhere (four-word fetches, 64-bit addresses: DESIGN.md section 4.8 has the figures of both forms)
+	constexpr bool kPair = BPV == 1 && LAYOUT == kLayoutBricked && ADDR != kAddrWide;
+	auto central = [&](auto axis) -> float {
+		constexpr int X = decltype(axis)::value;
+		float k = kx;
+		asm volatile("" : "+v"(k));
+		float xb = VR_FMA(k, A.x, B.x), yb = VR_FMA(k, A.y, B.y), zb = VR_FMA(k, A.z, B.z);
+		const TriFetch<BPV, LAYOUT> fp = tri_issue<BPV, ADDR, LAYOUT>(vol, ka, lut, X == 0 ? xb + 1.0f : xb, X == 1 ? yb + 1.0f : yb, X == 2 ? zb + 1.0f : zb, true);
+		TriFetch<BPV, LAYOUT> fm;
+		if constexpr (kPair) fm = tri_issue<BPV, ADDR, LAYOUT>(vol, ka, lut, X == 0 ? xb - 1.0f : xb, X == 1 ? yb - 1.0f : yb, X == 2 ? zb - 1.0f : zb, true);
+		__builtin_amdgcn_sched_barrier(0);
+		asm volatile("" : "+v"(k));
+		xb = VR_FMA(k, A.x, B.x); yb = VR_FMA(k, A.y, B.y); zb = VR_FMA(k, A.z, B.z);
+		float vp = tri_resolve<BPV, LAYOUT, Q8>(fp, ka, X == 0 ? xb + 1.0f : xb, X == 1 ? yb + 1.0f : yb, X == 2 ? zb + 1.0f : zb);
+		if constexpr (!kPair) {
+			asm volatile("" : "+v"(vp), "+v"(k));
+			__builtin_amdgcn_sched_barrier(0);
+			xb = VR_FMA(k, A.x, B.x); yb = VR_FMA(k, A.y, B.y); zb = VR_FMA(k, A.z, B.z);
+			fm = tri_issue<BPV, ADDR, LAYOUT>(vol, ka, lut, X == 0 ? xb - 1.0f : xb, X == 1 ? yb - 1.0f : yb, X == 2 ? zb - 1.0f : zb, true);
+			__builtin_amdgcn_sched_barrier(0);
+			asm volatile("" : "+v"(k));
+			xb = VR_FMA(k, A.x, B.x); yb = VR_FMA(k, A.y, B.y); zb = VR_FMA(k, A.z, B.z);
+		}
+		const float vm = tri_resolve<BPV, LAYOUT, Q8>(fm, ka, X == 0 ? xb - 1.0f : xb, X == 1 ? yb - 1.0f : yb, X == 2 ? zb - 1.0f : zb);
+		float g = (vp - vm) * (X == 0 ? a->half_x : (X == 1 ? a->half_y : a->half_z));
+		asm volatile("" : "+v"(g));
+		__builtin_amdgcn_sched_barrier(0);
+		return g;
+	};
+	const float gx = central(std::integral_constant<int, 0>()), gy = central(std::integral_constant<int, 1>()), gz = central(std::integral_constant<int, 2>());
+	const f3 pt = march_point<VR_SAMPLE_TRILINEAR>(origin, dir, kx);
+	const float gg = VR_FMA(gz, gz, VR_FMA(gy, gy, gx * gx));
+	lit &= __builtin_amdgcn_fcmpf(gg, 0.0f, kFcmpOGT);                          // a plateau has no surface to light: the sample stays as looked up
+	m_out = 1.0f; spec_out = 0.0f;
+	if (lit == 0ull) return;
+	const float ig = rsqrt_nr(gg);
+	const f3 dl = mk3(a->p.view.light_pos[0] - pt.x, a->p.view.light_pos[1] - pt.y, a->p.view.light_pos[2] - pt.z);
+	const float ll = VR_FMA(dl.z, dl.z, VR_FMA(dl.y, dl.y, dl.x * dl.x));
+	const float il = rsqrt_nr(ll);
+	const float dot = VR_FMA(gz, dl.z, VR_FMA(gy, dl.y, gx * dl.x));
+	const float sd = ll > 0.0f ? __builtin_fminf(__builtin_fabsf((dot * ig) * il), 1.0f) : 0.0f;      // two-sided, as the isosurface is
+	const float iv = rsqrt_nr(VR_FMA(dir.z, dir.z, VR_FMA(dir.y, dir.y, dir.x * dir.x)));
+	const f3 h = mk3(VR_FMA(-dir.x, iv, dl.x * il), VR_FMA(-dir.y, iv, dl.y * il), VR_FMA(-dir.z, iv, dl.z * il));
+	const float hh = VR_FMA(h.z, h.z, VR_FMA(h.y, h.y, h.x * h.x));
+	float sp = __builtin_fminf(__builtin_fabsf((VR_FMA(gz, h.z, VR_FMA(gy, h.y, gx * h.x)) * ig) * rsqrt_nr(hh)), 1.0f);
+	sp = (ll > 0.0f && hh > 0.0f) ? sp : 0.0f;
+	for (uint32_t n = a->light_n; n != 0u; n--) sp = sp * sp;                   // the power 2^n by n squarings: no powf, CPU and GPU share every bit
+	m_out = select_lanes_else(lit, VR_FMA(a->light_kd, sd, a->light_ka), 1.0f);    // fma(c, 1, 0) == c: other lanes unchanged
+	spec_out = select_lanes(lit, (a->light_ks * sp) * cw);                      // the highlight is white and premultiplied
+}
+// whether the gradient-lit frame is shadowed too (wave-uniform; read where it is used, like the constants above)
+__device__ __forceinline__ bool lit_frame_shadowed() {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	return a->shadow_on != 0u;
+}
+
 // -- the address tables of the quad / voxel / oct bricks into LDS; no barrier.  Entry j of a table belongs to cell
 //    clamp(j - kLutPad, 0, dim - 1): the pad entries repeat the edge cells.
 __device__ __forceinline__ uint32_t lut_cell_of(uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); }

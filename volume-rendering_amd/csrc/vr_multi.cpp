@@ -355,6 +355,12 @@ int vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow) {
 	return VR_OK;
 }
 
+int vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting) {
+	if (m == nullptr) return VR_ERR_INVALID;
+	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_lighting(m->ctx[r], lighting)); if (rc) return rc; }
+	return VR_OK;
+}
+
 int vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip) {
 	if (m == nullptr) return VR_ERR_INVALID;
 	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_clip(m->ctx[r], clip)); if (rc) return rc; }

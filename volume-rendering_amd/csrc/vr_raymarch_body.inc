@@ -1,6 +1,6 @@
 // vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
-// `constexpr bool CLIP` and `SHADOW` set) and of raymarch_shadowed (vr_shadow.hip): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the
-// kernel's parameters.
+// `constexpr bool CLIP`, `SHADOW` and `LIT` set), of raymarch_shadowed (vr_shadow.hip) and of composite_lit (vr_light.hip): a, vol, tf_g,
+// esl_g, out, tile_order, tile_cost are the kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
 	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live
@@ -323,9 +323,10 @@
 			// (the clipped linear-array kernels as well: a slot of theirs holds four words whatever the voxel size — their unclipped twins for 1-byte
 			// voxels, not on any default path, take 72-74 VGPRs)
 			constexpr bool kFourWordSlots = BPV == 2 || (CLIP && LAYOUT == kLayoutLinear);
-			// (a shadowed frame: one sample less ahead — with the factor fetch of its dense block the full depth takes 66-69 VGPRs, 7 waves per SIMD)
+			// (a shadowed frame: one sample less ahead — with the factor fetch of its dense block the full depth takes 66-69 VGPRs, 7 waves per SIMD;
+			// a gradient-lit frame likewise: one or two gradient fetches are in flight inside its dense block)
 			constexpr int kFullDepth = is_run_layout(LAYOUT) ? kRunDepth : (!kFourWordSlots ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth));
-			constexpr int kDepth = SHADOW && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
+			constexpr int kDepth = (SHADOW || LIT) && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
 			TriFetch<BPV, LAYOUT> f[kSlots]; float ks[kSlots];
 			ks[0] = kx;
 			f[kSlots - 1].w0 = f[kSlots - 1].w1 = f[kSlots - 1].w2 = f[kSlots - 1].w3 = 0; f[kSlots - 1].q = 0; f[kSlots - 1].q2 = 0; f[kSlots - 1].o = (u32x4) (0u);
@@ -401,20 +402,39 @@
 						c.x = VR_FMA(w, dc.x, c0.x); c.y = VR_FMA(w, dc.y, c0.y);
 						c.z = VR_FMA(w, dc.z, c0.z); c.w = VR_FMA(w, dc.w, c0.w);
 					}
-					const uint64_t shaded = lit ? (__builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live) : 0ull;   // GPURenderer4.cu:78
-					if (shaded != 0ull) {                                                              // GPURenderer4.cu:41-51 shade_texture
-						const f3 p3 = march_point<SAMPLING>(origin, dir, kx);
-						const f3 d = mk3(light.x - p3.x, light.y - p3.y, light.z - p3.z);
-						const float inv = rsqrt_nr(VR_FMA(d.z, d.z, VR_FMA(d.y, d.y, d.x * d.x)));
-						const float lx = VR_FMA(d.x * inv, a.lh_x, xb), ly = VR_FMA(d.y * inv, a.lh_y, yb), lz = VR_FMA(d.z * inv, a.lh_z, zb);
-						TriFetch<BPV, LAYOUT> lf;
-						if (LAYOUT == kLayoutRunDual) {                     // clamp with the true bounds, then hand the tile's table order over
-							const float cy = __builtin_amdgcn_fmed3f(ly, 0.0f, a.max_y), cz = __builtin_amdgcn_fmed3f(lz, 0.0f, a.max_z);
-							lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, __builtin_amdgcn_fmed3f(lx, 0.0f, a.max_x), along_y ? cz : cy, along_y ? cy : cz, false);
-						} else lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, lx, ly, lz, true);
-						const float raw_l = tri_resolve<BPV, LAYOUT, kQ8>(lf, a, lx, ly, lz, along_y);
-						const float diffuse = select_lanes(shaded, (raw_l - raw) * a.kd_scaled);       // 0 for lanes that are not shaded
-						c.x += diffuse; c.y += diffuse; c.z += diffuse;
+					if constexpr (!LIT) {
+						const uint64_t shaded = lit ? (__builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live) : 0ull;   // GPURenderer4.cu:78
+						if (shaded != 0ull) {                                                              // GPURenderer4.cu:41-51 shade_texture
+							const f3 p3 = march_point<SAMPLING>(origin, dir, kx);
+							const f3 d = mk3(light.x - p3.x, light.y - p3.y, light.z - p3.z);
+							const float inv = rsqrt_nr(VR_FMA(d.z, d.z, VR_FMA(d.y, d.y, d.x * d.x)));
+							const float lx = VR_FMA(d.x * inv, a.lh_x, xb), ly = VR_FMA(d.y * inv, a.lh_y, yb), lz = VR_FMA(d.z * inv, a.lh_z, zb);
+							TriFetch<BPV, LAYOUT> lf;
+							if (LAYOUT == kLayoutRunDual) {                     // clamp with the true bounds, then hand the tile's table order over
+								const float cy = __builtin_amdgcn_fmed3f(ly, 0.0f, a.max_y), cz = __builtin_amdgcn_fmed3f(lz, 0.0f, a.max_z);
+								lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, __builtin_amdgcn_fmed3f(lx, 0.0f, a.max_x), along_y ? cz : cy, along_y ? cy : cz, false);
+							} else lf = tri_issue<BPV, ADDR, LAYOUT>(vol, a, lut, lx, ly, lz, true);
+							const float raw_l = tri_resolve<BPV, LAYOUT, kQ8>(lf, a, lx, ly, lz, along_y);
+							const float diffuse = select_lanes(shaded, (raw_l - raw) * a.kd_scaled);       // 0 for lanes that are not shaded
+							c.x += diffuse; c.y += diffuse; c.z += diffuse;
+						}
+					}
+					if constexpr (LIT) {                                                               // vr_hip_set_lighting: the cue above gives way to Blinn-Phong from the field's gradient
+						const uint64_t dense = __builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live;
+						if (dense != 0ull) {
+							// (register diet: only c.w and tb cross the gradient fetches — the colour is looked up again behind them, the same bits)
+							float m, spec, tb2 = tb;
+							light_sample<BPV, ADDR, LAYOUT, kQ8>(vol, a, lut, A, B, origin, dir, kx, dense, c.w, m, spec);
+							asm volatile("" : "+v"(tb2));
+							const uint32_t i2 = (uint32_t) (int) tb2;
+							const float w2 = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb2));
+							const f4 c0 = lds.tf[i2], dc = lds.dtf[i2];
+							c.x = VR_FMA(VR_FMA(w2, dc.x, c0.x), m, spec); c.y = VR_FMA(VR_FMA(w2, dc.y, c0.y), m, spec); c.z = VR_FMA(VR_FMA(w2, dc.z, c0.z), m, spec);
+							if (lit_frame_shadowed()) {                                                    // wave-uniform: a kernel argument (vr_hip_set_shadow composes)
+								const float f = select_lanes_else(dense, shadow_factor(march_point<SAMPLING>(origin, dir, kx)), 1.0f);
+								c.x *= f; c.y *= f; c.z *= f;
+							}
+						}
 					}
 					if constexpr (SHADOW) {                                                            // vr_hip_set_shadow: dense samples are scaled by the light grid, lit or not
 						const uint64_t dense = __builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live;

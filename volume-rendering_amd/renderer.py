@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_shadow
+from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_shadow
 
 
 class HipRenderer:
@@ -145,6 +145,23 @@ class HipRenderer:
         n, ms = C.c_uint64(0), C.c_float(0)
         self._check(self._L.vr_hip_shadow_builds(self._ctx, C.byref(n), C.byref(ms)), "shadow_builds")
         return int(n.value), float(ms.value)
+
+    def set_lighting(self, ambient=0.25, diffuse=0.65, specular=0.4, shininess_log2=4):
+        """vr_hip_set_lighting: every later COMPOSITE frame shades its dense samples from the gradient of the interpolated field — ambient +
+        diffuse * |n.l| (two-sided) on the looked-up colour and a white highlight specular * |n.h|^(2^shininess_log2) — in place of the
+        reference's cue; params.light_kd is then ignored and the light is params.view.light_pos.  Coefficients 0..1, shininess_log2 0..10.
+        The frames must be TRILINEAR / TRILINEAR_Q8; MIP and isosurface frames ignore the lighting; a shadow and a clip compose with it."""
+        self._check(self._L.vr_hip_set_lighting(self._ctx, C.byref(make_lighting(ambient, diffuse, specular, shininess_log2))), "set_lighting")
+
+    def clear_lighting(self):
+        """Gradient lighting off (the default): the reference's cue again."""
+        self._check(self._L.vr_hip_set_lighting(self._ctx, None), "clear_lighting")
+
+    def lighting_frames(self):
+        """vr_hip_lighting_frames: the composite frames this context launched on the gradient-lit kernels"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_lighting_frames(self._ctx, C.byref(n)), "lighting_frames")
+        return int(n.value)
 
     def last_launch(self):
         """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
@@ -344,6 +361,13 @@ class MultiRenderer:
         if self._shadow is not None:
             self._check(self._L.vr_hip_multi_set_shadow(self._m, C.byref(make_shadow(step=float(ray_step), **self._shadow))), "set_shadow")
             self._shadow = None
+
+    def set_lighting(self, ambient=0.25, diffuse=0.65, specular=0.4, shininess_log2=4):
+        """vr_hip_multi_set_lighting: HipRenderer.set_lighting on every device's context"""
+        self._check(self._L.vr_hip_multi_set_lighting(self._m, C.byref(make_lighting(ambient, diffuse, specular, shininess_log2))), "set_lighting")
+
+    def clear_lighting(self):
+        self._check(self._L.vr_hip_multi_set_lighting(self._m, None), "clear_lighting")
 
     def set_volume(self, voxels):
         v = np.ascontiguousarray(voxels)
