@@ -407,6 +407,40 @@ typedef struct vr_lighting {
 int vr_hip_set_lighting(vr_ctx *ctx, const vr_lighting *lighting);      /* NULL = off (the default): the reference's cue */
 int vr_hip_lighting_frames(vr_ctx *ctx, uint64_t *frames_out);          /* testing aid: composite frames launched on the gradient-lit kernels */
 
+/* ---- pre-integrated (slab) classification for composite frames, in the integral-function form.  No reference counterpart. ----
+ * The reference classifies a sample by one transfer-function lookup at its value: whatever the transfer function holds between the values of
+ * two consecutive samples is never seen, a thin peak shows as rings and missed shells, and whether a ray catches it depends on the phase of
+ * its samples.  Pre-integration classifies the SLAB between two consecutive samples by the mean of the piecewise-linear transfer function
+ * over it.  It is context state, like the clip, the shadow and the lighting: off by default, and without it every frame is what it was, byte
+ * for byte.  vr_params and every other struct keep their size and layout.
+ * Integral table.  vr_hip_set_transfer_fn builds K, 128 x float4, on the host from the 128 premultiplied entries it is given and uploads it
+ * next to them: K[0] = 0 and K[i + 1] = fmaf(0.5f, tf[i] + tf[i + 1], K[i]) per channel for i = 0..126, in that order (the explicit fmaf).
+ * K(t), for a transfer-function coordinate t in [0, 127]: i = min((uint32_t) t, 126), w = t - (float) i,
+ * K(t) = fmaf(w, fmaf(0.5f * w, tf[i + 1] - tf[i], tf[i]), K[i]) per channel — full fp32 weights in both TRILINEAR modes (the shadow factor's
+ * precedent).  No expf and no powf: CPU and GPU do not share one bit for bit.
+ * Slab composite frame.  vr_hip_render / vr_hip_render_device (and vr_hip_multi_* through the per-device contexts) composite as before with one
+ * replacement, the looked-up colour c of a sample.  tb is the sample's clamped transfer-function coordinate, formed as before:
+ * fmed3(fma(raw, tf_scale, -0.5f), 0, 127).  tp is the tb of the PREVIOUS sample of the accumulation loop; for the loop's first sample — the
+ * first at or after the clipped and leapt kx; there is no leaping inside the accumulation loop — tp = tb.  d = tb - tp.
+ *  - Narrow slab, !(fabsf(d) >= 0.5f): c is the ordinary filtered lookup of the frame's sampling mode (in _Q8 the weight is rounded) at
+ *    tm = 0.5f * (tp + tb).  With d == 0 this is the point-classified lookup, bit for bit.
+ *  - Wide slab, otherwise: r = 1.0f / d by IEEE division and c = (K(tb) - K(tp)) * r per channel, the difference and the product rounded
+ *    separately.
+ * Everything after the lookup is unchanged and sees this c: the c.w > 0.05f dense test, the reference's cue (with the sample's own raw and
+ * raw_l), the shadow factor, the gradient lighting (steps 1-5 of its contract), the accumulation and early termination.
+ * Exact shortcuts.  K(t) is exactly 0 for t <= tf_zero_below, so a sample contributes exactly nothing when both tp and tb are below it; a
+ * sample whose tb is below it but whose tp is not is NOT transparent.
+ * Other behaviour.  VR_SAMPLE_NEAREST composite frames under pre-integration return VR_ERR_INVALID (the isosurface's, the shadow's and the
+ * lighting's precedent).  MIP and isosurface frames IGNORE the state.  The shadow builder ignores it: light rays stay point classified.  A
+ * slab frame reads what a clipped frame reads — the linear array, quad bricks with the per-view plane, or oct bricks —, never a run copy or a
+ * column window: vr_launch_info::layout is then 0, 1 or 5.  Setting a state that differs from the current one forgets the cached tile
+ * mappings and recorded orders, as vr_hip_set_lighting does.  There is no opacity correction: the table is the one of the frame's own step.
+ * Errors.  VR_ERR_INVALID for on > 1.  vr_hip_preint_frames counts the composite frames this context launched on the slab kernels and
+ * vr_hip_download_tf_integral returns K as uploaded, 512 floats (testing aids). */
+int vr_hip_set_preintegration(vr_ctx *ctx, uint32_t on);               /* 0 = off (the default), 1 = slab classification; other values VR_ERR_INVALID */
+int vr_hip_preint_frames(vr_ctx *ctx, uint64_t *frames_out);           /* testing aid: composite frames launched on the slab kernels */
+int vr_hip_download_tf_integral(vr_ctx *ctx, float *host_out512);      /* testing aid: K, 128 x float4; VR_ERR_NOT_READY without a transfer function */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {
@@ -476,6 +510,7 @@ int  vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf_premult_rgba, con
 int  vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip);      /* vr_hip_set_clip on every device's context */
 int  vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow); /* vr_hip_set_shadow on every device's context */
 int  vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting); /* vr_hip_set_lighting on every device's context */
+int  vr_hip_multi_set_preintegration(vr_multi *m, uint32_t on);           /* vr_hip_set_preintegration on every device's context */
 int  vr_hip_multi_set_volume(vr_multi *m, const void *host_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);
 int  vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bytes_per_voxel);
 int  vr_hip_multi_render(vr_multi *m, const vr_params *params, uint8_t *host_rgba);           /* whole frame -> host buffer */

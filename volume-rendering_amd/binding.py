@@ -158,6 +158,9 @@ def lib():
         "vr_hip_shadow_builds": (C.c_int, [vp, P(u64), f32p]),
         "vr_hip_set_lighting": (C.c_int, [vp, P(VrLighting)]),
         "vr_hip_lighting_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_set_preintegration": (C.c_int, [vp, u32]),
+        "vr_hip_preint_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_download_tf_integral": (C.c_int, [vp, f32p]),
         "vr_hip_last_launch": (C.c_int, [vp, P(VrLaunchInfo)]),
         "vr_hip_read_tile_costs": (C.c_int, [vp, vp, u32, P(u32), P(u32)]),
         "vr_hip_render": (C.c_int, [vp, P(VrParams), vp]),
@@ -188,6 +191,7 @@ def lib():
         "vr_hip_multi_set_clip": (C.c_int, [vp, P(VrClip)]),
         "vr_hip_multi_set_shadow": (C.c_int, [vp, P(VrShadow)]),
         "vr_hip_multi_set_lighting": (C.c_int, [vp, P(VrLighting)]),
+        "vr_hip_multi_set_preintegration": (C.c_int, [vp, u32]),
         "vr_hip_multi_set_volume": (C.c_int, [vp, vp, u32, u32, u32, u32]),
         "vr_hip_multi_generate_volume": (C.c_int, [vp, u32, u32, u32, u32]),
         "vr_hip_multi_render": (C.c_int, [vp, P(VrParams), vp]),

@@ -116,6 +116,14 @@ int HipRenderer::set_lighting(const vr_lighting *lighting) {
 	return rc == 0 ? 0 : 1;
 }
 
+int HipRenderer::set_preintegration(bool on) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	const int rc = multi_ ? vr_hip_multi_set_preintegration(multi_, on ? 1u : 0u) : vr_hip_set_preintegration(ctx_, on ? 1u : 0u);
+	return rc == 0 ? 0 : 1;
+}
+
 int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 	if (!ok() || buffer == nullptr)
 		return 1;

@@ -105,6 +105,10 @@ class HipRenderer : public Renderer {
 		// ignore it.  clear_lighting() = set_lighting(NULL) = off.  0 = ok, 1 = failure (a coefficient outside 0..1, shininess_log2 > 10).
 		int set_lighting(const vr_lighting *lighting);
 		int clear_lighting() { return set_lighting(nullptr); }
+		// Pre-integrated (slab) classification of every later COMPOSITE frame of this renderer (vr_hip_set_preintegration /
+		// vr_hip_multi_set_preintegration: a sample takes the mean of the transfer function between the previous sample's value and its own);
+		// set_mip and set_iso frames ignore it; clip, shadow and lighting compose with it.  false = off, the default.  0 = ok, 1 = failure.
+		int set_preintegration(bool on);
 		// fills the by-value parameter block from a Raycaster (whole-frame partition)
 		static void to_params(const Raycaster &r, vr_sampling sampling, vr_params *out);
 	private:

@@ -5,7 +5,7 @@
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
 //              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
-//              [-phong <ka> <kd> <ks> <n>] [-o <frame.ppm>]
+//              [-phong <ka> <kd> <ks> <n>] [-preint] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -49,6 +49,8 @@ void print_usage() {
 	       "         grid of S^3 nodes (2..256) marched towards the view's light; strength 0..1 (default 1), step in model units (default: the ray step)\n"
 	       "  -phong <ka> <kd> <ks> <n> : gradient lighting for the composite of the trilinear renderer (-r 1): ambient, diffuse and specular\n"
 	       "         coefficients 0..1 and shininess_log2 0..10 (the highlight is raised to the power 2^n); composes with -shadow and the clip\n"
+	       "  -preint : pre-integrated (slab) classification for the composite of the trilinear renderer (-r 1): a sample takes the mean of the\n"
+	       "         transfer function between the previous sample's value and its own; composes with the clip, -shadow and -phong\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -254,7 +256,7 @@ int main(int argc, char **argv) {
 	bool clip_box = false, clip_plane = false;
 	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
 	int shadow_dims = 0;
-	bool phong = false;
+	bool phong = false, preint = false;
 	vr_lighting lighting = { 0.25f, 0.65f, 0.4f, 4u };
 	float shadow_strength = 1.0f, shadow_step = 0.0f;
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
@@ -303,6 +305,7 @@ int main(int argc, char **argv) {
 		else if (strcmp(arg, "-shadow") == 0) { if (need(1)) shadow_dims = atoi(argv[++i]); }
 		else if (strcmp(arg, "-shadow-strength") == 0) { if (need(1)) shadow_strength = (float) atof(argv[++i]); }
 		else if (strcmp(arg, "-shadow-step") == 0) { if (need(1)) shadow_step = (float) atof(argv[++i]); }
+		else if (strcmp(arg, "-preint") == 0) preint = true;
 		else if (strcmp(arg, "-phong") == 0) {
 			if (need(4)) { lighting.ambient = (float) atof(argv[++i]); lighting.diffuse = (float) atof(argv[++i]); lighting.specular = (float) atof(argv[++i]); lighting.shininess_log2 = (uint32_t) atoi(argv[++i]); phong = true; }
 		}
@@ -377,6 +380,12 @@ int main(int argc, char **argv) {
 		if (!benchmark_mode && renderer_id != 1) { printf("Error: -phong needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
 		if (renderers[1]->set_lighting(&lighting) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
 		printf("Lighting: ambient %g, diffuse %g, specular %g, shininess 2^%u\n", lighting.ambient, lighting.diffuse, lighting.specular, lighting.shininess_log2);
+	}
+	if (preint) {
+		if (mip || iso) { printf("Error: -preint works with the composite (drop -mip / -iso)\n"); return EXIT_FAILURE; }
+		if (!benchmark_mode && renderer_id != 1) { printf("Error: -preint needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
+		if (renderers[1]->set_preintegration(true) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
+		printf("Classification: pre-integrated (slab)\n");
 	}
 	if (benchmark_mode) {
 		benchmark();

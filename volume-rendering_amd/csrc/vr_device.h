@@ -122,6 +122,9 @@ struct RayKernelArgs {
 	uint32_t *bc_fault;
 	uint32_t bc_ntiles;
 #endif
+	// vr_hip_set_preintegration (include/vr_hip.h): 1 = slab classification.  For the host alone (launch_raymarch
+	// hands such a frame to vr_slab.hip); no kernel reads it.  The table K lies behind the 128 entries of the transfer function.
+	uint32_t slab_on;
 };
 // Tiles are numbered in VR_TILE_ORDER x VR_TILE_ORDER blocks (blocks row-major, tiles column by column inside a block — VR_XCD_MODE
 // below —, the ragged right / bottom margins after them): consecutive workgroups — which the hardware spreads over the eight XCDs — are screen neighbours.
@@ -389,6 +392,13 @@ hipError_t launch_raymarch_shadowed(const RayKernelArgs &a, const void *linear, 
 // vr_light.hip launches composite_lit
 hipError_t launch_composite_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                                 const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
+
+// the pre-integrated composite frame (a.slab_on; include/vr_hip.h vr_hip_set_preintegration): launch_raymarch hands
+// it over, vr_slab.hip launches composite_slab or, with a.light_on, composite_slab_lit.  tf_premult: the 128 entries and K behind them.
+hipError_t launch_composite_slab(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                 const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
+hipError_t launch_composite_slab_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                     const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);

@@ -111,6 +111,10 @@ struct vr_ctx {
 	// gradient lighting (vr_hip_set_lighting): composite frames run the composite_lit kernels; lit_frames counts them (vr_hip_lighting_frames)
 	bool lighting_on = false; vr_lighting lighting = {};
 	uint64_t lit_frames = 0;
+	// pre-integrated classification (vr_hip_set_preintegration): composite frames run the composite_slab / composite_slab_lit kernels;
+	// preint_frames counts them (vr_hip_preint_frames).  The integral table K lies behind the 128 entries of `tf` on the device.
+	bool preint_on = false;
+	uint64_t preint_frames = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -569,8 +573,14 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	if (lighting && p->sampling == VR_SAMPLE_NEAREST)
 		return fail(c, VR_ERR_INVALID, "a lighting is set: the gradient is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
 		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_lighting(ctx, NULL) switches the lighting off)");
+	// A pre-integrated frame (vr_hip_set_preintegration) reads what a clipped frame reads as well; clip, shadow and lighting compose with it
+	const bool preint = c->preint_on;
+	if (preint && p->sampling == VR_SAMPLE_NEAREST)
+		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab lies between two samples of the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_preintegration(ctx, 0) switches it off)");
 	RayKernelArgs a;
 	volume_args(c, p, a);
+	if (preint) a.slab_on = 1u;
 	if (lighting) {
 		a.light_on = 1u; a.light_ka = c->lighting.ambient; a.light_kd = c->lighting.diffuse; a.light_ks = c->lighting.specular;
 		a.light_n = c->lighting.shininess_log2;
@@ -621,7 +631,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	}
 	a.force_wide = c->force_wide;
 	// (a shadowed frame reads what a clipped frame reads: its kernels are the clipped ones with one more fetch per dense sample)
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting || preint;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
 	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
@@ -948,6 +958,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
 	if (rc) return rc;
 	if (lighting) c->lit_frames++;
+	if (preint) c->preint_frames++;
 	if (dual_advance) {                          // behind the frame, on its stream
 		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
 		VR_TRY(c, hipEventRecord(hit->order_ready, stream));
@@ -1295,7 +1306,7 @@ int vr_hip_create(int device, vr_ctx **out) {
 		VR_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
 		VR_TRY(c, hipStreamCreateWithPriority(&c->stream_first, hipStreamNonBlocking, greatest));
 	}
-	VR_TRY(c, hipMalloc((void **) &c->tf, VR_TF_SIZE * 4 * sizeof(float)));
+	VR_TRY(c, hipMalloc((void **) &c->tf, 2 * VR_TF_SIZE * 4 * sizeof(float)));      // the 128 entries, and their running integral K behind them
 	VR_TRY(c, hipMalloc((void **) &c->esl, VR_ESL_VOLUME_SIZE * sizeof(uint32_t)));
 	VR_TRY(c, hipMalloc((void **) &c->minmax, 32 * 32 * 32 * 2));
 	VR_TRY(c, hipMalloc((void **) &c->hist, 256 * sizeof(unsigned long long)));
@@ -1365,6 +1376,13 @@ int vr_hip_set_transfer_fn(vr_ctx *c, const float *tf, const uint32_t *esl) {
 	// (UI.cpp:52-61,317-341), so other contexts and streams of the device are not stalled (no hipDeviceSynchronize).
 	VR_TRY(c, drain(c));
 	VR_TRY(c, hipMemcpyAsync(c->tf, tf, VR_TF_SIZE * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	// K, the running integral of the piecewise-linear transfer function (vr_hip_set_preintegration): K[0] = 0, K[i + 1] = fma(0.5, tf[i] + tf[i + 1], K[i])
+	float integral[VR_TF_SIZE * 4];
+	for (int ch = 0; ch < 4; ch++) {
+		integral[ch] = 0.0f;
+		for (int i = 0; i + 1 < VR_TF_SIZE; i++) integral[4 * (i + 1) + ch] = std::fmaf(0.5f, tf[4 * i + ch] + tf[4 * (i + 1) + ch], integral[4 * i + ch]);
+	}
+	VR_TRY(c, hipMemcpyAsync(c->tf + VR_TF_SIZE * 4, integral, sizeof integral, hipMemcpyHostToDevice, c->stream));      // (the stream is synchronised below, while `integral` lives)
 	VR_TRY(c, hipMemcpyAsync(c->esl, esl, VR_ESL_VOLUME_SIZE * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	VR_TRY(c, hipStreamSynchronize(c->stream));
 	int zero = -1;
@@ -1532,6 +1550,31 @@ int vr_hip_set_lighting(vr_ctx *c, const vr_lighting *l) {
 int vr_hip_lighting_frames(vr_ctx *c, uint64_t *frames_out) {
 	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
 	*frames_out = c->lit_frames;
+	return VR_OK;
+}
+
+int vr_hip_set_preintegration(vr_ctx *c, uint32_t on) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (on > 1u) return fail(c, VR_ERR_INVALID, "pre-integration must be 0 (off) or 1 (slab classification)");
+	if ((on != 0u) == c->preint_on) return VR_OK;
+	c->preint_on = on != 0u;
+	forget_tile_mappings(c);                     // as for a lighting: the caches are keyed by vr_params alone, and a slab frame reads other copies
+	forget_recorded_orders(c);
+	return VR_OK;
+}
+
+int vr_hip_preint_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->preint_frames;
+	return VR_OK;
+}
+
+int vr_hip_download_tf_integral(vr_ctx *c, float *host_out512) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (host_out512 == nullptr) return fail(c, VR_ERR_INVALID, "host_out512 is NULL");
+	if (!c->tf_set) return fail(c, VR_ERR_NOT_READY, "no transfer function is set (vr_hip_set_transfer_fn)");
+	VR_TRY(c, hipSetDevice(c->device));
+	VR_TRY(c, hipMemcpy(host_out512, c->tf + VR_TF_SIZE * 4, VR_TF_SIZE * 4 * sizeof(float), hipMemcpyDeviceToHost));
 	return VR_OK;
 }
 

@@ -361,6 +361,12 @@ int vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting) {
 	return VR_OK;
 }
 
+int vr_hip_multi_set_preintegration(vr_multi *m, uint32_t on) {
+	if (m == nullptr) return VR_ERR_INVALID;
+	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_preintegration(m->ctx[r], on)); if (rc) return rc; }
+	return VR_OK;
+}
+
 int vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip) {
 	if (m == nullptr) return VR_ERR_INVALID;
 	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_clip(m->ctx[r], clip)); if (rc) return rc; }

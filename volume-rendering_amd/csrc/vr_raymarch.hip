@@ -15,7 +15,7 @@ __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)
 void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
                      const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                      const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	constexpr bool CLIP = false, SHADOW = false, LIT = false;
+	constexpr bool CLIP = false, SHADOW = false, LIT = false, SLAB = false;
 #include "vr_raymarch_body.inc"
 }
 // ... of a clipped frame (vr_hip_set_clip): the linear array, the quad, voxel and oct bricks — never a run copy (launch_frame).  Its own
@@ -26,7 +26,7 @@ void raymarch_clipped(const RayKernelArgs a, const void *__restrict__ vol, const
                       const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                       const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT), "a clipped frame never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = false;
+	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = false;
 #include "vr_raymarch_body.inc"
 }
 
@@ -52,6 +52,9 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
                            const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
 	if (bricked != nullptr && (args.layout == kLayoutColumn || args.layout == kLayoutVoxCol))      // orthogonal view along args.col_axis, full march, 1-byte voxels (launch_frame)
 		return launch_colmarch(args, bricked, tf, out, stream);
+	if (args.slab_on)                                            // a pre-integrated frame (vr_hip_set_preintegration), clipped, shadowed, lit or not: kernels of its own, in vr_slab.hip
+		return args.light_on ? launch_composite_slab_lit(args, linear, bricked, bpv, tf, esl, out, sched, stream)
+		                     : launch_composite_slab(args, linear, bricked, bpv, tf, esl, out, sched, stream);
 	if (args.light_on)                                           // a gradient-lit frame (vr_hip_set_lighting), shadowed or not: kernels of its own, in vr_light.hip
 		return launch_composite_lit(args, linear, bricked, bpv, tf, esl, out, sched, stream);
 	if (args.shadow_on)                                          // a shadowed frame (vr_hip_set_shadow): kernels of its own, in vr_shadow.hip

@@ -1,6 +1,6 @@
 // vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
-// `constexpr bool CLIP`, `SHADOW` and `LIT` set), of raymarch_shadowed (vr_shadow.hip) and of composite_lit (vr_light.hip): a, vol, tf_g,
-// esl_g, out, tile_order, tile_cost are the kernel's parameters.
+// `constexpr bool CLIP`, `SHADOW`, `LIT` and `SLAB` set), of raymarch_shadowed (vr_shadow.hip), of composite_lit (vr_light.hip) and of
+// composite_slab and composite_slab_lit (vr_slab.hip): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
 	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live
@@ -39,6 +39,9 @@
 	constexpr bool kUseLut = L::max_dim != 0;
 	__shared__ LdsTables lds;
 	__shared__ __attribute__((aligned(16))) uint32_t lut[L::words];
+	// SLAB (vr_hip_set_preintegration): the running integral K of the piecewise-linear transfer function, 2 KiB that only the slab kernels
+	// declare (one element elsewhere, never referenced: it takes no LDS).  The host uploads K behind the 128 entries of the transfer function.
+	__shared__ f4 slab_k[SLAB ? VR_TF_SIZE : 1];
 #ifdef VR_LDS_PAD          // tuning aid: occupy extra LDS to lower the number of resident workgroups per CU
 	__shared__ uint32_t lds_pad[VR_LDS_PAD / 4];
 	if (a.dim_x == 0xffffffffu) lds_pad[threadIdx.x] = 1;
@@ -76,6 +79,7 @@
 			f4 d; d.x = c1.x - c0.x; d.y = c1.y - c0.y; d.z = c1.z - c0.z; d.w = c1.w - c0.w;
 			lds.dtf[t] = d;
 		}
+		if (SLAB && t < VR_TF_SIZE) slab_k[t] = ((const f4 *) tf_g)[VR_TF_SIZE + t];
 		for (uint32_t i = t; i < VR_ESL_VOLUME_SIZE; i += kThreads) lds.esl[i] = esl_g[i];
 		if (SAMPLING == VR_SAMPLE_NEAREST && BPV == 1 && t < 256u) lds.unit[t] = (float) t / 255.0f;   // the same IEEE division, once
 	}
@@ -324,11 +328,26 @@
 			// voxels, not on any default path, take 72-74 VGPRs)
 			constexpr bool kFourWordSlots = BPV == 2 || (CLIP && LAYOUT == kLayoutLinear);
 			// (a shadowed frame: one sample less ahead — with the factor fetch of its dense block the full depth takes 66-69 VGPRs, 7 waves per SIMD;
-			// a gradient-lit frame likewise: one or two gradient fetches are in flight inside its dense block)
+			// a gradient-lit frame likewise: one or two gradient fetches are in flight inside its dense block; a slab frame likewise: the previous
+			// sample's coordinate crosses the march and a wide slab holds two integrals beside the colour)
 			constexpr int kFullDepth = is_run_layout(LAYOUT) ? kRunDepth : (!kFourWordSlots ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth));
-			constexpr int kDepth = (SHADOW || LIT) && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
+			constexpr int kDepth = (SHADOW || LIT || SLAB) && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
 			TriFetch<BPV, LAYOUT> f[kSlots]; float ks[kSlots];
 			ks[0] = kx;
+			// SLAB: the clamped transfer-function coordinate of the previous sample of this loop; below 0 = there is none yet (the first
+			// sample is every lane's first: ks[0] is the lane's own kx), and the sample's own coordinate stands in
+			// kSlabLazy (shortcut variant (a), the default; VR_SLAB_LAZY=0 builds variant (b), which resolves every sample): shortcut (1)
+			// stays — taken when the corners are low AND no live lane's previous coordinate is above tf_zero_below, for a slab that
+			// ends in transparent values but starts in dense ones is not transparent — and a skipped sample leaves tp = -2: "not
+			// resolved".  The first sample behind a run of skipped ones resolves its predecessor then, from a copy of that slot's words
+			// and k taken before the prefetch re-issues the slot: the exact coordinate, at the price of the copy.
+#ifndef VR_SLAB_LAZY
+#define VR_SLAB_LAZY 1
+#endif
+			constexpr bool kSlabLazy = SLAB && VR_SLAB_LAZY;
+			float tp = -1.0f;
+			(void) tp;
+			if constexpr (kSlabLazy) ks[kSlots - 1] = kx;                       // (read by the first sample's copy, never used)
 			f[kSlots - 1].w0 = f[kSlots - 1].w1 = f[kSlots - 1].w2 = f[kSlots - 1].w3 = 0; f[kSlots - 1].q = 0; f[kSlots - 1].q2 = 0; f[kSlots - 1].o = (u32x4) (0u);
 			static_for<0, kDepth>([&](auto j) {
 				if constexpr (j.value > 0) ks[j.value] = ks[j.value - 1] + step_v;
@@ -336,6 +355,9 @@
 			});
 			auto step_sample = [&](auto jc) {
 				constexpr int c = decltype(jc)::value, n = (c + kDepth) % kSlots, nx = (c + 1) % kSlots;
+				TriFetch<BPV, LAYOUT> before = f[n];                                    // kSlabLazy: slot n held the previous sample
+				const float k_before = ks[n];
+				(void) before; (void) k_before;
 				ks[n] = ks[(n + kSlots - 1) % kSlots] + step_v;
 				f[n] = issue(ks[n]);
 #ifndef VR_NO_SCHED_BARRIER
@@ -373,7 +395,13 @@
 				if (LAYOUT != kLayoutLinear) corners = BPV == 1 ? (now.w0 | now.w1) : (now.w0 | now.w1 | now.w2 | now.w3);
 				else                          corners = now.w0 | now.w1 | now.w2 | now.w3;
 				// skip_cmp is 0; a TF without leading zero entries (nothing may be skipped) comes with skip_mask 0 and skip_cmp 1: 0 != 1 always
-				if ((__builtin_amdgcn_uicmp(corners & a.skip_mask, a.skip_cmp, kIcmpNE) & live) != 0ull && VR_OPEN_LANES(acc.w, live) != 0ull) {
+				// SLAB: the next sample needs this one's coordinate exactly, transparent or not.  Variant (b) resolves every sample; variant (a),
+				// kSlabLazy above, keeps shortcut (1) and resolves a skipped sample when its successor asks.  (2) is widened to "this
+				// coordinate and the previous one" (K is exactly 0 up to tf_zero_below).  The saturation shortcut stays: a lane whose alpha
+				// is exactly 1 composites with weight 0 for good, whatever its tp is by then.
+				if (((SLAB && !kSlabLazy) ||
+				     ((kSlabLazy ? (__builtin_amdgcn_uicmp(corners & a.skip_mask, a.skip_cmp, kIcmpNE) | __builtin_amdgcn_fcmpf(tp, a.tf_zero_below, kFcmpOGT))
+				                 : __builtin_amdgcn_uicmp(corners & a.skip_mask, a.skip_cmp, kIcmpNE)) & live) != 0ull) && VR_OPEN_LANES(acc.w, live) != 0ull) {
 				if (kLazy) {
 					const uint64_t inside = __builtin_amdgcn_fcmpf(kx, ky, kFcmpOLE);
 					if ((live & ~inside) != 0ull) { live &= inside; step_v = select_lanes(live, step); }
@@ -393,14 +421,49 @@
 				const float raw = tri_resolve<BPV, LAYOUT, kQ8>(now, a, xb, yb, zb, along_y);                 // GPURenderer4.cu:76
 				// GPURenderer4.cu:77 filtered TF: texel coordinate tb, entries floor(tb) and floor(tb)+1
 				const float tb = __builtin_amdgcn_fmed3f(VR_FMA(raw, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
-				if ((__builtin_amdgcn_fcmpf(tb, a.tf_zero_below, kFcmpOGE) & live) != 0ull) {
+				if constexpr (kSlabLazy) {
+					if (__builtin_amdgcn_ballot_w64(tp == -2.0f) != 0ull) {                                       // wave-uniform: the previous sample was skipped
+						const float raw_p = tri_resolve<BPV, LAYOUT, kQ8>(before, a, VR_FMA(k_before, A.x, B.x), VR_FMA(k_before, A.y, B.y), VR_FMA(k_before, A.z, B.z));
+						tp = __builtin_amdgcn_fmed3f(VR_FMA(raw_p, a.tf_scale, -0.5f), 0.0f, (float) (VR_TF_SIZE - 1));
+					}
+				}
+				const float tq = SLAB ? (tp < 0.0f ? tb : tp) : tb;                                              // SLAB: the front of the slab
+				if constexpr (SLAB) tp = tb;
+				if (((SLAB ? (__builtin_amdgcn_fcmpf(tb, a.tf_zero_below, kFcmpOGE) | __builtin_amdgcn_fcmpf(tq, a.tf_zero_below, kFcmpOGE))
+				           : __builtin_amdgcn_fcmpf(tb, a.tf_zero_below, kFcmpOGE)) & live) != 0ull) {
 					f4 c;
 					{
-						const uint32_t i = (uint32_t) (int) tb;
-						const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb));
+						const float tm = SLAB ? 0.5f * (tq + tb) : tb;                                             // a narrow slab: the lookup at its middle (tb itself where d is 0)
+						const uint32_t i = (uint32_t) (int) tm;
+						const float w = filter_weight<kQ8>(__builtin_amdgcn_fractf(tm));
 						const f4 c0 = lds.tf[i], dc = lds.dtf[i];
 						c.x = VR_FMA(w, dc.x, c0.x); c.y = VR_FMA(w, dc.y, c0.y);
 						c.z = VR_FMA(w, dc.z, c0.z); c.w = VR_FMA(w, dc.w, c0.w);
+					}
+					if constexpr (SLAB) {
+						// a wide slab, |d| >= 0.5: c = (K(tb) - K(tp)) / d, the mean of the transfer function over the slab, with full fp32 weights in
+						// both sampling modes; the division, the difference and the product each rounded once (include/vr_hip.h)
+						const float d = tb - tq;
+						const uint64_t wide = __builtin_amdgcn_fcmpf(__builtin_fabsf(d), 0.5f, kFcmpOGE) & live;
+						if (wide != 0ull) {
+							auto integral = [&](float t) {
+								const uint32_t i0 = (uint32_t) t, i = i0 < (uint32_t) (VR_TF_SIZE - 2) ? i0 : (uint32_t) (VR_TF_SIZE - 2);
+								const float w = t - (float) i, hw = 0.5f * w;
+								const f4 c0 = lds.tf[i], dc = lds.dtf[i], k0 = slab_k[i];
+								f4 r;
+								r.x = VR_FMA(w, VR_FMA(hw, dc.x, c0.x), k0.x); r.y = VR_FMA(w, VR_FMA(hw, dc.y, c0.y), k0.y);
+								r.z = VR_FMA(w, VR_FMA(hw, dc.z, c0.z), k0.z); r.w = VR_FMA(w, VR_FMA(hw, dc.w, c0.w), k0.w);
+								return r;
+							};
+							// (register diet: the front's integral is complete before the back's three table reads are issued)
+							f4 kp = integral(tq);
+							asm volatile("" : "+v"(kp.x), "+v"(kp.y), "+v"(kp.z), "+v"(kp.w));
+							__builtin_amdgcn_sched_barrier(0);
+							const f4 kb = integral(tb);
+							const float r = 1.0f / d;
+							c.x = select_lanes_else(wide, (kb.x - kp.x) * r, c.x); c.y = select_lanes_else(wide, (kb.y - kp.y) * r, c.y);
+							c.z = select_lanes_else(wide, (kb.z - kp.z) * r, c.z); c.w = select_lanes_else(wide, (kb.w - kp.w) * r, c.w);
+						}
 					}
 					if constexpr (!LIT) {
 						const uint64_t shaded = lit ? (__builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live) : 0ull;   // GPURenderer4.cu:78
@@ -425,12 +488,25 @@
 							// (register diet: only c.w and tb cross the gradient fetches — the colour is looked up again behind them, the same bits)
 							float m, spec, tb2 = tb;
 							light_sample<BPV, ADDR, LAYOUT, kQ8>(vol, a, lut, A, B, origin, dir, kx, dense, c.w, m, spec);
+							if constexpr (SLAB) {                                                      // a slab's colour is not one lookup: it crosses the gradient fetches
+								c.x = VR_FMA(c.x, m, spec); c.y = VR_FMA(c.y, m, spec); c.z = VR_FMA(c.z, m, spec);
+							} else {
 							asm volatile("" : "+v"(tb2));
 							const uint32_t i2 = (uint32_t) (int) tb2;
 							const float w2 = filter_weight<kQ8>(__builtin_amdgcn_fractf(tb2));
 							const f4 c0 = lds.tf[i2], dc = lds.dtf[i2];
 							c.x = VR_FMA(VR_FMA(w2, dc.x, c0.x), m, spec); c.y = VR_FMA(VR_FMA(w2, dc.y, c0.y), m, spec); c.z = VR_FMA(VR_FMA(w2, dc.z, c0.z), m, spec);
+							}
 							if (lit_frame_shadowed()) {                                                    // wave-uniform: a kernel argument (vr_hip_set_shadow composes)
+								const float f = select_lanes_else(dense, shadow_factor(march_point<SAMPLING>(origin, dir, kx)), 1.0f);
+								c.x *= f; c.y *= f; c.z *= f;
+							}
+						}
+					}
+					if constexpr (SLAB && !LIT) {                                                      // a slab frame takes the shadow as composite_lit does: a kernel argument, wave-uniform
+						if (lit_frame_shadowed()) {
+							const uint64_t dense = __builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live;
+							if (dense != 0ull) {
 								const float f = select_lanes_else(dense, shadow_factor(march_point<SAMPLING>(origin, dir, kx)), 1.0f);
 								c.x *= f; c.y *= f; c.z *= f;
 							}
@@ -449,7 +525,7 @@
 					live &= ~__builtin_amdgcn_fcmpf(acc.w, threshold, kFcmpOGT);                        // ERT (CPURenderer.cpp:35-36)
 					if (kFree) step_v = select_lanes(live, step);                                       // terminated rays stop marching
 				}
-				}
+				} else if constexpr (kSlabLazy) tp = -2.0f;                                                 // skipped: resolved later, if a sample needs it
 				if (!kLazy) {
 					const uint64_t still = __builtin_amdgcn_fcmpf(kn, ky, kFcmpOLE);                    // the loop condition
 					if (kFree && (live & ~still) != 0ull) step_v = select_lanes(live & still, step);    // a lane has just left its segment

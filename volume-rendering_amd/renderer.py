@@ -163,6 +163,30 @@ class HipRenderer:
         self._check(self._L.vr_hip_lighting_frames(self._ctx, C.byref(n)), "lighting_frames")
         return int(n.value)
 
+    def set_preintegration(self, on=True):
+        """vr_hip_set_preintegration: every later COMPOSITE frame classifies the slab between two consecutive samples — the mean of the
+        piecewise-linear transfer function between the previous sample's value and its own, from the integral table K — in place of one
+        lookup per sample.  The frames must be TRILINEAR / TRILINEAR_Q8; MIP and isosurface frames ignore it; clip, shadow and lighting
+        compose with it.  `on` is passed through as an integer: anything but 0 / 1 / False / True is VR_ERR_INVALID."""
+        self._check(self._L.vr_hip_set_preintegration(self._ctx, int(on)), "set_preintegration")
+
+    def clear_preintegration(self):
+        """Pre-integration off (the default): one transfer-function lookup per sample again."""
+        self._check(self._L.vr_hip_set_preintegration(self._ctx, 0), "clear_preintegration")
+
+    def preint_frames(self):
+        """vr_hip_preint_frames: the composite frames this context launched on the slab kernels"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_preint_frames(self._ctx, C.byref(n)), "preint_frames")
+        return int(n.value)
+
+    def download_tf_integral(self):
+        """vr_hip_download_tf_integral: K as uploaded, [128, 4] float32"""
+        import numpy as np
+        out = np.zeros((128, 4), np.float32)
+        self._check(self._L.vr_hip_download_tf_integral(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "download_tf_integral")
+        return out
+
     def last_launch(self):
         """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
         column_voxels, column_shade_pairs, shadowed)."""
@@ -368,6 +392,10 @@ class MultiRenderer:
 
     def clear_lighting(self):
         self._check(self._L.vr_hip_multi_set_lighting(self._m, None), "clear_lighting")
+
+    def set_preintegration(self, on=True):
+        """vr_hip_multi_set_preintegration: HipRenderer.set_preintegration on every device's context"""
+        self._check(self._L.vr_hip_multi_set_preintegration(self._m, int(on)), "set_preintegration")
 
     def set_volume(self, voxels):
         v = np.ascontiguousarray(voxels)
