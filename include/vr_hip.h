@@ -441,6 +441,50 @@ int vr_hip_set_preintegration(vr_ctx *ctx, uint32_t on);               /* 0 = of
 int vr_hip_preint_frames(vr_ctx *ctx, uint64_t *frames_out);           /* testing aid: composite frames launched on the slab kernels */
 int vr_hip_download_tf_integral(vr_ctx *ctx, float *host_out512);      /* testing aid: K, 128 x float4; VR_ERR_NOT_READY without a transfer function */
 
+/* ---- backdrop: a composite frame over an opaque layer, and the hybrid of isosurface and volume.  No reference counterpart. ----
+ * A backdrop frame is a composite frame (with the context's clip, shadow, lighting and pre-integration as vr_hip_render_device sees them)
+ * whose rays stop at the depth of an opaque RGBA8 layer and whose accumulated colour is blended over the layer's: a rasterised tool, a slice
+ * plane or a background image behind the volume, or — the hybrid — the isosurface of the same volume inside it.  It is a per-call argument,
+ * not context state: without it every frame is what it was, byte for byte.  vr_params and every other struct keep their size and layout.
+ * Layers.  rgba: out_width * out_rows RGBA8 words, premultiplied; depth: as many floats, k of the pixel's own ray — the unit of the
+ * isosurface frame's depth buffer.  Both are partitioned by x0, out_width, out_rows, band_* exactly as the output: pixel (lx, ly) reads element
+ * ly * out_width + lx.
+ * Per pixel, behind View::get_ray, Raycaster::intersect and steps 1-3 of the clip contract (a backdrop frame always runs the clip's
+ * arithmetic, under the identity clip when none is set, which changes no bit):
+ *  1. d = depth[pixel].  The pixel HAS A SURFACE iff d >= 0.0f, an ordered compare: -1, any negative value and NaN mean no surface, +inf is a
+ *     surface behind everything (the background image).
+ *  2. No surface: the pixel is exactly what the frame without a backdrop stores; the layer's colour word is ignored.
+ *  3. Surface: ky = flmin(ky, d) (intersect's flmin), and the ray is a hit iff it was one and (kx < ky) && (ky > 0), the clip's test.  Everything
+ *     after that is the composite's own definition on the narrowed segment: the leaping loop and the accumulation loop `while (kx <= ky)` — a
+ *     sample at k == d is composited —, the classification, the cue, the shadow, the lighting, the slab, early termination.  The two guards
+ *     on ray_step look at the unnarrowed segment, as under a clip.
+ *  4. Pixel of a surface ray, b the layer's colour word: if the ray is a miss, or leaping leaves kx > ky, the pixel is b bit for bit.  Otherwise,
+ *     per channel, bf = ((float) byte + 0.5f) * (1.0f / 256.0f) (both exact), t = 1.0f - acc.w, o = fmaf(bf, t, acc) and the pixel is
+ *     write_color(o).  With acc == 0 that is b again; t is not clamped, and early termination changes nothing here.
+ *  5. In place: dev_rgba may be the layer's rgba — a pixel reads its own layer elements and writes only its own output element.
+ * Hybrid.  vr_hip_render_hybrid_device is by definition vr_hip_render_iso_device with the same params and iso into dev_rgba and dev_depth (a
+ * context-owned depth buffer when dev_depth is NULL), followed on the same stream by vr_hip_render_backdrop_device in place.  The isosurface
+ * frame sees clip, light_kd and esl as it always does and ignores shadow, lighting and pre-integration; the composite pass sees all of them.
+ * The depth returned is the isosurface's.  The context-owned buffers (the depth, and the staging of the layers for the host entry points)
+ * are allocated on first use and grown, never per frame; the host entry points are one upload per layer into one staging buffer (backdrop) or none
+ * (hybrid), the launches and one copy back per buffer.
+ * What such a frame reads.  What a clipped frame reads — vr_launch_info::layout is 0, 1 or 5 —, never a run copy or a column window.  Its
+ * tiles start in grid order: it neither uses nor records a measured tile order and leaves the cached mappings alone (the caches are keyed
+ * by vr_params and the layer changes per frame; this affects placement only).  Single device: the vr_hip_multi_* path has no backdrop.
+ * Errors.  VR_ERR_INVALID for a NULL struct or member and for VR_SAMPLE_NEAREST: the hybrid's surface is defined on the interpolated field
+ * and the kernels cover the TRILINEAR modes; a NEAREST backdrop is not provided.  VR_ERR_NOT_READY, the NULL conventions and everything else
+ * as for vr_hip_render_device (the hybrid: and as for vr_hip_render_iso_device).  vr_hip_backdrop_frames counts the composite frames this
+ * context launched on the backdrop kernels (testing aid). */
+typedef struct vr_backdrop {
+	const void *rgba;   /* out_width * out_rows RGBA8 words, premultiplied, laid out exactly like the frame's output buffer */
+	const void *depth;  /* out_width * out_rows floats, same layout: k of the pixel's own ray (the isosurface frame's depth) */
+} vr_backdrop;          /* 16 bytes */
+int vr_hip_render_backdrop_device(vr_ctx *ctx, const vr_params *params, const vr_backdrop *dev, void *dev_rgba, void *stream);
+int vr_hip_render_backdrop(vr_ctx *ctx, const vr_params *params, const vr_backdrop *host, uint8_t *host_rgba);
+int vr_hip_render_hybrid_device(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
+int vr_hip_render_hybrid(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, uint8_t *host_rgba, float *host_depth /* may be NULL */);
+int vr_hip_backdrop_frames(vr_ctx *ctx, uint64_t *frames_out);         /* testing aid: composite frames launched on the backdrop kernels */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

@@ -94,6 +94,12 @@ def make_lighting(ambient=0.25, diffuse=0.65, specular=0.4, shininess_log2=4):
     return VrLighting(float(ambient), float(diffuse), float(specular), int(shininess_log2))
 
 
+class VrBackdrop(C.Structure):
+    """vr_backdrop: the opaque layer of a backdrop frame — RGBA8 words (premultiplied) and float depths (k of the pixel's own ray; negative or
+    NaN = no surface), both laid out like the frame's output buffer"""
+    _fields_ = [("rgba", C.c_void_p), ("depth", C.c_void_p)]
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -169,6 +175,11 @@ def lib():
         "vr_hip_render_mip_device": (C.c_int, [vp, P(VrParams), vp, vp]),
         "vr_hip_render_iso": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp]),
         "vr_hip_render_iso_device": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp, vp]),
+        "vr_hip_render_backdrop": (C.c_int, [vp, P(VrParams), P(VrBackdrop), vp]),
+        "vr_hip_render_backdrop_device": (C.c_int, [vp, P(VrParams), P(VrBackdrop), vp, vp]),
+        "vr_hip_render_hybrid": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp]),
+        "vr_hip_render_hybrid_device": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp, vp]),
+        "vr_hip_backdrop_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

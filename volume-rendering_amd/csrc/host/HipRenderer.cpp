@@ -32,14 +32,14 @@ void HipRenderer::to_params(const Raycaster &r, vr_sampling sampling, vr_params 
 }
 
 HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
 	create_status_ = vr_hip_create(device, &ctx_);
 	if (create_status_ == 0)
 		prime(r);
 }
 
 HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
 	create_status_ = vr_hip_multi_create(n_devices, devices, &multi_);
 	if (create_status_ == 0)
 		prime(r);
@@ -139,10 +139,29 @@ int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 		mirror_error_ = "the isosurface renders on a single device (vr_hip_render_iso): construct the renderer without a device list";
 		return 1;
 	}
-	if (iso_) rc = device_buffer_ ? vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_iso(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
+	if (hybrid_ && multi_) {
+		mirror_error_ = "the hybrid renders on a single device (vr_hip_render_hybrid): construct the renderer without a device list";
+		return 1;
+	}
+	if (hybrid_) rc = device_buffer_ ? vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_hybrid(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
+	else if (iso_) rc = device_buffer_ ? vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_iso(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
 	else if (mip_) rc = device_buffer_ ? vr_hip_render_mip_device(ctx_, &p, buffer, nullptr) : vr_hip_render_mip(ctx_, &p, (uint8_t *) buffer);
 	else if (multi_) rc = device_buffer_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_multi_render(multi_, &p, (uint8_t *) buffer);
 	else rc = device_buffer_ ? vr_hip_render_device(ctx_, &p, buffer, nullptr) : vr_hip_render(ctx_, &p, (uint8_t *) buffer);
+	return rc == 0 ? 0 : 1;
+}
+
+int HipRenderer::render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop *layer) {
+	if (!ok() || buffer == nullptr)
+		return 1;
+	mirror_error_ = nullptr;
+	if (multi_) {
+		mirror_error_ = "a backdrop frame renders on a single device (vr_hip_render_backdrop): construct the renderer without a device list";
+		return 1;
+	}
+	vr_params p;
+	to_params(r, sampling_, &p);
+	const int rc = device_buffer_ ? vr_hip_render_backdrop_device(ctx_, &p, layer, buffer, nullptr) : vr_hip_render_backdrop(ctx_, &p, layer, (uint8_t *) buffer);
 	return rc == 0 ? 0 : 1;
 }
 

@@ -88,11 +88,20 @@ class HipRenderer : public Renderer {
 		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
 		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
 		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
-		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = false; }
+		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = false; }
 		// on: render_volume() produces the shaded isosurface at `level` (raw voxel units) with `refine` bisection steps (vr_hip_render_iso;
 		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
-		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = false; }
+		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = false; }
+		// on: render_volume() produces the hybrid (vr_hip_render_hybrid): that isosurface seen through the translucent volume in front of it —
+		// the isosurface frame, then the composite frame stopped at its depth and blended over it; the composite pass sees the clip, the
+		// shadow, the lighting and the pre-integration of this renderer.  Needs a TRILINEAR sampling mode.  Excludes set_mip and set_iso:
+		// the one set last holds.  Single device only, like them.
+		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = false; }
+		// One composite frame over an opaque layer (vr_hip_render_backdrop / vr_hip_render_backdrop_device by the buffer flavour of this
+		// renderer): `layer` holds host or device pointers accordingly, view.dims pixels each.  Whatever set_mip / set_iso / set_hybrid say,
+		// this is a composite frame.  Single device only.  0 = ok, 1 = failure.
+		int render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop *layer);
 		// The clip region of every later frame of this renderer — composite, set_mip and set_iso alike, and with a device list every device's
 		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
 		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.
@@ -122,6 +131,7 @@ class HipRenderer : public Renderer {
 		bool device_buffer_;
 		bool mip_;
 		bool iso_;
+		bool hybrid_;
 		vr_iso iso_params_;
 		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
 };

@@ -5,7 +5,7 @@
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
 //              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
-//              [-phong <ka> <kd> <ks> <n>] [-preint] [-o <frame.ppm>]
+//              [-phong <ka> <kd> <ks> <n>] [-preint] [-hybrid <level> [-refine <n>]] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -51,6 +51,9 @@ void print_usage() {
 	       "         coefficients 0..1 and shininess_log2 0..10 (the highlight is raised to the power 2^n); composes with -shadow and the clip\n"
 	       "  -preint : pre-integrated (slab) classification for the composite of the trilinear renderer (-r 1): a sample takes the mean of the\n"
 	       "         transfer function between the previous sample's value and its own; composes with the clip, -shadow and -phong\n"
+	       "  -hybrid <level> [-refine <n>] : the isosurface at <level> seen through the translucent volume in front of it (the isosurface frame, then\n"
+	       "         the composite stopped at its depth and blended over it), from the trilinear renderer (-r 1); single device; works alone and with\n"
+	       "         the clip, -shadow, -phong and -preint, which the composite pass sees; excludes -mip, -iso and -devices\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -250,7 +253,7 @@ int write_ppm(const char *path) {
 
 int main(int argc, char **argv) {
 	std::string file_name, out_ppm;
-	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false;
+	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false, hybrid = false;
 	float iso_level = 0.0f;
 	int iso_refine = 4;
 	bool clip_box = false, clip_plane = false;
@@ -297,6 +300,7 @@ int main(int argc, char **argv) {
 		else if (strcmp(arg, "-persp") == 0) persp = true;
 		else if (strcmp(arg, "-mip") == 0) mip = true;
 		else if (strcmp(arg, "-iso") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); iso = true; } }
+		else if (strcmp(arg, "-hybrid") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); hybrid = true; } }
 		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
 		else if (strcmp(arg, "-clip-box") == 0) {
 			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
@@ -347,6 +351,15 @@ int main(int argc, char **argv) {
 		if (!benchmark_mode && renderer_id != 1) { printf("Error: -iso needs the trilinear renderer (-r 1): an isosurface is defined on the interpolated field\n"); return EXIT_FAILURE; }
 		renderers[1]->set_iso(true, iso_level, (uint32_t) iso_refine);
 		printf("Isosurface at level %g, %d bisection steps\n", iso_level, iso_refine);
+	}
+
+	if (hybrid) {
+		if (!device_list.empty()) { printf("Error: -hybrid renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		if (mip || iso) { printf("Error: -hybrid excludes -mip and -iso\n"); return EXIT_FAILURE; }
+		if (iso_refine < 0 || iso_refine > 16) { printf("Error: -refine must be in 0..16\n"); return EXIT_FAILURE; }
+		if (renderer_id != 1) { printf("Error: -hybrid needs the trilinear renderer (-r 1): its surface is defined on the interpolated field\n"); return EXIT_FAILURE; }
+		renderers[1]->set_hybrid(true, iso_level, (uint32_t) iso_refine);
+		printf("Hybrid: isosurface at level %g, %d bisection steps, behind the composite\n", iso_level, iso_refine);
 	}
 
 	if (clip_box || clip_plane) {

@@ -125,6 +125,12 @@ struct RayKernelArgs {
 	// vr_hip_set_preintegration (include/vr_hip.h): 1 = slab classification.  For the host alone (launch_raymarch
 	// hands such a frame to vr_slab.hip); no kernel reads it.  The table K lies behind the 128 entries of the transfer function.
 	uint32_t slab_on;
+	// vr_hip_render_backdrop (include/vr_hip.h vr_backdrop): the opaque layer a backdrop frame stops at and blends over.
+	// Read by the composite_backdrop* kernels only (vr_backdrop.hip, vr_backdrop_slab.hip), through the laundered kernel-argument pointer like
+	// the clip words: the depth in front of the march, the colour (and the depth again) behind it.  Addresses, not pointers: the output buffer
+	// may be the colour layer.  backdrop_on is for the host (launch_raymarch hands such a frame to the new units).
+	uint32_t backdrop_on;
+	uint64_t backdrop_rgba, backdrop_depth;
 };
 // Tiles are numbered in VR_TILE_ORDER x VR_TILE_ORDER blocks (blocks row-major, tiles column by column inside a block — VR_XCD_MODE
 // below —, the ragged right / bottom margins after them): consecutive workgroups — which the hardware spreads over the eight XCDs — are screen neighbours.
@@ -399,6 +405,14 @@ hipError_t launch_composite_slab(const RayKernelArgs &a, const void *linear, con
                                  const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 hipError_t launch_composite_slab_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                                      const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
+
+// the backdrop frame (a.backdrop_on; include/vr_hip.h vr_hip_render_backdrop): launch_raymarch hands it over; the
+// family is chosen by a.slab_on and a.light_on — composite_backdrop / composite_backdrop_lit (vr_backdrop.hip), composite_backdrop_slab /
+// composite_backdrop_slab_lit (vr_backdrop_slab.hip).  out_rgba may be the colour layer.
+hipError_t launch_composite_backdrop(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                     const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
+hipError_t launch_composite_backdrop_slab(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
+                                          const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);

@@ -115,6 +115,11 @@ struct vr_ctx {
 	// preint_frames counts them (vr_hip_preint_frames).  The integral table K lies behind the 128 entries of `tf` on the device.
 	bool preint_on = false;
 	uint64_t preint_frames = 0;
+	// backdrop frames (vr_hip_render_backdrop / vr_hip_render_hybrid): backdrop_frames counts the composite frames on the composite_backdrop*
+	// kernels; the hybrid's depth buffer when the caller gives none and the staging of the host entry points' layers, grown on demand
+	uint64_t backdrop_frames = 0;
+	float *hybrid_depth = nullptr; size_t hybrid_depth_bytes = 0;
+	void *backdrop_stage = nullptr; size_t backdrop_stage_bytes = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -559,7 +564,8 @@ int launch_timed(vr_ctx *c, RayKernelArgs &a, const vr_params *p, const Raymarch
 
 int build_shadow(vr_ctx *c);
 
-int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+// bd: the opaque layer of a backdrop frame (vr_hip_render_backdrop_device; device addresses), or NULL
+int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream, const vr_backdrop *bd = nullptr) {
 	// A shadowed frame (vr_hip_set_shadow): the light grid first, on the context's stream and synchronous like a brick copy's first use
 	const bool shadow = c->shadow_on;
 	if (shadow) {
@@ -578,9 +584,13 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	if (preint && p->sampling == VR_SAMPLE_NEAREST)
 		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab lies between two samples of the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
 		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_preintegration(ctx, 0) switches it off)");
+	// A backdrop frame (vr_hip_render_backdrop) reads what a clipped frame reads as well; clip, shadow, lighting and pre-integration compose with it
+	if (bd != nullptr && p->sampling == VR_SAMPLE_NEAREST)
+		return fail(c, VR_ERR_INVALID, "a backdrop frame is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
 	RayKernelArgs a;
 	volume_args(c, p, a);
 	if (preint) a.slab_on = 1u;
+	if (bd != nullptr) { a.backdrop_on = 1u; a.backdrop_rgba = (uint64_t) (uintptr_t) bd->rgba; a.backdrop_depth = (uint64_t) (uintptr_t) bd->depth; }
 	if (lighting) {
 		a.light_on = 1u; a.light_ka = c->lighting.ambient; a.light_kd = c->lighting.diffuse; a.light_ks = c->lighting.specular;
 		a.light_n = c->lighting.shininess_log2;
@@ -631,7 +641,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	}
 	a.force_wide = c->force_wide;
 	// (a shadowed frame reads what a clipped frame reads: its kernels are the clipped ones with one more fetch per dense sample)
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting || preint;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting || preint || bd != nullptr;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
 	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
@@ -677,7 +687,9 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	esl_divisor(a, p->esl_block_dims);
 
 	vr_ctx::MapEntry *hit = nullptr;
+	uint32_t uncached_straddle = 1000u;
 	if (c->tile_lane_map >= 0) { a.lane_map = (uint32_t) c->tile_lane_map; a.phase_x = c->tile_phase_x; a.phase_y = c->tile_phase_y; }
+	else if (bd != nullptr) uncached_straddle = choose_tile_mapping(a);      // a backdrop frame leaves the cached mappings alone: they are keyed by vr_params, and it reads other copies
 	else {
 		for (uint32_t i = 0; i < c->map_cached && hit == nullptr; i++)
 			if (memcmp(&c->map_cache[i].p, p, sizeof *p) == 0 && memcmp(c->map_cache[i].dim, c->dim, sizeof c->dim) == 0) hit = &c->map_cache[i];
@@ -821,7 +833,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	TileSchedule sched;
 	vr_ctx::SchedSlot *read_slot = nullptr, *record_slot = nullptr;
 	vr_ctx::OrderEntry *oe = nullptr;
-	if (c->tile_scheduling == 1 && c->tile_lane_map < 0 && (VR_ORDER_ALWAYS || p->esl || p->ray_threshold < 1.0f) && ntiles >= 64 && ntiles <= (1u << 20)) {
+	// (not a backdrop frame: the layer changes per frame and the recorded orders are keyed by vr_params — its tiles start in grid order)
+	if (c->tile_scheduling == 1 && c->tile_lane_map < 0 && bd == nullptr && (VR_ORDER_ALWAYS || p->esl || p->ray_threshold < 1.0f) && ntiles >= 64 && ntiles <= (1u << 20)) {
 		advance_completed(c);
 		vr_ctx::OrderKey key;
 		memset(&key, 0, sizeof key);
@@ -951,7 +964,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// (the TRILINEAR column march over the voxel windows reports layout 7, the column march, and column_voxels = 1; column_shade_pairs = 1
 	// when it shades from the quad-element windows)
 	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
-	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : 1000u,
+	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : uncached_straddle,
 	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u, shadow ? 1u : 0u };
 
 	uint64_t frame_seq = 0;
@@ -959,6 +972,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	if (rc) return rc;
 	if (lighting) c->lit_frames++;
 	if (preint) c->preint_frames++;
+	if (bd != nullptr) c->backdrop_frames++;
 	if (dual_advance) {                          // behind the frame, on its stream
 		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
 		VR_TRY(c, hipEventRecord(hit->order_ready, stream));
@@ -1268,6 +1282,37 @@ int render_preamble(vr_ctx *c, const vr_params *p, const void *buffer, bool host
 	return VR_OK;
 }
 
+// what the two backdrop entry points check beyond render_preamble
+int validate_backdrop(vr_ctx *c, const vr_params *p, const vr_backdrop *bd) {
+	if (bd == nullptr) return fail(c, VR_ERR_INVALID, "backdrop is NULL");
+	if (bd->rgba == nullptr || bd->depth == nullptr) return fail(c, VR_ERR_INVALID, "backdrop rgba / depth is NULL");
+	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
+		return fail(c, VR_ERR_INVALID, "a backdrop frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	return VR_OK;
+}
+
+// a context-owned device buffer of at least `bytes`: allocated on first use and grown (behind the context's frames, one of which may
+// still read the old one), never per frame
+int grow_buffer(vr_ctx *c, void **buffer, size_t &have, size_t bytes) {
+	if (have >= bytes) return VR_OK;
+	VR_TRY(c, drain(c));
+	if (*buffer) { (void) hipFree(*buffer); *buffer = nullptr; have = 0; }
+	VR_TRY(c, hipMalloc(buffer, bytes));
+	have = bytes;
+	return VR_OK;
+}
+
+// The hybrid (include/vr_hip.h): the isosurface frame into dev_rgba and the depth buffer, then the backdrop frame in place, on one stream
+int launch_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	if (dev_depth == nullptr) {
+		if (const int rc = grow_buffer(c, (void **) &c->hybrid_depth, c->hybrid_depth_bytes, (size_t) p->out_width * p->out_rows * sizeof(float))) return rc;
+		dev_depth = c->hybrid_depth;
+	}
+	if (const int rc = launch_iso_frame(c, p, iso, dev_rgba, dev_depth, stream)) return rc;
+	const vr_backdrop layer = { dev_rgba, dev_depth };
+	return launch_frame(c, p, dev_rgba, stream, &layer);
+}
+
 // ... and what the two host-buffer ones end with: the frame in host memory (where the reference's timed region ends, GPURenderer1.cu:107-110)
 // and the time since t0
 void take_total_time(vr_ctx *c, std::chrono::steady_clock::time_point t0) {
@@ -1343,6 +1388,8 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->minmax) (void) hipFree(c->minmax);
 	if (c->mip_bounds) (void) hipFree(c->mip_bounds);
 	if (c->iso_depth) (void) hipFree(c->iso_depth);
+	if (c->hybrid_depth) (void) hipFree(c->hybrid_depth);
+	if (c->backdrop_stage) (void) hipFree(c->backdrop_stage);
 	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
@@ -1711,6 +1758,57 @@ int vr_hip_render_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t 
 	if (rc) return rc;
 	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->iso_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+
+// ---- backdrop and hybrid frames (include/vr_hip.h vr_backdrop) ----
+
+int vr_hip_render_backdrop_device(vr_ctx *c, const vr_params *p, const vr_backdrop *dev, void *dev_rgba, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_backdrop(c, p, dev)) return rc;
+	return launch_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream, dev);
+}
+
+int vr_hip_render_backdrop(vr_ctx *c, const vr_params *p, const vr_backdrop *host, uint8_t *host_rgba) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_backdrop(c, p, host);
+	if (rc) return rc;
+	// the two layers are two caller-owned arrays: one upload each (one upload of both would need a host copy of our own first) into ONE
+	// context-owned staging buffer, colour first, on the frame's stream
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	if (const int grow = grow_buffer(c, &c->backdrop_stage, c->backdrop_stage_bytes, pixels * 8)) return grow;
+	const auto t0 = std::chrono::steady_clock::now();
+	VR_TRY(c, hipMemcpyAsync(c->backdrop_stage, host->rgba, pixels * 4, hipMemcpyHostToDevice, c->stream));
+	VR_TRY(c, hipMemcpyAsync((uint8_t *) c->backdrop_stage + pixels * 4, host->depth, pixels * 4, hipMemcpyHostToDevice, c->stream));
+	const vr_backdrop dev = { c->backdrop_stage, (uint8_t *) c->backdrop_stage + pixels * 4 };
+	rc = launch_frame(c, p, c->fb, c->stream, &dev);
+	if (rc) return rc;
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+
+int vr_hip_render_hybrid_device(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_iso(c, p, iso)) return rc;
+	return launch_hybrid(c, p, iso, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t *host_rgba, float *host_depth) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_iso(c, p, iso);
+	if (rc) return rc;
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_hybrid(c, p, iso, c->fb, nullptr, c->stream);       // (the context's own depth buffer)
+	if (rc) return rc;
+	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->hybrid_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+
+int vr_hip_backdrop_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->backdrop_frames;
+	return VR_OK;
 }
 
 #ifdef VR_MIP_STATS

@@ -14,7 +14,7 @@ void composite_lit(const RayKernelArgs a, const void *__restrict__ vol, const fl
                    const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                    const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a gradient-lit frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = true, SLAB = false;
+	constexpr bool CLIP = true, SHADOW = false, LIT = true, SLAB = false, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 

@@ -801,6 +801,33 @@ __device__ __forceinline__ bool lit_frame_shadowed() {
 	return a->shadow_on != 0u;
 }
 
+// -- the opaque layer of a backdrop frame (include/vr_hip.h vr_backdrop), for the composite_backdrop* kernels alone: the
+//    depth and the colour word of element `px` (= ly * out_width + lx, the layout of the output buffer).  The two addresses come through the
+//    laundered kernel-argument pointer, as in clip_segment, so nothing of the layer occupies a scalar register across the march; they are
+//    addresses, not __restrict__ pointers, and the output pointer of those kernels carries no __restrict__ either: the output may be the
+//    colour layer.  A pixel reads its own elements before it stores its own output element, so in-place frames are well defined.
+__device__ __forceinline__ float backdrop_depth_at(size_t px) {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	return ((const float *) (uintptr_t) a->backdrop_depth)[px];
+}
+__device__ __forceinline__ uint32_t backdrop_rgba_at(size_t px) {
+	typedef const RayKernelArgs __attribute__((address_space(4))) *ConstArgs;
+	ConstArgs a = (ConstArgs) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(a));
+	return ((const uint32_t *) (uintptr_t) a->backdrop_rgba)[px];
+}
+// ... and the output address of element px: the kernels' arguments are (RayKernelArgs, vol, tf, esl, out, ...), so the output pointer lies
+// three pointers behind the first argument in the kernel-argument segment — read again there, behind the march, instead of kept across it
+struct RayKernelSegment { RayKernelArgs a; const void *vol; const float *tf; const uint32_t *esl; uint32_t *out; };
+__device__ __forceinline__ uint32_t *backdrop_out_at(size_t px) {
+	typedef const RayKernelSegment __attribute__((address_space(4))) *ConstSegment;
+	ConstSegment s = (ConstSegment) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(s));
+	return s->out + px;
+}
+
 // -- the address tables of the quad / voxel / oct bricks into LDS; no barrier.  Entry j of a table belongs to cell
 //    clamp(j - kLutPad, 0, dim - 1): the pad entries repeat the edge cells.
 __device__ __forceinline__ uint32_t lut_cell_of(uint32_t j, uint32_t n) { const int c = (int) j - kLutPad; return (uint32_t) (c < 0 ? 0 : (c > (int) n - 1 ? (int) n - 1 : c)); }

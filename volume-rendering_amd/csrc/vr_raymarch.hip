@@ -15,7 +15,7 @@ __global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)
 void raymarch_kernel(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
                      const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                      const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	constexpr bool CLIP = false, SHADOW = false, LIT = false, SLAB = false;
+	constexpr bool CLIP = false, SHADOW = false, LIT = false, SLAB = false, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 // ... of a clipped frame (vr_hip_set_clip): the linear array, the quad, voxel and oct bricks — never a run copy (launch_frame).  Its own
@@ -26,7 +26,7 @@ void raymarch_clipped(const RayKernelArgs a, const void *__restrict__ vol, const
                       const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                       const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT), "a clipped frame never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = false;
+	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = false, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 
@@ -52,6 +52,9 @@ hipError_t launch_raymarch(const RayKernelArgs &args, const void *linear, const 
                            const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
 	if (bricked != nullptr && (args.layout == kLayoutColumn || args.layout == kLayoutVoxCol))      // orthogonal view along args.col_axis, full march, 1-byte voxels (launch_frame)
 		return launch_colmarch(args, bricked, tf, out, stream);
+	if (args.backdrop_on)                                        // a frame over an opaque layer (vr_hip_render_backdrop), whatever else is set: kernels of its own, in vr_backdrop.hip and vr_backdrop_slab.hip
+		return args.slab_on ? launch_composite_backdrop_slab(args, linear, bricked, bpv, tf, esl, out, sched, stream)
+		                    : launch_composite_backdrop(args, linear, bricked, bpv, tf, esl, out, sched, stream);
 	if (args.slab_on)                                            // a pre-integrated frame (vr_hip_set_preintegration), clipped, shadowed, lit or not: kernels of its own, in vr_slab.hip
 		return args.light_on ? launch_composite_slab_lit(args, linear, bricked, bpv, tf, esl, out, sched, stream)
 		                     : launch_composite_slab(args, linear, bricked, bpv, tf, esl, out, sched, stream);

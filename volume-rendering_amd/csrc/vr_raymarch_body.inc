@@ -1,6 +1,7 @@
 // vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
-// `constexpr bool CLIP`, `SHADOW`, `LIT` and `SLAB` set), of raymarch_shadowed (vr_shadow.hip), of composite_lit (vr_light.hip) and of
-// composite_slab and composite_slab_lit (vr_slab.hip): a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
+// `constexpr bool CLIP`, `SHADOW`, `LIT`, `SLAB` and `BACKDROP` set), of raymarch_shadowed (vr_shadow.hip), of composite_lit (vr_light.hip), of
+// composite_slab and composite_slab_lit (vr_slab.hip) and of the four composite_backdrop* kernels (vr_backdrop.hip, vr_backdrop_slab.hip):
+// a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
 	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live
@@ -93,7 +94,11 @@
 	if (lx >= a.p.out_width || ly >= a.p.out_rows)
 		return;                                     // no barrier below this point
 	const uint32_t lane = threadIdx.x & 63u;
-	uint32_t *out_px = out + (size_t) ly * a.p.out_width + lx;
+	// BACKDROP: the pixel's element index alone crosses the march (one register; out_width * out_rows < 2^32) — the output address and the
+	// layer's are formed from it behind the march, from addresses read again in the kernel-argument segment
+	uint32_t *out_px = BACKDROP ? nullptr : out + (size_t) ly * a.p.out_width + lx;
+	uint32_t pixel = 0;
+	if constexpr (BACKDROP) { pixel = ly * a.p.out_width + lx; asm volatile("" : "+v"(pixel)); }
 
 	const PixelRay ray = pixel_ray(a, a.p.x0 + lx, frame_row(a, ly));
 	f3 origin = ray.origin, dir = ray.dir;
@@ -101,6 +106,15 @@
 	const float step = a.p.ray_step;
 	bool alive = ray.alive;
 	if constexpr (CLIP) alive = clip_segment(origin, dir, kx, ky) && alive;
+	// BACKDROP (vr_hip_render_backdrop, DESIGN.md section 4.11): the ray stops at the depth of the opaque layer — k of the pixel's own ray;
+	// negative or NaN = no surface (an ordered compare).  Only the narrowed ky crosses the march: the layer is read again behind it.
+	if constexpr (BACKDROP) {
+		const float d = backdrop_depth_at(pixel);
+		if (d >= 0.0f) {
+			ky = flmin(ky, d);
+			alive = alive && (kx < ky) && (ky > 0);
+		}
+	}
 	const bool hit = alive;
 	f3 pt = march_point<SAMPLING>(origin, dir, kx);
 
@@ -331,7 +345,8 @@
 			// a gradient-lit frame likewise: one or two gradient fetches are in flight inside its dense block; a slab frame likewise: the previous
 			// sample's coordinate crosses the march and a wide slab holds two integrals beside the colour)
 			constexpr int kFullDepth = is_run_layout(LAYOUT) ? kRunDepth : (!kFourWordSlots ? vr::kDepth : (vr::kDepth > kDepthTwoByte ? kDepthTwoByte : vr::kDepth));
-			constexpr int kDepth = (SHADOW || LIT || SLAB) && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
+			// (a backdrop frame likewise: its base family carries the shadow's factor fetch behind a kernel argument, the others are lit or slab frames)
+			constexpr int kDepth = (SHADOW || LIT || SLAB || BACKDROP) && kFullDepth > 1 ? kFullDepth - 1 : kFullDepth, kSlots = kDepth + 1;
 			TriFetch<BPV, LAYOUT> f[kSlots]; float ks[kSlots];
 			ks[0] = kx;
 			// SLAB: the clamped transfer-function coordinate of the previous sample of this loop; below 0 = there is none yet (the first
@@ -503,7 +518,7 @@
 							}
 						}
 					}
-					if constexpr (SLAB && !LIT) {                                                      // a slab frame takes the shadow as composite_lit does: a kernel argument, wave-uniform
+					if constexpr ((SLAB || BACKDROP) && !LIT) {                                        // a slab frame and a backdrop frame take the shadow as composite_lit does: a kernel argument, wave-uniform
 						if (lit_frame_shadowed()) {
 							const uint64_t dense = __builtin_amdgcn_fcmpf(c.w, 0.05f, kFcmpOGT) & live;
 							if (dense != 0ull) {
@@ -555,6 +570,19 @@
 	if (hit && visible) {
 		rgba = map_float_int(acc.x, 256) | (map_float_int(acc.y, 256) << 8) |
 		       (map_float_int(acc.z, 256) << 16) | (map_float_int(acc.w, 256) << 24);
+	}
+	if constexpr (BACKDROP) {
+		// a pixel with a surface: the layer's colour word bit for bit where nothing was composited, else the accumulated colour over it
+		const size_t px = pixel;
+		out_px = backdrop_out_at(px);
+		if (backdrop_depth_at(px) >= 0.0f) {
+			const uint32_t b = backdrop_rgba_at(px);
+			if (hit && visible) {
+				const float t = 1.0f - acc.w;
+				auto over = [&](uint32_t byte, float c) { return map_float_int(VR_FMA(((float) byte + 0.5f) * (1.0f / 256.0f), t, c), 256); };
+				rgba = over(b & 0xffu, acc.x) | (over((b >> 8) & 0xffu, acc.y) << 8) | (over((b >> 16) & 0xffu, acc.z) << 16) | (over(b >> 24, acc.w) << 24);
+			} else rgba = b;
+		}
 	}
 	*out_px = rgba;
 	// cost of the tile = the end of its last wave after the start of the workgroup, in 64-cycle units (at least 1); every wave

@@ -100,7 +100,7 @@ void raymarch_shadowed(const RayKernelArgs a, const void *__restrict__ vol, cons
                        const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                        const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a shadowed frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = true, LIT = false, SLAB = false;
+	constexpr bool CLIP = true, SHADOW = true, LIT = false, SLAB = false, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 

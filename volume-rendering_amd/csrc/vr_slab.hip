@@ -14,7 +14,7 @@ void composite_slab(const RayKernelArgs a, const void *__restrict__ vol, const f
                     const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                     const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a slab frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = true;
+	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = true, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 // ... with the gradient lighting (vr_hip_set_lighting) in place of the cue
@@ -24,7 +24,7 @@ void composite_slab_lit(const RayKernelArgs a, const void *__restrict__ vol, con
                         const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
                         const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
 	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a slab frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = true, SLAB = true;
+	constexpr bool CLIP = true, SHADOW = false, LIT = true, SLAB = true, BACKDROP = false;
 #include "vr_raymarch_body.inc"
 }
 

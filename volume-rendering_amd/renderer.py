@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_shadow
+from .binding import VrBackdrop, VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_shadow
 
 
 class HipRenderer:
@@ -258,6 +258,54 @@ class HipRenderer:
         iso = VrIso(float(level), int(refine))
         self._check(self._L.vr_hip_render_iso_device(self._ctx, C.byref(params), C.byref(iso), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
                                                      C.c_void_p(stream) if stream else None), "render_iso_device")
+
+    # -- backdrop and hybrid (vr_hip_render_backdrop / vr_hip_render_hybrid: a composite frame that stops at an opaque layer and blends over it)
+    def render_backdrop(self, params, rgba, depth):
+        """Host-buffer flavour: the composite frame (with the context's clip, shadow, lighting and pre-integration) over the opaque layer
+        `rgba` ((out_rows, out_width, 4) uint8, premultiplied) at `depth` ((out_rows, out_width) float32: k of the pixel's own ray, the
+        isosurface frame's depth; negative or NaN = no surface, +inf = behind everything).  Returns an (out_rows, out_width, 4) uint8 array.
+        params.sampling must be one of the TRILINEAR modes."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if rgba.size != params.out_rows * params.out_width * 4 or depth.size != params.out_rows * params.out_width:
+            raise ValueError("render_backdrop: the layers must have out_rows * out_width pixels")
+        layer = VrBackdrop(rgba.ctypes.data, depth.ctypes.data)
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_backdrop(self._ctx, C.byref(params), C.byref(layer), out.ctypes.data), "render_backdrop")
+        return out
+
+    def render_backdrop_device(self, params, rgba_ptr, depth_ptr, dev_ptr, stream=None):
+        """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None); the layers are device addresses,
+        and `dev_ptr` may be `rgba_ptr` (in place)."""
+        layer = VrBackdrop(rgba_ptr or None, depth_ptr or None)
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_backdrop_device(self._ctx, C.byref(params), C.byref(layer), C.c_void_p(dev_ptr),
+                                                          C.c_void_p(stream) if stream else None), "render_backdrop_device")
+
+    def render_hybrid(self, params, level, refine=4, depth=False):
+        """Host-buffer flavour of the hybrid: the isosurface of `level` (render_iso with the same arguments) seen through the translucent
+        volume in front of it.  An (out_rows, out_width, 4) uint8 array, or with depth=True (rgba, depth): the isosurface's depth."""
+        iso = VrIso(float(level), int(refine))
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_hybrid(self._ctx, C.byref(params), C.byref(iso), out.ctypes.data, dep.ctypes.data if depth else None), "render_hybrid")
+        return (out, dep) if depth else out
+
+    def render_hybrid_device(self, params, level, refine, dev_ptr, depth_ptr=None, stream=None):
+        """Device-buffer flavour: the isosurface frame into `dev_ptr` and `depth_ptr` (a context-owned buffer when None), then the backdrop
+        frame in place, both on `stream` (raw hipStream_t or None)."""
+        iso = VrIso(float(level), int(refine))
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_hybrid_device(self._ctx, C.byref(params), C.byref(iso), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
+                                                        C.c_void_p(stream) if stream else None), "render_hybrid_device")
+
+    def backdrop_frames(self):
+        """vr_hip_backdrop_frames: the composite frames this context launched on the backdrop kernels"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_backdrop_frames(self._ctx, C.byref(n)), "backdrop_frames")
+        return int(n.value)
 
     # -- timing (Profiler.cpp:46-67)
     def timing(self):
