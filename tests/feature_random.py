@@ -3,7 +3,9 @@ the MIP, the isosurface, the clip region, the light grid with its shadowed frame
 those of tests/test_gpu_random.py (odd extents, one extent forced to 1 / 2 / 8 / 16 / 33, cameras inside the cube, exact zeros in the
 direction, the four-fold ray step); this module adds a clip, a light, a grid size, a lighting and an isosurface level per frame, and the
 hand-made EDGE_SHAPES.  Everything is drawn from numpy generators seeded from VR_TEST_SEED (default 20261019), one per list of frames, so
-that both tiers see the same frames whatever the order of the tests.  A plain module: no fixtures."""
+that both tiers see the same frames whatever the order of the tests.  The slab, backdrop and hybrid frames (ExpectedLayers) reuse those
+frames as they are — nothing more is drawn from the scene generators — and take their depth layers from backdrop_helpers.synthetic_layer
+under salts of 2000 and above.  A plain module: no fixtures."""
 import os
 
 import numpy as np
@@ -179,6 +181,51 @@ def random_scenes(oracle, vr, stream=0, scenes=SCENES, frames=FRAMES_PER_SCENE):
     return _lists[key]
 
 
+HOLED_STREAM, HOLED_SCENES, HOLED_FRAMES = 7, 6, 4
+
+
+def holed_scenes(oracle, vr):
+    """Scenes for the pre-integration's skipped samples, from a generator stream of their own (the frames of random_scenes stay what they
+    are).  The random volumes are smooth: between two consecutive samples the value hardly ever jumps from what a wave may skip — below the
+    largest power of two inside the transfer function's leading zeros — to what shows, so a sample behind a skipped one contributes
+    nothing there.  Here a slab of exact zeros, a third to a half of the volume thick, is cut through a random volume of 12 to 39
+    voxels per axis, and the random transfer function has at least its first entry zero: whole waves skip inside the slab, and the
+    first sample behind it needs the coordinate of a skipped predecessor.  Frames are redrawn until they are 16 pixels or more a side."""
+    key = ("holed",)
+    if key not in _lists:
+        rng = generator(HOLED_STREAM)
+        out = []
+        while len(out) < HOLED_SCENES:
+            vox = random_scene(rng, oracle, vr)[0]
+            if min(vox.shape) < 12:
+                continue
+            vox = np.array(vox)
+            axis = int(rng.integers(0, 3))
+            n = vox.shape[axis]
+            thick = int(rng.integers(n // 3, n // 2 + 1))
+            lo = int(rng.integers(2, n - thick - 1))
+            cut = [slice(None)] * 3
+            cut[axis] = slice(lo, lo + thick)
+            vox[tuple(cut)] = 0
+            vox = np.ascontiguousarray(vox)
+            vox.setflags(write=False)
+            base = rng.random((128, 4)).astype(np.float32)
+            base[:, 3] *= (rng.random(128) < 0.7)
+            base[: int(rng.integers(1, 40)), 3] = 0
+            tf, esl, bd, bs, ray_step = oracle.scene_for(vox, base)
+            i = len(out)
+            s = Scene(name=f"holed scene {i}", vox=vox, tf=tf, esl=esl, bd=bd, bs=bs, ray_step=ray_step,
+                      layout=vr.LAYOUT_BRICKED if i % 2 else vr.LAYOUT_LINEAR, wide=WIDE[i % len(WIDE)])
+            s.frames = []
+            while len(s.frames) < HOLED_FRAMES:
+                f = random_frame(rng, vr, s)
+                if min(f.p.view.width, f.p.view.height) >= 16:       # two waves a side at the least: it is whole waves that skip
+                    s.frames.append(f)
+            out.append(s)
+        _lists[key] = out
+    return _lists[key]
+
+
 def edge_volume(shape_xyz, dtype):
     """a deterministic field that is nowhere constant: non-zero gradients and values either side of 128 on every shape of EDGE_SHAPES"""
     x, y, z = shape_xyz
@@ -238,3 +285,37 @@ class Expected:
         self.q = shadow_ref.build(f.light, f.S, f.shadow_step, v, tf, CUTOFF, f.shadow_sampling, clip=f.clip)
         self.shadowed = shadow_ref.render(f.p, v, tf, esl, self.q, f.strength, f.clip)
         self.lit, self.dense, self.flat = light_ref.render(f.p, v, tf, esl, f.lighting, self.q, f.strength, clip=f.clip, counters=True)
+
+
+def layer_salt(scene_index, frame_index):
+    """the salt of a random frame's synthetic layer (backdrop_helpers.synthetic_layer); the tests of the two feature files stay below 1000"""
+    return 2000 + 8 * scene_index + frame_index
+
+
+EDGE_SALT = 3000                                     # the layers of the edge shapes: EDGE_SALT + 8 * (2 * shape + dtype) + frame
+
+
+class ExpectedLayers:
+    """The restatements' answers for the slab, backdrop and hybrid frames of one (scene, frame), beside Expected so that the tests of the
+    older features do not pay for them: tests/slab_ref.c and tests/backdrop_ref.c under the frame's clip, point classified with the cue
+    and — `*_all` — slab classified under the frame's lighting, light grid and strength.  The synthetic layer comes from
+    backdrop_helpers.synthetic_layer, which has its own generator stream: the frames draw nothing for it."""
+
+    def __init__(self, scene, f, salt=None):
+        """salt None: the hybrid frames alone (they take no layer)"""
+        from backdrop_helpers import BackdropRef, synthetic_layer
+        from shadow_helpers import CUTOFF, ShadowRef
+        from slab_helpers import POINT, SLAB, SlabRef
+        v, tf, esl = scene.vox, scene.tf, scene.esl
+        slab_ref, ref = SlabRef.instance(), BackdropRef.instance()
+        self.q = ShadowRef.instance().build(f.light, f.S, f.shadow_step, v, tf, CUTOFF, f.shadow_sampling, clip=f.clip)
+        states = (SLAB, f.clip, f.lighting, self.q, f.strength)
+        self.hybrid, self.hybrid_depth, self.hybrid_iso = ref.hybrid(f.p, v, tf, esl, f.level, f.refine, POINT, f.clip)
+        self.hybrid_all = ref.hybrid(f.p, v, tf, esl, f.level, f.refine, *states)[0]
+        if salt is None:
+            return
+        self.slab, self.samples, self.wide, self.narrow = slab_ref.render(f.p, v, tf, esl, SLAB, f.clip, counters=True)
+        self.slab_all = slab_ref.render(f.p, v, tf, esl, *states)
+        self.rgba, self.depth = synthetic_layer(ref, f.p, v, tf, esl, f.clip, salt=salt)
+        self.backdrop = ref.render(f.p, v, tf, esl, self.rgba, self.depth, POINT, f.clip)
+        self.backdrop_all = ref.render(f.p, v, tf, esl, self.rgba, self.depth, *states)

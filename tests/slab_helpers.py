@@ -13,7 +13,7 @@ from helpers import axis_view
 from light_helpers import lit_views, lit_volumes
 from mip_helpers import compile_test_library, ramp_tf
 
-POINT, SLAB, SLAB_DOUBLE = 0, 1, 2                  # the `mode` of slab_render
+POINT, SLAB, SLAB_DOUBLE, SLAB_SKIPPED_IS_NONE = 0, 1, 2, 3      # the `mode` of slab_render; the last is a wrong reading (sensitivity)
 # what the GPU tier renders; on the plateau whole waves skip the empty samples in front of the block, and the first block sample needs the
 # coordinate of a skipped one; on the ramp volume a peak three entries wide lies between consecutive samples
 SLAB_VOLUMES = ("bucky", "blob_40x24x56", "random_u16", "plateau", "ramp")
@@ -109,7 +109,7 @@ class SlabRef:
 
     def render(self, params, voxels, tf, esl, mode=SLAB, clip=IDENTITY, lighting=None, q=None, strength=1.0, counters=False):
         """the composite frame (TRILINEAR modes) under `clip`, with the reference's cue (lighting None) or lit by `lighting` = (ambient,
-        diffuse, specular, shininess_log2), scaled by the light grid q (None: no shadow); mode POINT / SLAB / SLAB_DOUBLE.
+        diffuse, specular, shininess_log2), scaled by the light grid q (None: no shadow); mode POINT / SLAB / SLAB_DOUBLE / SLAB_SKIPPED_IS_NONE.
         counters=True: (frame, samples of the accumulation loop, wide-slab samples, narrow-slab samples)"""
         assert params.x0 == 0 and params.out_width == params.view.width and params.out_rows == params.view.height and params.band_stride == 1
         vox = voxels if voxels.flags["C_CONTIGUOUS"] else np.ascontiguousarray(voxels)

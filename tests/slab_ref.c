@@ -11,7 +11,10 @@
  *
  * Whole frames only (pixel (x, y) of the view -> out[y * out_width + x]).  lighting NULL = the reference's cue (light_kd); q NULL = no
  * shadow.  mode: 0 = point classification, 1 = slab classification, 2 = slab classification with the wide-slab branch in double
- * precision (K, K(t), the difference and the division; rounded to fp32 once) — what the fp32 branch is held against.
+ * precision (K, K(t), the difference and the division; rounded to fp32 once) — what the fp32 branch is held against; 3 = a wrong reading for
+ * the sensitivity tests: a sample that the library may skip without resolving it — its value below the largest power of two P whose
+ * coordinate lies within the transfer function's leading zeros, behind a predecessor within them too — counts as no predecessor at all
+ * for the next sample (tp = tb), instead of handing its coordinate on.  Per ray: what a wave of the library skips is a subset of it.
  * counters_out[3]: samples of the accumulation loop, those that took the wide-slab branch, those that took the narrow one.
  */
 #include "light_ref.c"
@@ -68,8 +71,8 @@ static f4 slab_lookup(const scene *s, float t) {
 }
 
 static void slab_render_ray(const scene *s, const float *K, const double *Kd, const float *clip, const float *lighting, uint32_t shin,
-                            const uint8_t *q, uint32_t S, float strength, uint32_t mode, int px, int py, uint8_t *out_px,
-                            uint64_t *samples, uint64_t *wide, uint64_t *narrow) {
+                            const uint8_t *q, uint32_t S, float strength, uint32_t mode, float skip_below, float zero_below, int px, int py,
+                            uint8_t *out_px, uint64_t *samples, uint64_t *wide, uint64_t *narrow) {
 	const vr_params *p = s->p;
 	f3 origin, direction;
 	float kx, ky;
@@ -96,7 +99,7 @@ static void slab_render_ray(const scene *s, const float *K, const double *Kd, co
 	const f3 light_pos = f3_make(p->view.light_pos[0], p->view.light_pos[1], p->view.light_pos[2]);
 	const float tf_scale = s->bpv == 1 ? (float) VR_TF_SIZE / 255.0f : (float) VR_TF_SIZE / 65535.0f;
 	const float *tf = (const float *) s->tf;
-	int first = 1;
+	int first = 1, skipped = 0;
 	float tp = 0.0f;
 	while (kx <= ky) {
 		const float xb = fmaf(kx, A.x, B.x), yb = fmaf(kx, A.y, B.y), zb = fmaf(kx, A.z, B.z);
@@ -110,6 +113,10 @@ static void slab_render_ray(const scene *s, const float *K, const double *Kd, co
 			tb = tb < 0.0f ? 0.0f : (tb > SLAB_TF_MAX ? SLAB_TF_MAX : tb);          /* fmed3(.., 0, 127) for the finite coordinate of a frame */
 			if (first) tp = tb;                                                     /* the loop's first sample */
 			first = 0;
+			if (mode == 3) {                                                        /* the wrong reading: a skipped predecessor is none */
+				if (skipped) tp = tb;
+				skipped = raw < skip_below && tp <= zero_below;
+			}
 			const float d = tb - tp;
 			if (!(fabsf(d) >= 0.5f)) {                                              /* narrow slab: the lookup at its middle */
 				(*narrow)++;
@@ -189,7 +196,7 @@ static void slab_render_ray(const scene *s, const float *K, const double *Kd, co
 int slab_render(const vr_params *p, const void *voxels, const uint32_t dims[3], uint32_t bpv, const float *tf, const uint32_t *esl,
                 const float *clip, const float *lighting, uint32_t shin, const uint8_t *q, uint32_t S, float strength, uint32_t mode,
                 uint8_t *out, uint64_t *counters_out) {
-	if ((p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8) || mode > 2)
+	if ((p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8) || mode > 3)
 		return 1;
 	const scene s = scene_of(p, voxels, dims, bpv, tf, esl);
 	float K[4 * VR_TF_SIZE];
@@ -198,10 +205,18 @@ int slab_render(const vr_params *p, const void *voxels, const uint32_t dims[3], 
 	slab_build_integral_double(tf, Kd);
 	memset(out, 0, (size_t) p->out_width * p->out_rows * 4);
 	uint64_t samples = 0, wide = 0, narrow = 0;
+	/* mode 3: the leading all-zero entries of the transfer function and the bound on a skippable raw value, as the library forms them */
+	int zero = -1;
+	while (zero + 1 < VR_TF_SIZE && tf[4 * (zero + 1)] == 0.0f && tf[4 * (zero + 1) + 1] == 0.0f && tf[4 * (zero + 1) + 2] == 0.0f && tf[4 * (zero + 1) + 3] == 0.0f)
+		zero++;
+	const float tf_scale = bpv == 1 ? (float) VR_TF_SIZE / 255.0f : (float) VR_TF_SIZE / 65535.0f;
+	uint32_t below = 0;
+	for (uint32_t P = 1; P <= (bpv == 1 ? 256u : 65536u); P <<= 1)
+		if (zero >= 0 && fmaf((float) P, tf_scale, -0.5f) <= (float) zero) below = P;
 	#pragma omp parallel for schedule(dynamic, 4) reduction(+:samples, wide, narrow)
 	for (uint32_t y = 0; y < p->out_rows; y++)
 		for (uint32_t x = 0; x < p->out_width; x++)
-			slab_render_ray(&s, K, Kd, clip, lighting, shin, q, S, strength, mode, (int) x, (int) y, out + ((size_t) y * p->out_width + x) * 4,
+			slab_render_ray(&s, K, Kd, clip, lighting, shin, q, S, strength, mode, (float) below, (float) zero, (int) x, (int) y, out + ((size_t) y * p->out_width + x) * 4,
 			                &samples, &wide, &narrow);
 	counters_out[0] = samples; counters_out[1] = wide; counters_out[2] = narrow;
 	return 0;
