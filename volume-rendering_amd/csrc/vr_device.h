@@ -331,9 +331,19 @@ inline uint64_t bricked_elems(uint32_t dim_x, uint32_t dim_y, uint32_t dim_z) {
 
 // `linear` is the reference's array; `bricked` the brick copy RayKernelArgs::layout names (quad bricks of plane
 // brick_plane, or the run bricks) or NULL (VR_LAYOUT_LINEAR).
-hipError_t launch_raymarch(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
-                           const float *tf_premult /* 128 x float4 */, const uint32_t *esl_bits /* 1024 */,
-                           void *out_rgba, TileSchedule sched, hipStream_t stream);
+typedef hipError_t CompositeLauncher(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
+                                     const float *tf_premult /* 128 x float4 */, const uint32_t *esl_bits /* 1024 */,
+                                     void *out_rgba, TileSchedule sched, hipStream_t stream);
+CompositeLauncher launch_raymarch;
+// The feature frames launch_raymarch hands over, one launcher per kernel unit (the kernels of each are declared there through
+// vr_composite_family.inc); each refuses a frame that is not its own with hipErrorInvalidValue:
+//  * vr_shadow.hip: the shadowed frame (a.shadow_on; vr_hip_set_shadow), raymarch_shadowed;
+//  * vr_light.hip: the gradient-lit frame (a.light_on; vr_hip_set_lighting, section 4.8), composite_lit;
+//  * vr_slab.hip: the pre-integrated frame (a.slab_on; vr_hip_set_preintegration, section 4.10), composite_slab or, with a.light_on,
+//    composite_slab_lit.  tf_premult: the 128 entries and K behind them, here and in vr_backdrop_slab.hip;
+//  * vr_backdrop.hip (without a.slab_on) and vr_backdrop_slab.hip (with it): the backdrop frame (a.backdrop_on; vr_hip_render_backdrop,
+//    section 4.11), composite_backdrop / composite_backdrop_slab or, with a.light_on, their _lit kernels.  out_rgba may be the colour layer.
+CompositeLauncher launch_raymarch_shadowed, launch_composite_lit, launch_composite_slab, launch_composite_backdrop, launch_composite_backdrop_slab;
 // the column kernels' frame (a.layout kLayoutColumn / kLayoutVoxCol, `copy` = those column windows; a clipped frame is
 // hipErrorInvalidValue): launch_raymarch hands it over, vr_kernels.hip launches it
 hipError_t launch_colmarch(const RayKernelArgs &a, const void *copy, const float *tf_premult, void *out_rgba, hipStream_t stream);
@@ -390,29 +400,6 @@ struct ShadowBuildArgs {
 // a.p.sampling TRILINEAR — the copy a TRILINEAR MIP frame along z reads; the selector of launch_raymarch picks the addressing path.
 hipError_t launch_shadow_build(const RayKernelArgs &a, const ShadowBuildArgs &s, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
                                const float *tf_premult, uint8_t *q_out, hipStream_t stream);
-// the shadowed composite frame (a.shadow_on): launch_raymarch hands it over, vr_shadow.hip launches raymarch_shadowed
-hipError_t launch_raymarch_shadowed(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                    const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
-
-// the gradient-lit composite frame (a.light_on; include/vr_hip.h vr_hip_set_lighting): launch_raymarch hands it over,
-// vr_light.hip launches composite_lit
-hipError_t launch_composite_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
-
-// the pre-integrated composite frame (a.slab_on; include/vr_hip.h vr_hip_set_preintegration): launch_raymarch hands
-// it over, vr_slab.hip launches composite_slab or, with a.light_on, composite_slab_lit.  tf_premult: the 128 entries and K behind them.
-hipError_t launch_composite_slab(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                 const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
-hipError_t launch_composite_slab_lit(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                     const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
-
-// the backdrop frame (a.backdrop_on; include/vr_hip.h vr_hip_render_backdrop): launch_raymarch hands it over; the
-// family is chosen by a.slab_on and a.light_on — composite_backdrop / composite_backdrop_lit (vr_backdrop.hip), composite_backdrop_slab /
-// composite_backdrop_slab_lit (vr_backdrop_slab.hip).  out_rgba may be the colour layer.
-hipError_t launch_composite_backdrop(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                     const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
-hipError_t launch_composite_backdrop_slab(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
-                                          const uint32_t *esl_bits, void *out_rgba, TileSchedule sched, hipStream_t stream);
 
 hipError_t launch_histogram(const void *volume, uint32_t bytes_per_voxel, uint64_t voxels,
                             unsigned long long *hist256_dev, hipStream_t stream);

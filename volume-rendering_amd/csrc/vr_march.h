@@ -934,4 +934,47 @@ inline void tile_grid(uint32_t out_width, uint32_t out_rows, uint32_t phase_x, u
 	tiles_y = (out_rows + phase_y + threads / 32u - 1u) / (threads / 32u);
 }
 
+// A row of select_variant's table as a value, for the callables of launch_tiles; VR_ROW_KERNEL(kernel, row) is the kernel template's instantiation for it
+template <int SAMPLING, int BPV, int ADDR, int LAYOUT> struct VariantRow { static constexpr int sampling = SAMPLING, bpv = BPV, addr = ADDR, layout = LAYOUT; };
+#define VR_ROW_KERNEL(kernel, row) kernel<decltype(row)::sampling, decltype(row)::bpv, decltype(row)::addr, decltype(row)::layout>
+// Which rows a kernel family is instantiated for.  No run copy: a clipped composite frame and a MIP frame (launch_frame asks for none).
+// The interpolated field from the copies a TRILINEAR MIP frame reads — never NEAREST, the run bricks or the voxel bricks: an isosurface
+// frame and the shadowed, lit, slab and backdrop composite frames.
+constexpr bool rows_all(int, int, int, int) { return true; }
+constexpr bool rows_no_run(int, int, int, int layout) { return !is_run_layout(layout); }
+constexpr bool rows_field(int sampling, int, int, int layout) { return sampling != VR_SAMPLE_NEAREST && !is_run_layout(layout) && layout != (int) kLayoutVoxel; }
+struct NoDynamicLds { template <class Row> uint32_t operator()(Row, const RayKernelArgs &) const { return 0u; } };
+
+// One frame of a kernel with one workgroup per screen tile — the launch sequence of every ray kernel, stated once: the row select_variant
+// picks for the arguments (hipErrorInvalidValue where ROWS says the family has none), its tile grid filled into a copy of the arguments,
+// dynamic_lds(row, that copy) bytes of dynamic LDS, the kernel pick(row) names, launched with (the copy, the volume copy the row reads, tail...).
+template <bool (*ROWS)(int, int, int, int), class Lds, class Pick, class... Tail>
+static hipError_t launch_tiles(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, hipStream_t stream,
+                               Lds dynamic_lds, Pick pick, Tail... tail) {
+	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
+		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
+		if constexpr (!ROWS(SAMPLING, BPV, ADDR, LAYOUT)) return hipErrorInvalidValue;
+		else {
+			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
+			constexpr VariantRow<SAMPLING, BPV, ADDR, LAYOUT> row{};
+			RayKernelArgs a = args;
+			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
+			hipLaunchKernelGGL(pick(row), dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds(row, a), stream,
+			                   a, reads_linear ? linear : bricked, tail...);
+			return hipGetLastError();
+		}
+	});
+}
+
+// The frame of a composite feature family (shadowed, lit, slab, backdrop: the units beside vr_raymarch.hip, each with one launcher of
+// the type CompositeLauncher, vr_device.h): the argument checks those frames share, then launch_tiles over the rows they share.
+template <class Pick>
+static hipError_t launch_composite_feature(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
+                                           const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream, Pick pick) {
+	if ((args.shadow_on && args.shadow_q == 0ull) || (args.backdrop_on && (args.backdrop_rgba == 0ull || args.backdrop_depth == 0ull)) ||
+	    args.p.sampling == VR_SAMPLE_NEAREST)
+		return hipErrorInvalidValue;
+	return launch_tiles<rows_field>(args, linear, bricked, bpv, stream, NoDynamicLds(), pick, tf, esl, (uint32_t *) out, sched.order, sched.cost);
+}
+
 }  // namespace vr

@@ -84,21 +84,12 @@ hipError_t launch_mip_bounds(const uint8_t *minmax_dev, uint8_t *bounds_dev, hip
 hipError_t launch_mip(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf, const uint8_t *bounds,
                       void *out, hipStream_t stream) {
 	if (args.p.esl != 0u && bounds == nullptr) return hipErrorInvalidValue;
-	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
-		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
-		if constexpr (is_run_layout(LAYOUT)) return hipErrorInvalidValue;       // a MIP frame never reads the run bricks (the caller does not ask for them)
-		else {
-			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
-			RayKernelArgs a = args;
-			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
-			// the bound table is dynamic LDS, so that frames which do not skip keep every resident workgroup the address tables allow
-			const uint32_t dynamic_lds = a.p.esl != 0u ? kMipBoundEntries : 0u;
-			auto kernel = a.clip_on ? mip_clipped<SAMPLING, BPV, ADDR, LAYOUT> : mip_kernel<SAMPLING, BPV, ADDR, LAYOUT>;
-			hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
-			                   a, reads_linear ? linear : bricked, tf, bounds, (uint32_t *) out);
-			return hipGetLastError();
-		}
-	});
+	// a MIP frame never reads the run bricks (the caller does not ask for them); the bound table is dynamic LDS, so that frames which do
+	// not skip keep every resident workgroup the address tables allow
+	return launch_tiles<rows_no_run>(args, linear, bricked, bpv, stream,
+	                                 [](auto, const RayKernelArgs &a) { return a.p.esl != 0u ? kMipBoundEntries : 0u; },
+	                                 [&](auto row) { return args.clip_on ? VR_ROW_KERNEL(mip_clipped, row) : VR_ROW_KERNEL(mip_kernel, row); },
+	                                 tf, bounds, (uint32_t *) out);
 }
 
 // ---- shaded isosurface with depth (vr_hip_render_iso) -----------------------------------------------------------
@@ -142,22 +133,12 @@ void iso_clipped(const RayKernelArgs a, const void *__restrict__ vol, const floa
 hipError_t launch_iso(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf, const uint8_t *bounds,
                       float level, uint32_t refine, void *out_rgba, void *out_depth, hipStream_t stream) {
 	if (args.p.esl != 0u && bounds == nullptr) return hipErrorInvalidValue;
-	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
-		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
-		// the interpolated field from the copies a MIP frame reads: never NEAREST (the caller refuses it), the run bricks or the voxel bricks
-		if constexpr (SAMPLING == VR_SAMPLE_NEAREST || is_run_layout(LAYOUT) || LAYOUT == kLayoutVoxel) return hipErrorInvalidValue;
-		else {
-			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
-			RayKernelArgs a = args;
-			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
-			// the bit table is dynamic LDS: 4 KiB next to the address tables keep every resident workgroup frames without skipping have
-			const uint32_t dynamic_lds = a.p.esl != 0u ? VR_ESL_VOLUME_SIZE * 4u : 0u;
-			auto kernel = a.clip_on ? iso_clipped<SAMPLING, BPV, ADDR, LAYOUT> : iso_kernel<SAMPLING, BPV, ADDR, LAYOUT>;
-			hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), dynamic_lds, stream,
-			                   a, reads_linear ? linear : bricked, tf, bounds, level, refine, (uint32_t *) out_rgba, (float *) out_depth);
-			return hipGetLastError();
-		}
-	});
+	// the interpolated field from the copies a MIP frame reads: never NEAREST (the caller refuses it), the run bricks or the voxel bricks;
+	// the bit table is dynamic LDS: 4 KiB next to the address tables keep every resident workgroup frames without skipping have
+	return launch_tiles<rows_field>(args, linear, bricked, bpv, stream,
+	                                [](auto, const RayKernelArgs &a) { return a.p.esl != 0u ? VR_ESL_VOLUME_SIZE * 4u : 0u; },
+	                                [&](auto row) { return args.clip_on ? VR_ROW_KERNEL(iso_clipped, row) : VR_ROW_KERNEL(iso_kernel, row); },
+	                                tf, bounds, level, refine, (uint32_t *) out_rgba, (float *) out_depth);
 }
 
 }  // namespace vr

@@ -1,7 +1,7 @@
-// vr_raymarch_body.inc — the statements of raymarch_kernel and raymarch_clipped (vr_raymarch.hip, which includes this text inside both with
-// `constexpr bool CLIP`, `SHADOW`, `LIT`, `SLAB` and `BACKDROP` set), of raymarch_shadowed (vr_shadow.hip), of composite_lit (vr_light.hip), of
-// composite_slab and composite_slab_lit (vr_slab.hip) and of the four composite_backdrop* kernels (vr_backdrop.hip, vr_backdrop_slab.hip):
-// a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
+// vr_raymarch_body.inc — the statements of the composite-march kernels: vr_composite_family.inc, the one kernel definition, includes this
+// text with `constexpr bool CLIP`, `SHADOW`, `LIT`, `SLAB` and `BACKDROP` set as the family says — raymarch_kernel and raymarch_clipped
+// (vr_raymarch.hip), raymarch_shadowed (vr_shadow.hip), composite_lit (vr_light.hip), composite_slab and composite_slab_lit (vr_slab.hip),
+// the four composite_backdrop* kernels (vr_backdrop.hip, vr_backdrop_slab.hip).  a, vol, tf_g, esl_g, out, tile_order, tile_cost are the kernel's parameters.
 	// tile_order: workgroup id -> tile number (measured-cost launch order), or NULL: identity.  tile_cost: per tile, the longest wave of
 	// the tile in 64-cycle units (atomicMax), or NULL: not recorded.  Both are consumed FIRST, before the tables are staged: the hot
 	// variants sit at the 80-SGPR limit of 8 waves per SIMD and their peak is the staging code, so nothing of the schedule may be live

@@ -1,6 +1,7 @@
 // vr_shadow.hip — light-source shadows for composite frames (include/vr_hip.h vr_hip_set_shadow): shadow_build_kernel
 // marches from every node of the light grid to the light and stores the transmittance as a byte; raymarch_shadowed is the composite march
-// (vr_raymarch_body.inc once more) whose dense samples are scaled by the trilinear interpolation of those bytes.
+// (the family definition vr_composite_family.inc, declared here with SHADOW set) whose dense samples are scaled by the trilinear
+// interpolation of those bytes.
 #include "vr_march.h"
 
 namespace vr {
@@ -94,31 +95,15 @@ hipError_t launch_shadow_build(const RayKernelArgs &args, const ShadowBuildArgs 
 // ---- the shadowed composite frame ---------------------------------------------------------------------------------------------------------
 // raymarch_clipped with SHADOW set: it always runs clip_segment (the host fills the identity clip when no clip is set, which changes no bit
 // by contract), so shadow with clip needs no fourth family.  TRILINEAR and TRILINEAR_Q8 only; the clipped table without its NEAREST rows.
-template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
-__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
-void raymarch_shadowed(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
-                       const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
-                       const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a shadowed frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = true, LIT = false, SLAB = false, BACKDROP = false;
-#include "vr_raymarch_body.inc"
-}
+#define VR_FAMILY_KERNEL raymarch_shadowed
+#define VR_FAMILY_FLAGS  CLIP = true, SHADOW = true, LIT = false, SLAB = false, BACKDROP = false
+#define VR_FAMILY_OUT    __restrict__
+#include "vr_composite_family.inc"
 
 hipError_t launch_raymarch_shadowed(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
                                     const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
-	if (!args.shadow_on || args.shadow_q == 0ull || args.p.sampling == VR_SAMPLE_NEAREST) return hipErrorInvalidValue;
-	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
-		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
-		if constexpr (SAMPLING == VR_SAMPLE_NEAREST || is_run_layout(LAYOUT) || LAYOUT == kLayoutVoxel) return hipErrorInvalidValue;
-		else {
-			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
-			RayKernelArgs a = args;
-			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
-			hipLaunchKernelGGL((raymarch_shadowed<SAMPLING, BPV, ADDR, LAYOUT>), dim3(a.tiles_x * a.tiles_y), dim3(threads), 0, stream,
-			                   a, reads_linear ? linear : bricked, tf, esl, (uint32_t *) out, sched.order, sched.cost);
-			return hipGetLastError();
-		}
-	});
+	if (!args.shadow_on) return hipErrorInvalidValue;
+	return launch_composite_feature(args, linear, bricked, bpv, tf, esl, out, sched, stream, [](auto row) { return VR_ROW_KERNEL(raymarch_shadowed, row); });
 }
 
 }  // namespace vr

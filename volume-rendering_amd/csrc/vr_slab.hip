@@ -1,6 +1,7 @@
 // vr_slab.hip — pre-integrated (slab) classification for composite frames (include/vr_hip.h vr_hip_set_preintegration, DESIGN.md section
-// 4.10): composite_slab and composite_slab_lit are the composite march (vr_raymarch_body.inc once more) whose samples take the mean of the
-// transfer function between the previous sample's coordinate and their own — from the integral table K in LDS — in place of one lookup.
+// 4.10): composite_slab and composite_slab_lit are the composite march (the family definition vr_composite_family.inc, declared here with
+// SLAB set) whose samples take the mean of the transfer function between the previous sample's coordinate and their own — from the
+// integral table K in LDS — in place of one lookup.
 #include "vr_march.h"
 
 namespace vr {
@@ -8,54 +9,23 @@ namespace vr {
 // The clipped composite's body with SLAB set: it always runs clip_segment (the host fills the identity clip when no clip is set, which
 // changes no bit by contract), carries the reference's cue and tests the shadow per dense sample as a kernel argument, as composite_lit
 // does, so slab frames with clip, with shadow and with both need no further family.  TRILINEAR and TRILINEAR_Q8 only; the rows of composite_lit.
-template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
-__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
-void composite_slab(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
-                    const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
-                    const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a slab frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = false, SLAB = true, BACKDROP = false;
-#include "vr_raymarch_body.inc"
-}
+#define VR_FAMILY_KERNEL composite_slab
+#define VR_FAMILY_FLAGS  CLIP = true, SHADOW = false, LIT = false, SLAB = true, BACKDROP = false
+#define VR_FAMILY_OUT    __restrict__
+#include "vr_composite_family.inc"
 // ... with the gradient lighting (vr_hip_set_lighting) in place of the cue
-template <int SAMPLING, int BPV, int ADDR, int LAYOUT>
-__global__ __launch_bounds__(LutCfg<(LAYOUT != kLayoutLinear ? ADDR : kAddrWide)>::threads)
-void composite_slab_lit(const RayKernelArgs a, const void *__restrict__ vol, const float *__restrict__ tf_g,
-                        const uint32_t *__restrict__ esl_g, uint32_t *__restrict__ out,
-                        const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost) {
-	static_assert(!is_run_layout(LAYOUT) && SAMPLING != VR_SAMPLE_NEAREST, "a slab frame is TRILINEAR and never reads a run copy");
-	constexpr bool CLIP = true, SHADOW = false, LIT = true, SLAB = true, BACKDROP = false;
-#include "vr_raymarch_body.inc"
-}
+#define VR_FAMILY_KERNEL composite_slab_lit
+#define VR_FAMILY_FLAGS  CLIP = true, SHADOW = false, LIT = true, SLAB = true, BACKDROP = false
+#define VR_FAMILY_OUT    __restrict__
+#include "vr_composite_family.inc"
 
-template <bool LIT_FAMILY>
-static hipError_t launch_slab(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
-                              const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
-	if (!args.slab_on || (args.light_on != 0u) != LIT_FAMILY || (args.shadow_on && args.shadow_q == 0ull) || args.p.sampling == VR_SAMPLE_NEAREST)
-		return hipErrorInvalidValue;
-	return select_variant(args, bricked != nullptr, bpv, [&](auto sampling, auto voxel, auto addr, auto layout, bool reads_linear) {
-		constexpr int SAMPLING = decltype(sampling)::value, BPV = decltype(voxel)::value, ADDR = decltype(addr)::value, LAYOUT = decltype(layout)::value;
-		if constexpr (SAMPLING == VR_SAMPLE_NEAREST || is_run_layout(LAYOUT) || LAYOUT == kLayoutVoxel) return hipErrorInvalidValue;
-		else {
-			constexpr uint32_t threads = variant_threads<ADDR, LAYOUT>();
-			RayKernelArgs a = args;
-			tile_grid(a.p.out_width, a.p.out_rows, a.phase_x, a.phase_y, threads, a.tiles_x, a.tiles_y);
-			auto kernel = composite_slab<SAMPLING, BPV, ADDR, LAYOUT>;
-			if (LIT_FAMILY) kernel = composite_slab_lit<SAMPLING, BPV, ADDR, LAYOUT>;
-			hipLaunchKernelGGL(kernel, dim3(a.tiles_x * a.tiles_y), dim3(threads), 0, stream,
-			                   a, reads_linear ? linear : bricked, tf, esl, (uint32_t *) out, sched.order, sched.cost);
-			return hipGetLastError();
-		}
-	});
-}
-
+// tf: the 128 entries and their running integral K behind them
 hipError_t launch_composite_slab(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
                                  const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
-	return launch_slab<false>(args, linear, bricked, bpv, tf, esl, out, sched, stream);
-}
-hipError_t launch_composite_slab_lit(const RayKernelArgs &args, const void *linear, const void *bricked, uint32_t bpv, const float *tf,
-                                     const uint32_t *esl, void *out, TileSchedule sched, hipStream_t stream) {
-	return launch_slab<true>(args, linear, bricked, bpv, tf, esl, out, sched, stream);
+	if (!args.slab_on) return hipErrorInvalidValue;
+	return launch_composite_feature(args, linear, bricked, bpv, tf, esl, out, sched, stream, [&](auto row) {
+		return !args.light_on ? VR_ROW_KERNEL(composite_slab, row) : VR_ROW_KERNEL(composite_slab_lit, row);
+	});
 }
 
 }  // namespace vr
