@@ -1,17 +1,15 @@
-"""Test-side helpers of the backdrop tests: tests/backdrop_ref.c (the backdrop and hybrid frames of include/vr_hip.h vr_hip_render_backdrop /
-vr_hip_render_hybrid, restated with the CPU oracle's own statics) compiled on demand into a temporary directory like tests/slab_ref.c, the
-seeded generator of synthetic layers, and the volumes, views and isosurface levels both tiers use."""
-import atexit
+"""Test-side helpers of the backdrop tests: backdrop_render, hybrid_render and backdrop_segments of tests/feature_ref.c (the backdrop and
+hybrid frames of include/vr_hip.h vr_hip_render_backdrop / vr_hip_render_hybrid, restated with the CPU oracle's own statics;
+tests/ref_library.py loads it), the seeded generator of synthetic layers, and the isosurface levels both tiers use.  The volumes, views
+and scenes of these tests are light_helpers.lit_volumes, light_helpers.lit_views and slab_helpers.slab_scene."""
 import ctypes as C
-import shutil
-import tempfile
 
 import numpy as np
 
-from clip_helpers import IDENTITY, clip_floats
+from clip_helpers import IDENTITY
 from feature_random import generator
-from light_helpers import LIT_VOLUMES, lit_views, lit_volumes
-from mip_helpers import compile_test_library
+from light_helpers import LIT_VOLUMES, lit_views
+from ref_library import Ref, SceneArgs, frame_array, ptr
 from slab_helpers import POINT, slab_scene
 
 # what the GPU tier renders (with the eleven EDGE_SHAPES of tests/feature_random.py)
@@ -25,101 +23,49 @@ K_LT_D, NO_BLEND_AFTER_ERT, BYTE_OVER_255 = 1, 2, 3        # the `perturb` of ba
 STREAM = 411                                              # the generator stream of the synthetic layers (feature_random.generator)
 
 
-def backdrop_volumes(golden):
-    return lit_volumes(golden)
-
-
-def backdrop_views(vr, golden, name):
-    return lit_views(vr, golden, name)
-
-
-def backdrop_scene(vr, golden, oracle, volumes, name, view, sampling, full_march, step_factor=1):
-    """(voxels, params, tf, esl) of a volume's composite frame: slab_helpers.slab_scene"""
-    return slab_scene(vr, golden, oracle, volumes, name, view, sampling, full_march, step_factor)
-
-
-class BackdropRef:
-    """backdrop_render / hybrid_render / backdrop_segments of tests/backdrop_ref.c on WHOLE frames; cached per argument set."""
-    _inst = None
-
-    @classmethod
-    def instance(cls):
-        if cls._inst is None:
-            cls._inst = BackdropRef()
-        return cls._inst
+class BackdropRef(Ref):
+    """backdrop_render / hybrid_render / backdrop_segments of tests/feature_ref.c on WHOLE frames; cached per argument set."""
 
     def __init__(self):
-        self.dir = tempfile.mkdtemp(prefix="backdrop_ref_")
-        atexit.register(shutil.rmtree, self.dir, ignore_errors=True)
-        self.L = compile_test_library(self.dir, "backdrop_ref.c", "libbackdrop_ref.so")
+        super().__init__()
         for f in (self.L.backdrop_render, self.L.hybrid_render, self.L.backdrop_segments):
             f.restype = C.c_int
-        self._cache = {}
-
-    @staticmethod
-    def _scene_args(params, voxels, tf, esl, clip, lighting, q, strength, mode):
-        assert params.x0 == 0 and params.out_width == params.view.width and params.out_rows == params.view.height and params.band_stride == 1
-        vox = voxels if voxels.flags["C_CONTIGUOUS"] else np.ascontiguousarray(voxels)
-        tf = np.ascontiguousarray(tf, dtype=np.float32)
-        esl = np.ascontiguousarray(esl, dtype=np.uint32)
-        z, y, x = vox.shape
-        cf = clip_floats(clip)
-        lf = None if lighting is None else np.array(lighting[:3], np.float32)
-        shin = 0 if lighting is None else int(lighting[3])
-        qq = None if q is None else np.ascontiguousarray(q)
-        key = (bytes(params), vox.ctypes.data, vox.shape, tf.tobytes(), esl.tobytes(), cf.tobytes(), None if lf is None else lf.tobytes(), shin,
-               None if qq is None else qq.tobytes(), float(np.float32(strength)), int(mode))
-        args = [C.byref(params), vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize),
-                tf.ctypes.data_as(C.c_void_p), esl.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p),
-                None if lf is None else lf.ctypes.data_as(C.c_void_p), C.c_uint32(shin),
-                None if qq is None else qq.ctypes.data_as(C.c_void_p), C.c_uint32(0 if qq is None else qq.shape[0]),
-                C.c_float(strength), C.c_uint32(mode)]
-        return key, args, (vox, tf, esl, cf, lf, qq)
 
     def render(self, params, voxels, tf, esl, rgba=None, depth=None, mode=POINT, clip=IDENTITY, lighting=None, q=None, strength=1.0, perturb=0):
         """the composite frame over the layer (rgba [rows, width, 4] uint8, depth [rows, width] float32; both None: the bytes of slab_render)"""
-        key, args, keep = self._scene_args(params, voxels, tf, esl, clip, lighting, q, strength, mode)
+        a = SceneArgs(params, voxels, tf, esl, clip, lighting, q, strength, mode)
         if rgba is not None:
             rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
             depth = np.ascontiguousarray(depth, dtype=np.float32)
             assert rgba.shape == (params.out_rows, params.out_width, 4) and depth.shape == (params.out_rows, params.out_width)
-        key = ("backdrop",) + key + (None if rgba is None else rgba.tobytes(), None if depth is None else depth.tobytes(), int(perturb))
-        if key not in self._cache:
-            out = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            rc = self.L.backdrop_render(*args, C.c_uint32(perturb), None if rgba is None else rgba.ctypes.data_as(C.c_void_p),
-                                        None if depth is None else depth.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
-            assert rc == 0
-            out.setflags(write=False)
-            self._cache[key] = (out, keep)
-        return self._cache[key][0]
+
+        def make():
+            out = frame_array(params, 4)
+            assert self.L.backdrop_render(*a.base, a.esl, a.clip, *a.lighting, *a.shadow, a.mode, C.c_uint32(perturb), ptr(rgba), ptr(depth), ptr(out)) == 0
+            return (out,)
+        key = ("backdrop",) + a.key + (None if rgba is None else rgba.tobytes(), None if depth is None else depth.tobytes(), int(perturb))
+        return self.cached(key, a.keep, make)[0]
 
     def hybrid(self, params, voxels, tf, esl, level, refine, mode=POINT, clip=IDENTITY, lighting=None, q=None, strength=1.0, perturb=0):
         """(hybrid frame, depth, isosurface frame)"""
-        key, args, keep = self._scene_args(params, voxels, tf, esl, clip, lighting, q, strength, mode)
-        key = ("hybrid",) + key + (float(np.float32(level)), int(refine), int(perturb))
-        if key not in self._cache:
-            out = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            iso = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            dep = np.zeros((params.out_rows, params.out_width), np.float32)
-            rc = self.L.hybrid_render(*args, C.c_uint32(perturb), C.c_float(level), C.c_uint32(refine), out.ctypes.data_as(C.c_void_p),
-                                      dep.ctypes.data_as(C.c_void_p), iso.ctypes.data_as(C.c_void_p))
-            assert rc == 0
-            for a in (out, dep, iso):
-                a.setflags(write=False)
-            self._cache[key] = ((out, dep, iso), keep)
-        return self._cache[key][0]
+        a = SceneArgs(params, voxels, tf, esl, clip, lighting, q, strength, mode)
+
+        def make():
+            out, dep, iso = frame_array(params, 4), frame_array(params, dtype=np.float32), frame_array(params, 4)
+            assert self.L.hybrid_render(*a.base, a.esl, a.clip, *a.lighting, *a.shadow, a.mode, C.c_uint32(perturb), C.c_float(level), C.c_uint32(refine),
+                                        ptr(out), ptr(dep), ptr(iso)) == 0
+            return out, dep, iso
+        return self.cached(("hybrid",) + a.key + (float(np.float32(level)), int(refine), int(perturb)), a.keep, make)
 
     def segments(self, params, voxels, tf, esl, clip=IDENTITY):
         """[rows, width, 3] float32: kx, ky of the clipped segment and the k of the first sample of the accumulation loop; NaN = none"""
-        key, args, keep = self._scene_args(params, voxels, tf, esl, clip, None, None, 1.0, 0)
-        key = ("segments",) + key
-        if key not in self._cache:
-            seg = np.zeros((params.out_rows, params.out_width, 3), np.float32)
-            rc = self.L.backdrop_segments(*args[:7], seg.ctypes.data_as(C.c_void_p))
-            assert rc == 0
-            seg.setflags(write=False)
-            self._cache[key] = (seg, keep)
-        return self._cache[key][0]
+        a = SceneArgs(params, voxels, tf, esl, clip)
+
+        def make():
+            seg = frame_array(params, 3, dtype=np.float32)
+            assert self.L.backdrop_segments(*a.base, a.esl, a.clip, ptr(seg)) == 0
+            return (seg,)
+        return self.cached(("segments",) + a.key, a.keep, make)[0]
 
 
 def sample_ks(k0, step, n):
@@ -171,8 +117,8 @@ MARCHES = ("default", "full", "ert")     # esl on + the golden threshold; esl of
 
 
 def march_scene(vr, golden, oracle, volumes, name, view, sampling, march, step_factor=1):
-    """backdrop_scene in one of MARCHES"""
-    vox, p, tf, esl = backdrop_scene(vr, golden, oracle, volumes, name, view, sampling, march != "default", step_factor)
+    """slab_helpers.slab_scene in one of MARCHES"""
+    vox, p, tf, esl = slab_scene(vr, golden, oracle, volumes, name, view, sampling, march != "default", step_factor)
     if march == "ert":
         p = p.copy()
         p.ray_threshold = 0.95
@@ -185,7 +131,7 @@ def tier_frames(vr, golden, oracle, volumes, name, sampling):
     walks the same list."""
     from light_helpers import cue
     ref = BackdropRef.instance()
-    for v, (label, view) in enumerate(backdrop_views(vr, golden, name)):
+    for v, (label, view) in enumerate(lit_views(vr, golden, name)):
         for m, march in enumerate(MARCHES):
             for factor in (1, 4):
                 vox, p, tf, esl = march_scene(vr, golden, oracle, volumes, name, view, sampling, march, factor)

@@ -297,7 +297,7 @@ EDGE_SALT = 3000                                     # the layers of the edge sh
 
 class ExpectedLayers:
     """The restatements' answers for the slab, backdrop and hybrid frames of one (scene, frame), beside Expected so that the tests of the
-    older features do not pay for them: tests/slab_ref.c and tests/backdrop_ref.c under the frame's clip, point classified with the cue
+    older features do not pay for them: slab_render, backdrop_render and hybrid_render under the frame's clip, point classified with the cue
     and — `*_all` — slab classified under the frame's lighting, light grid and strength.  The synthetic layer comes from
     backdrop_helpers.synthetic_layer, which has its own generator stream: the frames draw nothing for it."""
 

@@ -1,13 +1,10 @@
-"""Test-side helpers of the isosurface tests: tests/iso_ref.c (vr_hip_render_iso restated with the CPU oracle's own statics) compiled on
-demand into a temporary directory like tests/mip_ref.c, and the (volume, level) pairs both tiers use."""
-import atexit
+"""Test-side helpers of the isosurface tests: iso_render of tests/feature_ref.c (vr_hip_render_iso restated with the CPU oracle's own
+statics; tests/ref_library.py loads it), and the (volume, level) pairs both tiers use."""
 import ctypes as C
-import shutil
-import tempfile
 
 import numpy as np
 
-from mip_helpers import compile_test_library
+from ref_library import Ref, SceneArgs, frame_array, ptr, volume_args
 
 # (volume, level in raw voxel units): what the GPU tier renders and the CPU tier checks the skipping emulation on
 PAIRS = (("bucky", 100.0), ("blob_40x24x56", 100.0), ("blob_40x24x56", 200.0), ("shell48", 100.0), ("random_u16", 24.5 * 257), ("random_u16", 200.0 * 257),
@@ -18,57 +15,32 @@ VOLUMES = GOLDEN_VOLUMES + ("random_u16", "late_max", "corner", "zeros", "first_
 SIZES = ((80, 80), (120, 72))                         # 72 rows: not a multiple of the 16-row workgroup tile
 
 
-class IsoRef:
-    """iso_render of tests/iso_ref.c: (RGBA frame, depth, {samples, fetches, hits}) of a WHOLE frame; cached per argument set."""
-    _inst = None
-
-    @classmethod
-    def instance(cls):
-        if cls._inst is None:
-            cls._inst = IsoRef()
-        return cls._inst
+class IsoRef(Ref):
+    """iso_render of tests/feature_ref.c: (RGBA frame, depth, {samples, fetches, hits}) of a WHOLE frame; cached per argument set."""
 
     def __init__(self):
-        self.dir = tempfile.mkdtemp(prefix="iso_ref_")
-        atexit.register(shutil.rmtree, self.dir, ignore_errors=True)
-        self.L = compile_test_library(self.dir, "iso_ref.c", "libiso_ref.so")
+        super().__init__()
         self.L.iso_render.restype = C.c_int
         self.L.iso_dilated_maxima.restype = None
-        self._cache = {}
-        self._dilated = {}
 
     def dilated_maxima(self, vox):
         """(32768 dilated block maxima, block edge) of the volume, built on the host"""
-        key = (vox.ctypes.data, vox.shape)
-        if key not in self._dilated:
-            z, y, x = vox.shape
-            dil = np.zeros(32768, np.uint8)
-            bd = C.c_uint32()
-            self.L.iso_dilated_maxima(vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize), dil.ctypes.data_as(C.c_void_p), C.byref(bd))
-            self._dilated[key] = (dil, int(bd.value), vox)
-        return self._dilated[key][:2]
+        def make():
+            dil, bd = np.zeros(32768, np.uint8), C.c_uint32()
+            self.L.iso_dilated_maxima(*volume_args(vox)[1], ptr(dil), C.byref(bd))
+            return dil, int(bd.value)
+        return self.cached(("dilated", vox.ctypes.data, vox.shape), vox, make)
 
     def render(self, params, voxels, tf, level, refine, skipping=False):
         """skipping: emulate the kernel's fetch skipping by the dilated block maxima (params.esl itself is not looked at)"""
-        vox = voxels if voxels.flags["C_CONTIGUOUS"] else np.ascontiguousarray(voxels)
-        tf = np.ascontiguousarray(tf, dtype=np.float32)
-        key = (bytes(params), vox.ctypes.data, vox.shape, tf.tobytes(), float(np.float32(level)), int(refine), bool(skipping))
-        if key not in self._cache:
-            assert params.x0 == 0 and params.out_width == params.view.width and params.out_rows == params.view.height and params.band_stride == 1
-            z, y, x = vox.shape
-            out = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            depth = np.zeros((params.out_rows, params.out_width), np.float32)
-            counters = (C.c_uint64 * 3)()
-            dil, bd = self.dilated_maxima(vox) if skipping else (None, 0)
-            rc = self.L.iso_render(C.byref(params), vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize),
-                                   tf.ctypes.data_as(C.c_void_p), C.c_float(level), C.c_uint32(refine),
-                                   dil.ctypes.data_as(C.c_void_p) if skipping else None, C.c_uint32(bd),
-                                   out.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), counters)
-            assert rc == 0
-            out.setflags(write=False)
-            depth.setflags(write=False)
-            self._cache[key] = (out, depth, {"samples": int(counters[0]), "fetches": int(counters[1]), "hits": int(counters[2])}, vox)
-        return self._cache[key][:3]
+        a = SceneArgs(params, voxels, tf)
+
+        def make():
+            out, depth, counters = frame_array(params, 4), frame_array(params, dtype=np.float32), (C.c_uint64 * 3)()
+            dil, bd = self.dilated_maxima(a.keep[0]) if skipping else (None, 0)
+            assert self.L.iso_render(*a.base, C.c_float(level), C.c_uint32(refine), ptr(dil), C.c_uint32(bd), ptr(out), ptr(depth), counters) == 0
+            return out, depth, {"samples": int(counters[0]), "fetches": int(counters[1]), "hits": int(counters[2])}
+        return self.cached(("iso",) + a.key + (float(np.float32(level)), int(refine), bool(skipping)), a.keep, make)
 
 
 def frame_params(vr, oracle, vox, view, sampling, esl, light_kd=0.7):

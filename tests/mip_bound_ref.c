@@ -1,6 +1,6 @@
 /*
  * mip_bound_ref.c — the bound argument of the MIP kernel's TRILINEAR fetch skipping, checked sample by sample on
- * the CPU.  TEST INFRASTRUCTURE, compiled on demand like tests/mip_ref.c.
+ * the CPU.  TEST INFRASTRUCTURE, compiled by tests/ref_library.py next to tests/feature_ref.c.
  *
  * For every sample of every ray of a whole frame: the block of the sample is formed the way the kernel's block_index does (fused
  * march_point, map_float_int((p + 1) / 2, dim) / block edge, the grid of vro_volume_minmax), the bound is the maximum over the 3x3x3

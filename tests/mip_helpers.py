@@ -1,68 +1,35 @@
-"""Test-side helpers of the maximum-intensity projection tests: tests/mip_ref.c (the MIP loop restated with the CPU oracle's own
-statics) and tests/mip_bound_ref.c (the skip bound checked per sample) compiled on demand into a temporary directory, and the small
+"""Test-side helpers of the maximum-intensity projection tests: mip_render of tests/feature_ref.c (the MIP loop restated with the CPU
+oracle's own statics) and tests/mip_bound_ref.c (the skip bound checked per sample), both loaded by tests/ref_library.py, and the small
 volumes / transfer functions both tiers use."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# what oracle/Makefile builds libvr_oracle.so with
-CFLAGS = ["-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-fopenmp"]
+from ref_library import Ref, SceneArgs, frame_array, ptr, volume_args
 
 
-def compile_test_library(tmp_dir, source, name):
-    lib = os.path.join(tmp_dir, name)
-    subprocess.check_call(["gcc", *CFLAGS, "-o", lib, os.path.join(ROOT, "tests", source), "-lm"])
-    return C.CDLL(lib)
-
-
-class MipRef:
-    """mip_render of tests/mip_ref.c: (RGBA frame, per-pixel maximum) of a WHOLE frame; cached per (params, volume, tf)."""
-    _inst = None
-
-    @classmethod
-    def instance(cls):
-        if cls._inst is None:
-            cls._inst = MipRef()
-        return cls._inst
+class MipRef(Ref):
+    """mip_render of tests/feature_ref.c: (RGBA frame, per-pixel maximum) of a WHOLE frame; cached per (params, volume, tf)."""
 
     def __init__(self):
-        self.dir = tempfile.mkdtemp(prefix="mip_ref_")
-        atexit.register(shutil.rmtree, self.dir, ignore_errors=True)
-        self.L = compile_test_library(self.dir, "mip_ref.c", "libmip_ref.so")
+        super().__init__()
         self.L.mip_render.restype = C.c_int
-        self.B = compile_test_library(self.dir, "mip_bound_ref.c", "libmip_bound_ref.so")
         self.B.bound_check.restype = C.c_long
-        self._cache = {}
 
     def render(self, params, voxels, tf):
-        vox = np.ascontiguousarray(voxels)
-        tf = np.ascontiguousarray(tf, dtype=np.float32)
-        key = (bytes(params), vox.ctypes.data, vox.shape, tf.tobytes())
-        if key not in self._cache:
-            assert params.x0 == 0 and params.out_width == params.view.width and params.out_rows == params.view.height and params.band_stride == 1
-            z, y, x = vox.shape
-            out = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            raw = np.zeros((params.out_rows, params.out_width), np.uint32)
-            rc = self.L.mip_render(C.byref(params), vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize),
-                                   tf.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p))
-            assert rc == 0
-            out.setflags(write=False)
-            raw.setflags(write=False)
-            self._cache[key] = (out, raw, vox)          # (vox keeps the array whose address is part of the key alive)
-        return self._cache[key][:2]
+        a = SceneArgs(params, voxels, tf)
+
+        def make():
+            out, raw = frame_array(params, 4), frame_array(params, dtype=np.uint32)
+            assert self.L.mip_render(*a.base, ptr(out), ptr(raw)) == 0
+            return out, raw
+        return self.cached(("mip",) + a.key, a.keep, make)
 
     def bound_violations(self, params, voxels):
         """(samples of the whole frame that exceed the kernel's TRILINEAR skip bound, smallest margin): tests/mip_bound_ref.c"""
-        vox = np.ascontiguousarray(voxels)
-        z, y, x = vox.shape
+        vox, volume = volume_args(voxels)
         margin = C.c_double()
-        bad = self.B.bound_check(C.byref(params), vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize), C.byref(margin))
+        bad = self.B.bound_check(C.byref(params), *volume, C.byref(margin))
         return int(bad), float(margin.value)
 
 

@@ -1,17 +1,15 @@
-"""Test-side helpers of the pre-integration tests: tests/slab_ref.c (the slab-classified composite frame of include/vr_hip.h
-vr_hip_set_preintegration, restated with the CPU oracle's own statics) compiled on demand into a temporary directory like
-tests/light_ref.c, and the volumes, transfer functions and views both tiers use."""
-import atexit
+"""Test-side helpers of the pre-integration tests: slab_render and slab_build_integral of tests/feature_ref.c (the slab-classified
+composite frame of include/vr_hip.h vr_hip_set_preintegration, restated with the CPU oracle's own statics; tests/ref_library.py loads
+it), and the volumes, transfer functions and views both tiers use."""
 import ctypes as C
-import shutil
-import tempfile
 
 import numpy as np
 
-from clip_helpers import IDENTITY, clip_floats, composite_params
+from clip_helpers import IDENTITY, composite_params
 from helpers import axis_view
 from light_helpers import lit_views, lit_volumes
-from mip_helpers import compile_test_library, ramp_tf
+from mip_helpers import ramp_tf
+from ref_library import Ref, SceneArgs, frame_array, ptr
 
 POINT, SLAB, SLAB_DOUBLE, SLAB_SKIPPED_IS_NONE = 0, 1, 2, 3      # the `mode` of slab_render; the last is a wrong reading (sensitivity)
 # what the GPU tier renders; on the plateau whole waves skip the empty samples in front of the block, and the first block sample needs the
@@ -82,56 +80,30 @@ def phase_scene(vr, sampling):
     return vox, vr.whole_frame(p), peak_tf(), np.zeros(1024, np.uint32), (slice(4, -4), slice(4, 36))
 
 
-class SlabRef:
-    """slab_render / slab_build_integral of tests/slab_ref.c; cached per argument set."""
-    _inst = None
-
-    @classmethod
-    def instance(cls):
-        if cls._inst is None:
-            cls._inst = SlabRef()
-        return cls._inst
+class SlabRef(Ref):
+    """slab_render / slab_build_integral of tests/feature_ref.c; cached per argument set."""
 
     def __init__(self):
-        self.dir = tempfile.mkdtemp(prefix="slab_ref_")
-        atexit.register(shutil.rmtree, self.dir, ignore_errors=True)
-        self.L = compile_test_library(self.dir, "slab_ref.c", "libslab_ref.so")
+        super().__init__()
         self.L.slab_render.restype = C.c_int
         self.L.slab_build_integral.restype = None
-        self._cache = {}
 
     def integral(self, tf):
         """K of the 128 premultiplied entries: [128, 4] float32"""
         tf = np.ascontiguousarray(tf, dtype=np.float32)
         out = np.zeros((128, 4), np.float32)
-        self.L.slab_build_integral(tf.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        self.L.slab_build_integral(ptr(tf), ptr(out))
         return out
 
     def render(self, params, voxels, tf, esl, mode=SLAB, clip=IDENTITY, lighting=None, q=None, strength=1.0, counters=False):
         """the composite frame (TRILINEAR modes) under `clip`, with the reference's cue (lighting None) or lit by `lighting` = (ambient,
         diffuse, specular, shininess_log2), scaled by the light grid q (None: no shadow); mode POINT / SLAB / SLAB_DOUBLE / SLAB_SKIPPED_IS_NONE.
         counters=True: (frame, samples of the accumulation loop, wide-slab samples, narrow-slab samples)"""
-        assert params.x0 == 0 and params.out_width == params.view.width and params.out_rows == params.view.height and params.band_stride == 1
-        vox = voxels if voxels.flags["C_CONTIGUOUS"] else np.ascontiguousarray(voxels)
-        tf = np.ascontiguousarray(tf, dtype=np.float32)
-        esl = np.ascontiguousarray(esl, dtype=np.uint32)
-        z, y, x = vox.shape
-        cf = clip_floats(clip)
-        lf = None if lighting is None else np.array(lighting[:3], np.float32)
-        shin = 0 if lighting is None else int(lighting[3])
-        qq = None if q is None else np.ascontiguousarray(q)
-        key = (bytes(params), vox.ctypes.data, vox.shape, tf.tobytes(), esl.tobytes(), cf.tobytes(), None if lf is None else lf.tobytes(), shin,
-               None if qq is None else qq.tobytes(), float(np.float32(strength)), int(mode))
-        if key not in self._cache:
-            out = np.zeros((params.out_rows, params.out_width, 4), np.uint8)
-            cnt = (C.c_uint64 * 3)()
-            rc = self.L.slab_render(C.byref(params), vox.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(x, y, z), C.c_uint32(vox.dtype.itemsize),
-                                    tf.ctypes.data_as(C.c_void_p), esl.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p),
-                                    None if lf is None else lf.ctypes.data_as(C.c_void_p), C.c_uint32(shin),
-                                    None if qq is None else qq.ctypes.data_as(C.c_void_p), C.c_uint32(0 if qq is None else qq.shape[0]),
-                                    C.c_float(strength), C.c_uint32(mode), out.ctypes.data_as(C.c_void_p), cnt)
-            assert rc == 0
-            out.setflags(write=False)
-            self._cache[key] = (out, int(cnt[0]), int(cnt[1]), int(cnt[2]), vox)      # (vox: the array whose address is part of the key stays alive)
-        out, samples, wide, narrow, _ = self._cache[key]
-        return (out, samples, wide, narrow) if counters else out
+        a = SceneArgs(params, voxels, tf, esl, clip, lighting, q, strength, mode)
+
+        def make():
+            out, cnt = frame_array(params, 4), (C.c_uint64 * 3)()
+            assert self.L.slab_render(*a.base, a.esl, a.clip, *a.lighting, *a.shadow, a.mode, ptr(out), cnt) == 0
+            return out, int(cnt[0]), int(cnt[1]), int(cnt[2])
+        out = self.cached(("frame",) + a.key, a.keep, make)
+        return out if counters else out[0]

@@ -1,8 +1,8 @@
-"""CPU tier of the backdrop and hybrid frames (include/vr_hip.h vr_hip_render_backdrop / vr_hip_render_hybrid): tests/backdrop_ref.c — the
-frames the GPU tier expects — tied to the pinned restatement of the composite (tests/slab_ref.c, and through it the clipped, shadowed and
-gradient-lit ones) where there is no surface, shown to return the layer where nothing is composited, to be non-trivial on the hybrids the
-GPU tier renders, and to be sensitive to three wrong readings of the contract on the GPU tier's own frames; the register figures of the
-built backdrop kernels next to those of their twins; the binding."""
+"""CPU tier of the backdrop and hybrid frames (include/vr_hip.h vr_hip_render_backdrop / vr_hip_render_hybrid): backdrop_render and
+hybrid_render of tests/feature_ref.c — the frames the GPU tier expects — tied to the pinned restatement of the composite (slab_render, and
+through it the clipped, shadowed and gradient-lit ones) where there is no surface, shown to return the layer where nothing is composited,
+to be non-trivial on the hybrids the GPU tier renders, and to be sensitive to three wrong readings of the contract on the GPU tier's own
+frames; the register figures of the built backdrop kernels next to those of their twins; the binding."""
 import ctypes as C
 import os
 import re
@@ -10,13 +10,15 @@ import re
 import numpy as np
 import pytest
 
-from backdrop_helpers import (BACKDROP_VOLUMES, BYTE_OVER_255, HYBRID_LEVELS, K_LT_D, NO_BLEND_AFTER_ERT, BackdropRef, backdrop_scene, backdrop_views,
-                              backdrop_volumes, synthetic_layer, tier_frames)
+from backdrop_helpers import BACKDROP_VOLUMES, BYTE_OVER_255, HYBRID_LEVELS, K_LT_D, NO_BLEND_AFTER_ERT, BackdropRef, synthetic_layer, tier_frames
 from clip_helpers import CLIPS, IDENTITY, ClipRef
 from feature_random import generator
 from light_helpers import PHONG
+from light_helpers import lit_views as backdrop_views
+from light_helpers import lit_volumes as backdrop_volumes
 from shadow_helpers import LIGHTS, ShadowRef
 from slab_helpers import POINT, SLAB, SlabRef
+from slab_helpers import slab_scene as backdrop_scene
 
 GRID_S = 9                                          # the light grid of the tie: small, and not uniform on any golden volume
 NEW_SYMBOLS = ("vr_hip_render_backdrop_device", "vr_hip_render_backdrop", "vr_hip_render_hybrid_device", "vr_hip_render_hybrid", "vr_hip_backdrop_frames")
@@ -37,7 +39,9 @@ def diff(a, b):
 def test_without_a_surface_the_frame_is_the_pinned_restatement(golden):
     """NULL layers, and a depth layer of all -1, all NaN, or negative values (random, -0.0 excluded, -inf included) under random colour
     words, give the bytes of slab_render: point and slab mode, every golden case that carries a frame (TRILINEAR and Q8 in turn), the identity clip
-    and each of CLIPS, the cue alone and a lighting with a light grid."""
+    and each of CLIPS, the cue alone and a lighting with a light grid.  backdrop_render and slab_render wrap one ray of
+    tests/feature_ref.c: the tie shows that layers without a surface switch nothing on, not that two texts agree —
+    tests/test_restatement_pins.py pins the single ray to the five texts it replaced."""
     ref, slab_ref, shadow_ref = BackdropRef.instance(), SlabRef.instance(), ShadowRef.instance()
     rng = generator(412)
     checked = turn = 0
@@ -139,7 +143,7 @@ def test_a_surface_behind_everything_is_a_background_image(vr, golden, oracle):
 
 
 def test_hybrid_is_the_isosurface_under_the_backdrop(vr, golden, oracle):
-    """hybrid_render's isosurface frame and depth are clip_iso_render's of tests/clip_ref.c, bits and bytes, under the identity clip and
+    """hybrid_render's isosurface frame and depth are clip_iso_render's (one frame function of tests/feature_ref.c), bits and bytes, under the identity clip and
     under `both`, at refine 0 and 4; and the hybrid is backdrop_render over them"""
     ref, clip_ref, volumes = BackdropRef.instance(), ClipRef.instance(), backdrop_volumes(golden)
     for name in BACKDROP_VOLUMES:

@@ -1,5 +1,5 @@
-"""CPU tier of the clip region (include/vr_hip.h vr_hip_set_clip): tests/clip_ref.c — the frames and depths the GPU tier expects — tied to
-the pinned restatements it was copied from (the oracle's vro_render, tests/mip_ref.c, tests/iso_ref.c), held against the geometry of the
+"""CPU tier of the clip region (include/vr_hip.h vr_hip_set_clip): the clip_* entry points of tests/feature_ref.c — the frames and depths the GPU
+tier expects — tied to the oracle's vro_render (clip_render_ray is a text of its own) and to the unclipped mip_render and iso_render, held against the geometry of the
 region itself, and shown to be neither empty nor unclipped on what the GPU tier renders; the register figures of the built *_clipped
 kernels; the layout of VrClip."""
 import ctypes as C
@@ -37,7 +37,9 @@ def test_identity_clip_is_the_unclipped_oracle_on_every_golden_case(golden, orac
 
 
 def test_identity_clip_is_the_pinned_mip_and_iso_restatement(golden):
-    """... and clip_mip_render / clip_iso_render are tests/mip_ref.c / tests/iso_ref.c, byte for byte and depth bit for depth bit"""
+    """... and clip_mip_render / clip_iso_render are mip_render / iso_render, byte for byte and depth bit for depth bit.  Each pair wraps one
+    frame function of tests/feature_ref.c, with the clip and without: the tie compares that text with itself under the identity clip, and
+    tests/test_restatement_pins.py pins it to the separate texts (mip_ref.c, iso_ref.c, clip_ref.c) it replaced"""
     ref, tf = ClipRef.instance(), ramp_tf()
     hits = 0
     for cid in SMALL_CASES:

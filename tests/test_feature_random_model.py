@@ -1,7 +1,10 @@
 """CPU tier of the randomised and ragged-volume parity of the newer render features (tests/test_gpu_feature_random.py holds the GPU against
 the restatements on the frames of tests/feature_random.py).  Here, on those same frames: the restatements agree with one another and with
 the CPU oracle wherever two of them state the same thing — ties that the other *_model.py tests hold on the golden cases only — and the
-frames are neither empty nor untouched by the feature they are meant to test, so the GPU tier cannot pass on frames that show nothing."""
+frames are neither empty nor untouched by the feature they are meant to test, so the GPU tier cannot pass on frames that show nothing.
+Since tests/feature_ref.c states the feature ray, the MIP frame and the isosurface frame once, only the ties to clip_render and to the
+oracle are between independent texts; the others compare two wrappers of one text, and tests/test_restatement_pins.py pins that text, on
+these same frames, to the separate files it replaced."""
 import numpy as np
 import pytest
 
@@ -18,7 +21,9 @@ def edge_scenes(oracle, vr):
 
 
 def check_ties(oracle, vr, scene, f, what):
-    """every statement two restatements share, on one frame; returns the number of non-transparent pixels compared"""
+    """every statement two restatements share, on one frame; returns the number of non-transparent pixels compared.  mip / clipped mip,
+    iso / clipped iso and shadow / identity lighting are wrappers of one text each (tests/test_restatement_pins.py pins it); the composite
+    against the oracle, and shadow and lighting against clip_render, are ties between independent texts"""
     clip_ref, mip_ref, iso_ref, shadow_ref, light_ref = ClipRef.instance(), MipRef.instance(), IsoRef.instance(), ShadowRef.instance(), LightRef.instance()
     v, tf, esl = scene.vox, scene.tf, scene.esl
     mip = mip_ref.render(f.mip, v, tf)[0]
@@ -173,8 +178,9 @@ def edge_layer_frames(oracle, vr):
 
 
 def check_layer_ties(scene, f, salt, what):
-    """every statement tests/slab_ref.c and tests/backdrop_ref.c share with the older restatements, on one frame under its clip; returns
-    the number of non-transparent pixels compared"""
+    """every statement slab_render, backdrop_render and hybrid_render share with the older restatements, on one frame under its clip;
+    returns the number of non-transparent pixels compared.  Only the tie to clip_render is between two texts; the rest compares wrappers
+    of one ray and one isosurface frame (tests/test_restatement_pins.py pins them)"""
     from backdrop_helpers import BackdropRef
     from slab_helpers import POINT, SLAB, SlabRef
     clip_ref, slab_ref, ref = ClipRef.instance(), SlabRef.instance(), BackdropRef.instance()
@@ -195,7 +201,7 @@ def check_layer_ties(scene, f, salt, what):
 def test_slab_and_backdrop_restatements_agree_on_the_random_frames(vr, oracle):
     """On all 56 random frames, byte for byte: the point-classified slab restatement is the clipped composite; a backdrop frame without a
     layer, or with the synthetic layer's colours under a depth layer of all -1 (point) or all NaN (slab), is the frame without one; the
-    hybrid's isosurface frame and depth bits are tests/clip_ref.c's and the hybrid is the backdrop frame over them"""
+    hybrid's isosurface frame and depth bits are clip_iso_render's and the hybrid is the backdrop frame over them"""
     compared = frames = 0
     for scene, f, salt, what in random_layer_frames(oracle, vr):
         compared += check_layer_ties(scene, f, salt, what)
@@ -330,7 +336,7 @@ def holed_layer_frames(oracle, vr):
 
 def test_holed_scenes_reach_the_skipped_predecessor(vr, oracle):
     """The holed scenes (fr.holed_scenes: a slab of exact zeros through a random volume) hold the ties of the random frames, and at least a
-    third of their slab frames change under the wrong reading SLAB_SKIPPED_IS_NONE of tests/slab_ref.c — a sample the library may skip
+    third of their slab frames change under the wrong reading SLAB_SKIPPED_IS_NONE of slab_render — a sample the library may skip
     unresolved counts as no predecessor for the next one.  On the 56 random frames that reading changes 5: their volumes are smooth, and
     a value seldom jumps from what may be skipped to what shows within one step.  The reading is per ray; the library skips per wave."""
     from slab_helpers import SLAB, SLAB_SKIPPED_IS_NONE, SlabRef

@@ -1,6 +1,6 @@
 """GPU tier of the backdrop and hybrid frames (vr_hip_render_backdrop* / vr_hip_render_hybrid*): every frame the four composite_backdrop*
-kernel families render is held byte for byte against tests/backdrop_ref.c, the contract of include/vr_hip.h restated with the CPU oracle's
-statics — no tolerance anywhere.  tests/test_backdrop_model.py ties that restatement to the pinned composites and shows that the frames
+kernel families render is held byte for byte against backdrop_render / hybrid_render of tests/feature_ref.c, the contract of
+include/vr_hip.h restated with the CPU oracle's statics — no tolerance anywhere.  tests/test_backdrop_model.py ties that restatement to the pinned composites and shows that the frames
 compared here tell three wrong readings of the contract apart."""
 import ctypes as C
 import os
@@ -10,15 +10,18 @@ import sys
 import numpy as np
 import pytest
 
-from backdrop_helpers import BACKDROP_VOLUMES, HYBRID_LEVELS, BackdropRef, backdrop_scene, backdrop_views, backdrop_volumes, synthetic_layer, tier_frames
+from backdrop_helpers import BACKDROP_VOLUMES, HYBRID_LEVELS, BackdropRef, synthetic_layer, tier_frames
 from clip_helpers import CLIPS, set_clip
 from feature_random import EDGE_DTYPES, EDGE_SHAPES, edge_scene
 from helpers import GOLDEN_DIR, ROOT
 from iso_helpers import IsoRef, depth_bits, frame_params
 from light_helpers import LIGHTINGS, PHONG
+from light_helpers import lit_views as backdrop_views
+from light_helpers import lit_volumes as backdrop_volumes
 from mip_helpers import MipRef
 from shadow_helpers import FRAME_SCENES, LIGHTS, ShadowRef
 from slab_helpers import POINT, SLAB
+from slab_helpers import slab_scene as backdrop_scene
 
 pytestmark = pytest.mark.gpu
 

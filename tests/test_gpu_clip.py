@@ -1,6 +1,6 @@
 """GPU tier of the clip region (vr_hip_set_clip / vr_hip_multi_set_clip): every clipped frame the HIP path renders — composite, MIP,
-isosurface with depth — is held byte for byte / bit for bit against tests/clip_ref.c, the three projections restated with the CPU oracle's
-statics and the segment of every ray narrowed as include/vr_hip.h defines it.  tests/test_clip_model.py ties that restatement to the pinned
+isosurface with depth — is held byte for byte / bit for bit against the clip_* entry points of tests/feature_ref.c, the three projections
+restated with the CPU oracle's statics and the segment of every ray narrowed as include/vr_hip.h defines it.  tests/test_clip_model.py ties that restatement to the pinned
 ones and shows that the frames compared here are neither empty nor unclipped."""
 import ctypes as C
 import os

@@ -1,9 +1,10 @@
 """Randomised and ragged-volume parity of the newer render features: the clipped composite, the MIP, the isosurface with depth, the light
 grid, the shadowed and the gradient-lit frames on the random volumes and views of tests/test_gpu_random.py (odd extents, an extent of
 1 / 2 / 8 / 16 / 33, cameras inside the cube, exact zeros in the direction, the four-fold ray step) under a random clip, light, grid size,
-lighting and level per frame, and on the hand-made EDGE_SHAPES — every byte equal to the restatements tests/clip_ref.c, shadow_ref.c and
-light_ref.c; and, on the same frames, the pre-integrated (slab) composite, the backdrop frame over a synthetic layer and the hybrid of
-isosurface and volume against tests/slab_ref.c and tests/backdrop_ref.c.  tests/feature_random.py draws the frames; tests/test_feature_random_model.py ties the restatements to one another on them
+lighting and level per frame, and on the hand-made EDGE_SHAPES — every byte equal to the restatements of tests/feature_ref.c (the clip_*,
+shadow_* and light_render entry points); and, on the same frames, the pre-integrated (slab) composite, the backdrop frame over a synthetic
+layer and the hybrid of isosurface and volume against its slab_render, backdrop_render and hybrid_render.  tests/feature_random.py draws
+the frames; tests/test_feature_random_model.py ties the restatements to one another on them
 and shows that they are neither empty nor untouched by the feature.  Other seeds: VR_TEST_SEED=... pytest -m gpu tests/test_gpu_feature_random.py"""
 import os
 import subprocess
@@ -337,7 +338,7 @@ def test_state_changes_between_slab_and_backdrop_frames(vr, gpu, oracle):
     """32 operations on one context at a fixed 64 x 48 view — another volume, another random transfer function, a clip set or cleared, the
     pre-integration switched, another shadow, a lighting set or cleared, a backdrop frame, a hybrid frame, a plain composite frame, a MIP;
     the first ten run each kind once — each followed by one frame of a random kind (composite, backdrop, hybrid) held against the
-    restatement for the state as it stands.  After every transfer function K is tests/slab_ref.c's, bit for bit; the three frame counters
+    restatement for the state as it stands.  After every transfer function K is slab_build_integral's of tests/feature_ref.c, bit for bit; the three frame counters
     move as the contract says; the light grid is built again exactly when something it depends on changed — never for the pre-integration,
     a lighting, or a backdrop or hybrid frame."""
     from backdrop_helpers import BackdropRef, synthetic_layer

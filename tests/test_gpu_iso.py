@@ -1,5 +1,5 @@
 """GPU tier of the shaded isosurface with depth (vr_hip_render_iso / vr_hip_render_iso_device): every frame and every depth buffer the
-HIP path renders is held byte for byte / bit for bit against tests/iso_ref.c — the contract restated with the CPU oracle's statics,
+HIP path renders is held byte for byte / bit for bit against iso_render of tests/feature_ref.c — the contract restated with the CPU oracle's statics,
 which tests/test_iso_model.py holds against the MIP restatement and an analytic sphere.  Since esl on and esl off are both held against
 the same frame, they equal each other."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """GPU tier of the gradient lighting (vr_hip_set_lighting / vr_hip_multi_set_lighting): every lit composite frame the composite_lit kernels
-render is held byte for byte against tests/light_ref.c, the contract of include/vr_hip.h restated with the CPU oracle's statics.
+render is held byte for byte against light_render of tests/feature_ref.c, the contract of include/vr_hip.h restated with the CPU oracle's statics.
 tests/test_light_model.py ties that restatement to the pinned clipped composite and shows that the frames compared here are neither
 trivial nor the cue-lit ones, and that the plateau volume takes the zero-gradient branch."""
 import ctypes as C

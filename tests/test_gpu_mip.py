@@ -1,5 +1,5 @@
 """GPU tier of the maximum-intensity projection (vr_hip_render_mip / vr_hip_render_mip_device): every frame the HIP path renders is
-held byte for byte against tests/mip_ref.c — the MIP loop restated with the CPU oracle's statics, which tests/test_mip_model.py
+held byte for byte against mip_render of tests/feature_ref.c — the MIP loop restated with the CPU oracle's statics, which tests/test_mip_model.py
 pins against the unmodified oracle.  Since esl on and esl off are both held against the same frame, they equal each other."""
 import ctypes as C
 import os

@@ -1,6 +1,6 @@
 """GPU tier of the light-source shadows (vr_hip_set_shadow / vr_hip_multi_set_shadow): every light grid the HIP builder marches and every
-shadowed composite frame is held byte for byte against tests/shadow_ref.c, the contract of include/vr_hip.h restated with the CPU oracle's
-statics.  tests/test_shadow_model.py ties that restatement to the pinned clipped composite and shows that the grids and frames compared
+shadowed composite frame is held byte for byte against shadow_build / shadow_render of tests/feature_ref.c, the contract of
+include/vr_hip.h restated with the CPU oracle's statics.  tests/test_shadow_model.py ties that restatement to the pinned clipped composite and shows that the grids and frames compared
 here are neither trivial nor unshadowed."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """GPU tier of the pre-integrated classification (vr_hip_set_preintegration / vr_hip_multi_set_preintegration): every slab-classified
-composite frame the composite_slab and composite_slab_lit kernels render is held byte for byte against tests/slab_ref.c, the contract of
+composite frame the composite_slab and composite_slab_lit kernels render is held byte for byte against slab_render of tests/feature_ref.c, the contract of
 include/vr_hip.h restated with the CPU oracle's statics.  tests/test_slab_model.py ties that restatement to the pinned clipped, shadowed
 and gradient-lit composites and shows that the frames compared here take both branches and are not the point-classified ones."""
 import ctypes as C

@@ -1,5 +1,5 @@
-"""CPU tier of the shaded isosurface with depth (include/vr_hip.h vr_hip_render_iso): tests/iso_ref.c — the frames and depths the GPU tier
-expects — held against what is already pinned (tests/mip_ref.c's per-pixel maximum), against its own skipping emulation, and against
+"""CPU tier of the shaded isosurface with depth (include/vr_hip.h vr_hip_render_iso): iso_render of tests/feature_ref.c — the frames and depths the GPU
+tier expects — held against what is already pinned (mip_render's per-pixel maximum), against its own skipping emulation, and against
 analytic ground truth, without a GPU; and the register figures of the built iso_kernel instantiations."""
 import os
 import re
@@ -26,7 +26,7 @@ def _params(golden, case, sampling):
 
 @pytest.mark.parametrize("sampling", (1, 2), ids=("fp32", "q8"))
 def test_hit_mask_is_where_the_mip_maximum_reaches_the_level(golden, sampling):
-    """A ray has a first sample >= level exactly when its largest sample is >= level: tests/mip_ref.c's per-pixel maximum is pinned
+    """A ray has a first sample >= level exactly when its largest sample is >= level: mip_render's per-pixel maximum is pinned
     against the unmodified oracle by tests/test_mip_model.py.  The mask does not depend on `refine`."""
     tf = ramp_tf()
     hits = 0

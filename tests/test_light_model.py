@@ -1,5 +1,5 @@
-"""CPU tier of the gradient lighting (include/vr_hip.h vr_hip_set_lighting): tests/light_ref.c — the frames the GPU tier expects — tied to
-the pinned restatement of the clipped composite, held against the geometry of three ramps, shown to be monotone in the shininess and to be
+"""CPU tier of the gradient lighting (include/vr_hip.h vr_hip_set_lighting): light_render of tests/feature_ref.c — the frames the GPU tier expects —
+tied to the pinned restatement of the clipped composite (clip_render_ray, a text of its own), held against the geometry of three ramps, shown to be monotone in the shininess and to be
 neither trivial nor the cue-lit frame on what the GPU tier renders; the register figures of the built composite_lit kernels; the layout of
 VrLighting."""
 import ctypes as C
@@ -14,8 +14,8 @@ from light_helpers import IDENTITY_LIGHTING, LIT_VOLUMES, PHONG, LightRef, cue, 
 
 
 def test_identity_lighting_is_the_unlit_clipped_composite_on_every_golden_case(golden):
-    """{ 1, 0, 0, 4 }: m = fma(0, sd, 1) = 1 and spec = (0 * sp) * c.w = 0, so fma(c, 1, 0) = c — light_render is clip_render of
-    tests/clip_ref.c with light_kd = 0, byte for byte, under the identity clip and each of CLIPS, TRILINEAR and Q8, on every golden case
+    """{ 1, 0, 0, 4 }: m = fma(0, sd, 1) = 1 and spec = (0 * sp) * c.w = 0, so fma(c, 1, 0) = c — light_render (the feature ray of
+    tests/feature_ref.c) is clip_render (clip_render_ray) with light_kd = 0, byte for byte, under the identity clip and each of CLIPS, TRILINEAR and Q8, on every golden case
     that carries a frame.  (4 184 769 non-transparent pixels compared on this tree.)"""
     ref, clip_ref = LightRef.instance(), ClipRef.instance()
     checked = 0

@@ -1,9 +1,9 @@
-"""CPU tier of the maximum-intensity projection (include/vr_hip.h vr_hip_render_mip): tests/mip_ref.c — the frames the GPU tier
+"""CPU tier of the maximum-intensity projection (include/vr_hip.h vr_hip_render_mip): mip_render of tests/feature_ref.c — the frames the GPU tier
 expects — pinned against the UNMODIFIED oracle, without a GPU.
 
 The oracle only composites.  With a step transfer function (entries >= t are (1,1,1,1), the rest 0), esl off, threshold 1 and no
 light, a pixel's alpha byte is non-zero exactly when some sample of its ray looks up an entry >= t with a visible weight, so the
-largest such t, T, is a function of the ray's MAXIMUM sample — the quantity mip_ref.c returns per pixel."""
+largest such t, T, is a function of the ray's MAXIMUM sample — the quantity mip_render returns per pixel."""
 import os
 import re
 
@@ -88,7 +88,7 @@ def test_trilinear_maximum_is_what_the_oracle_composites(golden, oracle, samplin
 
 
 def test_mip_frame_is_the_lookup_of_the_maximum(golden):
-    """mip_ref.c's frame against its own per-pixel maximum: NEAREST pixels are write_color(transfer_fn[s8 / 2]), misses stay cleared"""
+    """mip_render's frame against its own per-pixel maximum: NEAREST pixels are write_color(transfer_fn[s8 / 2]), misses stay cleared"""
     ref = MipRef.instance()
     case = _case(golden, 45)
     vox, tf = golden.voxels(case["volume"]), golden.volume_state(case["volume"])["tf"]

@@ -1,5 +1,5 @@
-"""CPU tier of the light-source shadows (include/vr_hip.h vr_hip_set_shadow): tests/shadow_ref.c — the light grids and frames the GPU tier
-expects — tied to the pinned restatement of the clipped composite it was copied from, held against the geometry of an opaque shell, and
+"""CPU tier of the light-source shadows (include/vr_hip.h vr_hip_set_shadow): shadow_build and shadow_render of tests/feature_ref.c — the light grids
+and frames the GPU tier expects — tied to the pinned restatement of the clipped composite, clip_render_ray, a text of its own, held against the geometry of an opaque shell, and
 shown to be neither trivial nor unshadowed on what the GPU tier renders; the register figures of the built shadow kernels; the layout of
 VrShadow and VrLaunchInfo."""
 import ctypes as C
@@ -26,7 +26,7 @@ def _package(vr):
 
 
 def test_shadow_off_is_the_clipped_composite_on_every_golden_case(golden):
-    """Without a grid, and with a grid at strength 0 (f = fma(0, Tq, 1) = 1), shadow_render is clip_render of tests/clip_ref.c byte for byte:
+    """Without a grid, and with a grid at strength 0 (f = fma(0, Tq, 1) = 1), shadow_render (the feature ray of tests/feature_ref.c) is clip_render (clip_render_ray) byte for byte:
     under the identity clip and under each of CLIPS, TRILINEAR and Q8, on every golden case that carries a frame"""
     ref, clip_ref = ShadowRef.instance(), ClipRef.instance()
     rng = np.random.default_rng(3)

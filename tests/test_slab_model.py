@@ -1,5 +1,5 @@
-"""CPU tier of the pre-integrated classification (include/vr_hip.h vr_hip_set_preintegration): tests/slab_ref.c — the frames the GPU tier
-expects — tied to the pinned restatements of the clipped, shadowed and gradient-lit composite, shown to be the point-classified frame where
+"""CPU tier of the pre-integrated classification (include/vr_hip.h vr_hip_set_preintegration): slab_render of tests/feature_ref.c — the frames the
+GPU tier expects — tied to the pinned restatements of the clipped, shadowed and gradient-lit composite, shown to be the point-classified frame where
 consecutive samples are equal, to be independent of the sampling phase where point classification is not, to lose nothing to cancellation,
 and to be neither trivial nor the point-classified frame on what the GPU tier renders; the register figures of the built slab kernels;
 the binding."""
@@ -20,9 +20,12 @@ GRID_S = 9                                          # the light grid of the tie:
 
 
 def test_slab_off_is_the_pinned_restatements_on_every_golden_case(golden):
-    """With mode POINT slab_render is clip_render of tests/clip_ref.c (no lighting, no grid), shadow_render of tests/shadow_ref.c (a grid)
-    and light_render of tests/light_ref.c (a lighting, with and without the grid), byte for byte, under the identity clip and each of CLIPS,
-    TRILINEAR and Q8, on every golden case that carries a frame — and through them the oracle's frame."""
+    """With mode POINT slab_render is clip_render (no lighting, no grid), shadow_render (a grid) and light_render (a lighting, with and
+    without the grid), byte for byte, under the identity clip and each of CLIPS, TRILINEAR and Q8, on every golden case that carries a
+    frame — and through clip_render the oracle's frame.  The tie to clip_render is between two texts of tests/feature_ref.c
+    (feature_render_ray, clip_render_ray).  shadow_render and light_render are wrappers of the same feature ray as slab_render: those
+    ties compare one text with itself under two argument lists, and it is tests/test_restatement_pins.py that pins the single ray to the
+    five texts (clip_ref.c .. backdrop_ref.c) it replaced."""
     ref, clip_ref, shadow_ref, light_ref = SlabRef.instance(), ClipRef.instance(), ShadowRef.instance(), LightRef.instance()
     checked = 0
     for case in golden.cases(True):
