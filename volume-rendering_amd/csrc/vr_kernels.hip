@@ -1,6 +1,7 @@
 // vr_kernels.hip — the column marches (orthogonal views along a volume axis): colmarch_kernel, colmarch_nearest_kernel, voxcol_tri_kernel,
 // voxcol_pairs_kernel, what they share, and their launcher.  The other kernel units: vr_raymarch.hip, vr_project.hip, vr_schedule.hip, vr_builders.hip.
 #include "vr_march.h"
+#include <type_traits>
 
 namespace vr {
 
@@ -237,10 +238,13 @@ __device__ __forceinline__ void col_skip_window(const ColBatch &b, int &pos, int
 	pos = pos < 64 ? pos : 63;
 }
 template <class Refill, class Body>
-__device__ __forceinline__ void col_for_window_samples(const ColBatch &b, int &pos, int cur, int bound, Refill refill, Body body) {      // body(k) for every sample of the window
+__device__ __forceinline__ void col_for_window_samples(const ColBatch &b, int &pos, int cur, int bound, Refill refill, Body body) {      // body(k), or body(k, the sample's lane in the batch), for every sample of the window
 	for (int batches = 0; batches < bound; batches++) {
 		const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(b.wvec == cur));
-		for (int i = pos; i < pos + cnt; i++) body(rlane(b.kvec, i));
+		for (int i = pos; i < pos + cnt; i++) {
+			if constexpr (std::is_invocable_v<Body, float, int>) body(rlane(b.kvec, i), i);
+			else body(rlane(b.kvec, i));
+		}
 		pos += cnt;
 		if (pos < 64) break;
 		refill(); pos = 0;
@@ -801,6 +805,7 @@ void colmarch_nearest_kernel(const RayKernelArgs a, const uint8_t *__restrict__ 
 // window of column j of that rectangle (ONE managed 16-byte gather per lane and 16 cells); a sample's eight corners come from the four
 // lanes that own its 2 x 2 columns — each owner aligns the two slices of the wave-uniform cell into one dword, four ds_bpermute and four
 // v_perm rebuild the quad-element pair (w0, w1) that colmarch_kernel reads from its copy, and from there on the sample is col_tri_sample.
+// The aligned dword holds four slices, so ONE exchange serves the samples of three consecutive cells (a cell group, window_step).
 // A flip is a switch of the lane's owner index at the first k of its second column (col_bisect),
 // exact per sample: no event windows.  The transparency test is ONE per window and wave: the slices 16w .. 16w + 16 of every column of
 // the rectangle (the 16 cells of window w need the first slice of window w + 1 too).  Waves that cannot share the k sequence or the
@@ -943,16 +948,28 @@ __device__ __forceinline__ void voxcol_march(const RayKernelArgs &a, const uint8
 		const bool forward = dsign > 0;
 		// where this lane reads its corners: the byte address (ds_bpermute) of the owner of its (u, v) column; the owners of (u+1, v), (u, v+1)
 		// and (u+1, v+1) follow at +4, +4 rw, +4 rw + 4.  A lane whose column flips switches at the first k of its second column
-		// (col_bisect; the cell is monotone in k): samples with k >= t read the second column — exact per sample
+		// (col_bisect; the cell is monotone in k): samples with k >= t read the second column — exact per sample.  The switch is made where
+		// the corners are exchanged (window_step): `at` moves on and the threshold is spent, and between two switches the march compares k
+		// with ONE scalar, t_next = the bits of the smallest threshold no lane has spent yet (0: unordered as bits — look at every sample)
 		const uint32_t rw4 = (uint32_t) rw * 4u;
-		const uint32_t own0 = (uint32_t) ((cu0 - ru0) + (cv0 - rv0) * rw) * 4u;
+		uint32_t at = (uint32_t) ((cu0 - ru0) + (cv0 - rv0) * rw) * 4u;
 		float t_u = __builtin_inff(), t_v = __builtin_inff();
 		uint32_t step_u = 0u, step_v = 0u;
+		auto next_threshold = [&]() {
+			const float t = t_u < t_v ? t_u : t_v;
+			uint32_t m = t > 0.0f ? __float_as_uint(t) : 0u;                // (positive floats order like their bits)
+			// (ds_swizzle: the partner lane is part of the instruction — a shuffle's address registers would be kept across the whole march)
+			static_for<0, 5>([&](auto j) { const uint32_t other = (uint32_t) __builtin_amdgcn_ds_swizzle((int) m, ((1 << decltype(j)::value) << 10) | 0x1f); m = other < m ? other : m; });
+			const uint32_t h0 = (uint32_t) __builtin_amdgcn_readlane((int) m, 0), h1 = (uint32_t) __builtin_amdgcn_readlane((int) m, 32);
+			return h0 < h1 ? h0 : h1;
+		};
+		uint32_t t_next = 0x7f800000u;
 		if (FLIPS && flips != 0ull) {
 			const uint32_t bu = col_bisect(ray, cu0 != cu1, cu0, cell_u), bv = col_bisect(ray, cv0 != cv1, cv0, cell_v);
 			t_u = cu0 != cu1 ? __uint_as_float(bu) : __builtin_inff();
 			t_v = cv0 != cv1 ? __uint_as_float(bv) : __builtin_inff();
 			step_u = (uint32_t) (cu1 - cu0) * 4u; step_v = (uint32_t) (cv1 - cv0) * rw4;      // (two's complement: the sums wrap back into range)
+			t_next = next_threshold();
 		}
 		auto cell_window = [&](float kk) { return (int) VR_FMA(kk, Am, Bm_l) >> 4; };      // (cell by truncation, as colmarch_kernel)
 		ColBatch batch = { 0.0f, wv.kx_l, 0 };
@@ -996,20 +1013,48 @@ __device__ __forceinline__ void voxcol_march(const RayKernelArgs &a, const uint8
 			if (!dense) col_skip_window(batch, pos, cur, kCells + 2, next_batch);
 			else {
 				const int first = cur * kCells;
-				col_for_window_samples(batch, pos, cur, kCells + 2, next_batch, [&](float kk) {
+				// One corner exchange per CELL GROUP.  The dword an owner aligns at cell `base` holds the four slices base .. base + 3 of its
+				// column, i.e. the cells base, base + 1 and base + 2; a sample advances at most one cell, so the samples that follow read their
+				// pair out of the four exchanged dwords with another v_perm selector (sub - base: uniform) for as long as their cell stays in the
+				// group and no lane has changed its owner.  Marching down the group ends at the sample's cell instead (base = sub - 2, not below
+				// the window's first cell).  A new window always exchanges again: `o` and `nx` are other registers then.
+				// voxcol_tri_kernel with FLIPS has no room for the four dwords beside its thresholds and steps (it is at 63 - 64 VGPRs without them; the
+				// other eighteen kernels hold them in 60 - 64): there a group holds the owner's aligned dword alone (one register) and every sample
+				// exchanges it; the selects, the alignment and the owner switch are still made once per group.
+				constexpr bool kHoldCorners = !FLIPS || PAIRS;
+				int base = 64;
+				uint32_t group = 0u, p00 = 0u, p10 = 0u, p01 = 0u, p11 = 0u;
+				auto exchange = [&]() {
+					p00 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) at, (int) group); p10 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + 4u), (int) group);
+					p01 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4), (int) group); p11 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4 + 4u), (int) group);
+				};
+				// the cells of the batch's 64 samples, once per window and batch (cell_window's own arithmetic): a sample reads its cell with one
+				// v_readlane instead of forming it again from three scalars
+				int cells = (int) VR_FMA(batch.kvec, Am, Bm_l);
+				auto next_cells = [&]() { next_batch(); cells = (int) VR_FMA(batch.kvec, Am, Bm_l); };
+				col_for_window_samples(batch, pos, cur, kCells + 2, next_cells, [&](float kk, int lane) {
 					k = kk;
-					const uint32_t sub = (uint32_t) ((int) rfl((uint32_t) (int) VR_FMA(k, Am, Bm_l)) - first) & 15u;      // the sample's cell inside the window (uniform)
-					// the owner's two slices of that cell in one dword (byte 0: slice sub, byte 1: slice sub + 1)
-					const uint32_t qw = sub >> 2;
-					const uint32_t lo = qw == 0u ? o.x : (qw == 1u ? o.y : (qw == 2u ? o.z : o.w));
-					const uint32_t hi = qw == 0u ? o.y : (qw == 1u ? o.z : (qw == 2u ? o.w : nx));
-					const int pair = (int) __builtin_amdgcn_alignbyte(hi, lo, sub & 3u);
-					uint32_t at = own0;
-					if (FLIPS) at += (k >= t_u ? step_u : 0u) + (k >= t_v ? step_v : 0u);
-					const uint32_t p00 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) at, pair), p10 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + 4u), pair);
-					const uint32_t p01 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4), pair), p11 = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (at + rw4 + 4u), pair);
-					// (u,v) (u+1,v) (u,v+1) (u+1,v+1) of slice sub -> w0, of slice sub + 1 -> w1
-					const uint32_t t0 = __builtin_amdgcn_perm(p10, p00, 0x05010400u), t1 = __builtin_amdgcn_perm(p11, p01, 0x05010400u);
+					const int sub = (__builtin_amdgcn_readlane(cells, lane) - first) & 15;              // the sample's cell inside the window (uniform)
+					const bool passed = FLIPS && __float_as_uint(kk) >= t_next;                         // some lane is at its second column from this sample on
+					if ((uint32_t) (sub - base) > 2u || passed) {
+						base = forward ? sub : (sub > 2 ? sub - 2 : 0);
+						const uint32_t qw = (uint32_t) base >> 2;
+						const uint32_t lo = qw == 0u ? o.x : (qw == 1u ? o.y : (qw == 2u ? o.z : o.w));
+						const uint32_t hi = qw == 0u ? o.y : (qw == 1u ? o.z : (qw == 2u ? o.w : nx));
+						group = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t) base & 3u);                  // byte i: slice base + i
+						if (FLIPS && passed) {
+							// t is monotone in k: a threshold that was passed is spent (+inf), and the wave waits for the smallest one left
+							const bool pu = k >= t_u, pv = k >= t_v;
+							at += (pu ? step_u : 0u) + (pv ? step_v : 0u);
+							t_u = pu ? __builtin_inff() : t_u; t_v = pv ? __builtin_inff() : t_v;
+							t_next = next_threshold();
+						}
+						if constexpr (kHoldCorners) exchange();
+					}
+					if constexpr (!kHoldCorners) exchange();
+					// (u,v) (u+1,v) (u,v+1) (u+1,v+1) of slice sub -> w0, of slice sub + 1 -> w1: bytes sub - base and sub - base + 1 of the four dwords
+					const uint32_t sel = 0x05010400u + (uint32_t) (sub - base) * 0x01010101u;
+					const uint32_t t0 = __builtin_amdgcn_perm(p10, p00, sel), t1 = __builtin_amdgcn_perm(p11, p01, sel);
 					sample(__builtin_amdgcn_perm(t1, t0, 0x05040100u), __builtin_amdgcn_perm(t1, t0, 0x07060302u));
 				});
 			}
