@@ -485,6 +485,60 @@ int vr_hip_render_hybrid_device(vr_ctx *ctx, const vr_params *params, const vr_i
 int vr_hip_render_hybrid(vr_ctx *ctx, const vr_params *params, const vr_iso *iso, uint8_t *host_rgba, float *host_depth /* may be NULL */);
 int vr_hip_backdrop_frames(vr_ctx *ctx, uint64_t *frames_out);         /* testing aid: composite frames launched on the backdrop kernels */
 
+/* ---- section: an oblique slice through the interpolated field and its thick-slab forms, with depth.  No reference counterpart. ----
+ * A section frame is the planar reformat of a volume viewer: the field on the plane n.x*x + n.y*y + n.z*z + d = 0 (POINT), or the maximum,
+ * minimum or mean of the field over the slab |n.x*x + n.y*y + n.z*z + d| <= h around it (slab MIP, MinIP, the X-ray-like average), coloured
+ * through the transfer function or a grey window.  It writes the depth layer of the isosurface frame, so it is the second producer of the
+ * layer a backdrop frame takes: vr_hip_render_section_in_volume is the slice inside the translucent volume, as the hybrid is for the
+ * isosurface.  The section is a per-call argument, not context state: vr_params and every other struct keep their size and layout.
+ * Per pixel:
+ *  1. Ray.  View::get_ray + Raycaster::intersect exactly as in vr_hip_render, then steps 1-3 of the clip contract under the context's clip.
+ *     As a backdrop frame does, a section frame always runs the clip's arithmetic, under the identity clip when none is set, which changes no
+ *     bit.  A miss gives pixel (0,0,0,0) and depth -1.
+ *  2. Plane, from the unreplaced dir, with the clip's two expressions: dn = fma(n.z, dir.z, fma(n.y, dir.y, n.x * dir.x)),
+ *     on = fma(n.z, o.z, fma(n.y, o.y, fma(n.x, o.x, d))).  dn == 0 is a miss in every mode: a ray parallel to the section has no section
+ *     point.  Otherwise kc = -on / dn by IEEE division.
+ *  3. Segment.  POINT: the pixel is a hit iff the ray was one and (kx <= kc) && (kc <= ky), ordered compares; the segment becomes [kc, kc].
+ *     Thick modes: ka = ((-h) - on) / dn, kb = (h - on) / dn, kx = flmax(kx, flmin(ka, kb)), ky = flmin(ky, flmax(ka, kb)) (intersect's
+ *     flmin / flmax), and the ray is a hit iff it was one and (kx < ky) && (ky > 0), the clip's test.
+ *  4. Samples.  k = kx; while (k <= ky) { v(k); k += ray_step; } — the MIP frame's sequence on the narrowed segment —, v the TRILINEAR (or
+ *     _Q8) interpolated RAW value at fma(k, A, B) with the A, B and lerps of the TRILINEAR mode.  POINT is the one sample v(kc).  The two
+ *     guards on ray_step look at the unnarrowed segment, as under a clip.  params.esl, ray_threshold, light_kd and light_pos are ignored:
+ *     every sample is fetched.
+ *  5. Value.  MAX: m = 0; m = raw > m ? raw : m.  MIN: m = +inf; m = raw < m ? raw : m.  MEAN: s = 0; s = s + raw in sample order, plain adds,
+ *     n counted; the value is s / (float) n by IEEE division (a hit has n >= 1).  POINT: v(kc).
+ *  6. Colour.  window == {0, 0}: the linearly filtered transfer-function lookup of the value with the arithmetic of a MIP pixel's lookup
+ *     (_Q8: rounded weight); the pixel is write_color of the premultiplied entry as stored.  Otherwise inv = 1.0f / (hi - lo), formed once on
+ *     the host, g = fmed3((value - lo) * inv, 0, 1) with the difference and the product rounded separately, and the pixel is
+ *     write_color(g, g, g, 1.0f): an opaque grey, which is what the backdrop wants as a layer.
+ *  7. Depth.  The layout of the isosurface's depth buffer.  POINT: kc.  Thick modes: the narrowed kx, the slab's front face.  Every other
+ *     pixel: -1, rows with gy >= height included.  The RGBA bytes do not depend on whether depth is asked for.
+ *     Raycaster::intersect clamps kx at 0, so a hit has kc >= kx >= 0: a section point behind a camera inside the cube is a miss, and the depth
+ *     of every hit reads as a surface to a backdrop frame (d >= 0.0f).
+ *  8. In volume.  vr_hip_render_section_in_volume_device is by definition vr_hip_render_section_device into dev_rgba and dev_depth (the
+ *     context-owned depth buffer of the hybrid when dev_depth is NULL), followed on the same stream by vr_hip_render_backdrop_device in
+ *     place.  The section pass ignores shadow, lighting and pre-integration; the composite pass sees them.  The depth returned is the
+ *     section's.  The host entry point mirrors vr_hip_render_hybrid.
+ *  9. What it reads.  What a clipped MIP frame of that view and sampling reads — quad bricks with the per-view plane, oct bricks for 2-byte
+ *     voxels, or the linear array —, never a run copy or a column window; vr_hip_set_wide_addressing, vr_hip_set_tile_mapping,
+ *     vr_hip_set_layout and vr_hip_set_brick_plane apply.  Tiles start in grid order.  Frames are counted by vr_hip_timing, described by
+ *     vr_hip_last_launch and counted by vr_hip_section_frames (testing aid).  Single device: the vr_hip_multi_* path has no section.
+ * 10. Errors.  VR_ERR_INVALID for a NULL section, a non-finite member, a normal of three zeros, mode > 3, half_width < 0, POINT with
+ *     half_width != 0, a thick mode with half_width == 0, a window that is neither {0, 0} nor hi > lo, and VR_SAMPLE_NEAREST: a section is
+ *     defined on the interpolated field.  Everything else as for vr_hip_render_iso*. */
+typedef enum vr_section_mode { VR_SECTION_POINT = 0, VR_SECTION_MAX = 1, VR_SECTION_MIN = 2, VR_SECTION_MEAN = 3 } vr_section_mode;
+typedef struct vr_section {
+	float    plane[4];    /* n.x, n.y, n.z, d: the section is n.x*x + n.y*y + n.z*z + d = 0, model space, cube [-1,1]^3 */
+	float    half_width;  /* h: the slab is |n.x*x + n.y*y + n.z*z + d| <= h (model units for a unit normal); 0 for POINT */
+	uint32_t mode;        /* vr_section_mode */
+	float    window[2];   /* lo, hi in RAW voxel units: grey window; both 0 = colour by the transfer function */
+} vr_section;             /* 32 bytes */
+int vr_hip_render_section(vr_ctx *ctx, const vr_params *params, const vr_section *section, uint8_t *host_rgba, float *host_depth /* may be NULL */);
+int vr_hip_render_section_device(vr_ctx *ctx, const vr_params *params, const vr_section *section, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
+int vr_hip_render_section_in_volume(vr_ctx *ctx, const vr_params *params, const vr_section *section, uint8_t *host_rgba, float *host_depth /* may be NULL */);
+int vr_hip_render_section_in_volume_device(vr_ctx *ctx, const vr_params *params, const vr_section *section, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
+int vr_hip_section_frames(vr_ctx *ctx, uint64_t *frames_out);          /* testing aid: section frames launched */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

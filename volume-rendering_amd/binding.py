@@ -100,6 +100,27 @@ class VrBackdrop(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("depth", C.c_void_p)]
 
 
+SECTION_POINT, SECTION_MAX, SECTION_MIN, SECTION_MEAN = 0, 1, 2, 3
+SECTION_MODES = {"point": SECTION_POINT, "max": SECTION_MAX, "min": SECTION_MIN, "mean": SECTION_MEAN}
+
+
+class VrSection(C.Structure):
+    """vr_section: the plane n.x*x + n.y*y + n.z*z + d = 0 in model space, the slab's half width (0 for POINT), the mode (SECTION_*) and the
+    grey window lo, hi in RAW voxel units (both 0 = colour by the transfer function)"""
+    _fields_ = [("plane", C.c_float * 4), ("half_width", C.c_float), ("mode", C.c_uint32), ("window", C.c_float * 2)]
+
+
+def make_section(plane, half_width=0.0, mode="point", window=None):
+    """A VrSection; mode by name ("point", "max", "min", "mean") or number, a missing window is {0, 0} (the transfer function)."""
+    sec = VrSection()
+    for i in range(4):
+        sec.plane[i] = float(plane[i])
+    sec.half_width = float(half_width)
+    sec.mode = SECTION_MODES[mode] if isinstance(mode, str) else int(mode)
+    sec.window[0], sec.window[1] = (0.0, 0.0) if window is None else (float(window[0]), float(window[1]))
+    return sec
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -180,6 +201,11 @@ def lib():
         "vr_hip_render_hybrid": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp]),
         "vr_hip_render_hybrid_device": (C.c_int, [vp, P(VrParams), P(VrIso), vp, vp, vp]),
         "vr_hip_backdrop_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_render_section": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp]),
+        "vr_hip_render_section_device": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp, vp]),
+        "vr_hip_render_section_in_volume": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp]),
+        "vr_hip_render_section_in_volume_device": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp, vp]),
+        "vr_hip_section_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

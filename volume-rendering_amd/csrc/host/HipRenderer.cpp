@@ -32,14 +32,14 @@ void HipRenderer::to_params(const Raycaster &r, vr_sampling sampling, vr_params 
 }
 
 HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, mirror_error_(nullptr) {
 	create_status_ = vr_hip_create(device, &ctx_);
 	if (create_status_ == 0)
 		prime(r);
 }
 
 HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, mirror_error_(nullptr) {
 	create_status_ = vr_hip_multi_create(n_devices, devices, &multi_);
 	if (create_status_ == 0)
 		prime(r);
@@ -143,7 +143,13 @@ int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 		mirror_error_ = "the hybrid renders on a single device (vr_hip_render_hybrid): construct the renderer without a device list";
 		return 1;
 	}
-	if (hybrid_) rc = device_buffer_ ? vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_hybrid(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
+	if (section_ && multi_) {
+		mirror_error_ = "a section frame renders on a single device (vr_hip_render_section): construct the renderer without a device list";
+		return 1;
+	}
+	if (section_ && section_in_volume_) rc = device_buffer_ ? vr_hip_render_section_in_volume_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section_in_volume(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
+	else if (section_) rc = device_buffer_ ? vr_hip_render_section_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
+	else if (hybrid_) rc = device_buffer_ ? vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_hybrid(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
 	else if (iso_) rc = device_buffer_ ? vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_iso(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
 	else if (mip_) rc = device_buffer_ ? vr_hip_render_mip_device(ctx_, &p, buffer, nullptr) : vr_hip_render_mip(ctx_, &p, (uint8_t *) buffer);
 	else if (multi_) rc = device_buffer_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_multi_render(multi_, &p, (uint8_t *) buffer);

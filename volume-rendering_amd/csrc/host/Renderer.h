@@ -88,16 +88,22 @@ class HipRenderer : public Renderer {
 		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
 		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
 		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
-		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = false; }
+		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = section_ = false; }
 		// on: render_volume() produces the shaded isosurface at `level` (raw voxel units) with `refine` bisection steps (vr_hip_render_iso;
 		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
-		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = false; }
+		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = section_ = false; }
 		// on: render_volume() produces the hybrid (vr_hip_render_hybrid): that isosurface seen through the translucent volume in front of it —
 		// the isosurface frame, then the composite frame stopped at its depth and blended over it; the composite pass sees the clip, the
 		// shadow, the lighting and the pre-integration of this renderer.  Needs a TRILINEAR sampling mode.  Excludes set_mip and set_iso:
 		// the one set last holds.  Single device only, like them.
-		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = false; }
+		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = section_ = false; }
+		// on: render_volume() produces the section frame (vr_hip_render_section): the oblique slice `section` through the interpolated field, or
+		// its thick-slab maximum, minimum or mean, coloured by the transfer function or the section's grey window; in_volume: that section seen
+		// through the translucent volume in front of it (vr_hip_render_section_in_volume: the composite pass sees the clip, the shadow, the
+		// lighting and the pre-integration of this renderer).  No depth comes back through this interface.  Needs a TRILINEAR sampling mode.
+		// Excludes set_mip, set_iso and set_hybrid: the one set last holds.  Single device only, like them.
+		void set_section(bool on, const vr_section &section, bool in_volume) { section_ = on; section_in_volume_ = in_volume; section_params_ = section; if (on) mip_ = iso_ = hybrid_ = false; }
 		// One composite frame over an opaque layer (vr_hip_render_backdrop / vr_hip_render_backdrop_device by the buffer flavour of this
 		// renderer): `layer` holds host or device pointers accordingly, view.dims pixels each.  Whatever set_mip / set_iso / set_hybrid say,
 		// this is a composite frame.  Single device only.  0 = ok, 1 = failure.
@@ -133,6 +139,9 @@ class HipRenderer : public Renderer {
 		bool iso_;
 		bool hybrid_;
 		vr_iso iso_params_;
+		bool section_;
+		bool section_in_volume_;
+		vr_section section_params_;
 		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
 };
 

@@ -5,7 +5,8 @@
 //   volr_bench [-h] [-f <file.pvm|.raw>] [-raw <w> <h> <d> [<bytes>]] [-synthetic <n>] [-dir <datasets>] [-r <id>]
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
 //              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
-//              [-phong <ka> <kd> <ks> <n>] [-preint] [-hybrid <level> [-refine <n>]] [-o <frame.ppm>]
+//              [-phong <ka> <kd> <ks> <n>] [-preint] [-hybrid <level> [-refine <n>]]
+//              [-section <nx> <ny> <nz> <d> [-section-half <h>] [-section-mode max|min|mean] [-section-window <lo> <hi>] [-section-in-volume]] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -54,6 +55,11 @@ void print_usage() {
 	       "  -hybrid <level> [-refine <n>] : the isosurface at <level> seen through the translucent volume in front of it (the isosurface frame, then\n"
 	       "         the composite stopped at its depth and blended over it), from the trilinear renderer (-r 1); single device; works alone and with\n"
 	       "         the clip, -shadow, -phong and -preint, which the composite pass sees; excludes -mip, -iso and -devices\n"
+	       "  -section <nx> <ny> <nz> <d> [-section-half <h>] [-section-mode max|min|mean] [-section-window <lo> <hi>] [-section-in-volume] : the section\n"
+	       "         nx*x + ny*y + nz*z + d = 0 through the interpolated field (model space); with -section-half h > 0 the maximum (default), minimum\n"
+	       "         or mean over the slab of that half width; -section-window: opaque grey between lo and hi (raw voxel units) instead of the transfer\n"
+	       "         function; -section-in-volume: the section seen through the translucent volume in front of it (the composite pass sees the clip,\n"
+	       "         -shadow, -phong and -preint); from the trilinear renderer (-r 1); single device; excludes -mip, -iso, -hybrid and -devices\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -256,6 +262,8 @@ int main(int argc, char **argv) {
 	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false, hybrid = false;
 	float iso_level = 0.0f;
 	int iso_refine = 4;
+	bool section_on = false, section_in_volume = false, section_mode_given = false, section_window_given = false;
+	vr_section section = { { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f, VR_SECTION_POINT, { 0.0f, 0.0f } };
 	bool clip_box = false, clip_plane = false;
 	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
 	int shadow_dims = 0;
@@ -301,6 +309,19 @@ int main(int argc, char **argv) {
 		else if (strcmp(arg, "-mip") == 0) mip = true;
 		else if (strcmp(arg, "-iso") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); iso = true; } }
 		else if (strcmp(arg, "-hybrid") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); hybrid = true; } }
+		else if (strcmp(arg, "-section") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) section.plane[k] = (float) atof(argv[++i]); section_on = true; } }
+		else if (strcmp(arg, "-section-half") == 0) { if (need(1)) section.half_width = (float) atof(argv[++i]); }
+		else if (strcmp(arg, "-section-mode") == 0) {
+			if (!need(1)) continue;
+			const char *m = argv[++i];
+			if (strcmp(m, "max") == 0) section.mode = VR_SECTION_MAX;
+			else if (strcmp(m, "min") == 0) section.mode = VR_SECTION_MIN;
+			else if (strcmp(m, "mean") == 0) section.mode = VR_SECTION_MEAN;
+			else { printf("%s error: Wrong parameters. Use -h to help.\n", arg); continue; }
+			section_mode_given = true;
+		}
+		else if (strcmp(arg, "-section-window") == 0) { if (need(2)) { section.window[0] = (float) atof(argv[++i]); section.window[1] = (float) atof(argv[++i]); section_window_given = true; } }
+		else if (strcmp(arg, "-section-in-volume") == 0) section_in_volume = true;
 		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
 		else if (strcmp(arg, "-clip-box") == 0) {
 			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
@@ -360,6 +381,21 @@ int main(int argc, char **argv) {
 		if (renderer_id != 1) { printf("Error: -hybrid needs the trilinear renderer (-r 1): its surface is defined on the interpolated field\n"); return EXIT_FAILURE; }
 		renderers[1]->set_hybrid(true, iso_level, (uint32_t) iso_refine);
 		printf("Hybrid: isosurface at level %g, %d bisection steps, behind the composite\n", iso_level, iso_refine);
+	}
+
+	if (section_on) {
+		if (!device_list.empty()) { printf("Error: -section renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		if (mip || iso || hybrid) { printf("Error: -section excludes -mip, -iso and -hybrid\n"); return EXIT_FAILURE; }
+		if (renderer_id != 1) { printf("Error: -section needs the trilinear renderer (-r 1): a section is defined on the interpolated field\n"); return EXIT_FAILURE; }
+		if (section.half_width > 0.0f && !section_mode_given) section.mode = VR_SECTION_MAX;      // a slab without a mode: the slab MIP
+		renderers[1]->set_section(true, section, section_in_volume);
+		static const char *const mode_names[] = { "point", "max", "min", "mean" };
+		printf("Section: plane %g x + %g y + %g z + %g = 0, half width %g, mode %s", section.plane[0], section.plane[1], section.plane[2], section.plane[3],
+		       section.half_width, mode_names[section.mode & 3u]);
+		if (section.window[0] != 0.0f || section.window[1] != 0.0f) printf(", grey window %g..%g", section.window[0], section.window[1]);
+		printf(section_in_volume ? ", behind the composite\n" : "\n");
+	} else if (section_in_volume || section_mode_given || section_window_given || section.half_width != 0.0f) {
+		printf("Error: -section-half, -section-mode, -section-window and -section-in-volume need -section\n"); return EXIT_FAILURE;
 	}
 
 	if (clip_box || clip_plane) {

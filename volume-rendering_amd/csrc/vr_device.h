@@ -385,6 +385,20 @@ hipError_t launch_mip(const RayKernelArgs &a, const void *linear, const void *br
 hipError_t launch_iso(const RayKernelArgs &a, const void *linear, const void *bricked, uint32_t bytes_per_voxel, const float *tf_premult,
                       const uint8_t *bounds, float level, uint32_t refine, void *out_rgba, void *out_depth, hipStream_t stream);
 
+// ---- section frames (include/vr_hip.h vr_hip_render_section) ----
+// The section of one frame, a kernel argument of its own behind the ones a MIP frame takes: vr_section with the window prepared.
+struct SectionArgs {
+	float    plane[4];                 // n.x, n.y, n.z, d
+	float    half_width;               // h (0 for VR_SECTION_POINT)
+	uint32_t mode;                     // vr_section_mode
+	uint32_t windowed;                 // 1: grey window, 0: colour by the transfer function
+	float    window_lo, window_inv;    // lo and 1.0f / (hi - lo), the division done once on the host
+};
+// One section frame.  `a`, `linear` and `bricked` as for launch_iso (the same rows: a.p.sampling TRILINEAR or TRILINEAR_Q8), the clip words of
+// `a` filled (the identity clip when none is set: the kernel always runs clip_segment); a.p.esl is not looked at.  out_depth may be NULL.
+hipError_t launch_section(const RayKernelArgs &a, const SectionArgs &section, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
+                          const float *tf_premult, void *out_rgba, void *out_depth, hipStream_t stream);
+
 // ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
 // What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
 struct ShadowBuildArgs {

@@ -118,6 +118,8 @@ struct vr_ctx {
 	// backdrop frames (vr_hip_render_backdrop / vr_hip_render_hybrid): backdrop_frames counts the composite frames on the composite_backdrop*
 	// kernels; the hybrid's depth buffer when the caller gives none and the staging of the host entry points' layers, grown on demand
 	uint64_t backdrop_frames = 0;
+	// section frames (vr_hip_render_section*): the frames launched on the section kernels
+	uint64_t section_frames = 0;
 	float *hybrid_depth = nullptr; size_t hybrid_depth_bytes = 0;
 	void *backdrop_stage = nullptr; size_t backdrop_stage_bytes = 0;
 #ifdef VR_BOUNDS_CHECK
@@ -1313,6 +1315,68 @@ int launch_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rg
 	return launch_frame(c, p, dev_rgba, stream, &layer);
 }
 
+// what the four section entry points check beyond render_preamble (include/vr_hip.h, step 10 of the section contract)
+int validate_section(vr_ctx *c, const vr_params *p, const vr_section *s) {
+	if (s == nullptr) return fail(c, VR_ERR_INVALID, "section is NULL");
+	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
+		return fail(c, VR_ERR_INVALID, "a section is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	for (int i = 0; i < 4; i++)
+		if (!std::isfinite(s->plane[i])) return fail(c, VR_ERR_INVALID, "section plane must be finite");
+	if (!std::isfinite(s->half_width) || !std::isfinite(s->window[0]) || !std::isfinite(s->window[1]))
+		return fail(c, VR_ERR_INVALID, "section half_width and window must be finite");
+	if (s->plane[0] == 0.0f && s->plane[1] == 0.0f && s->plane[2] == 0.0f) return fail(c, VR_ERR_INVALID, "section normal is zero");
+	if (s->mode > VR_SECTION_MEAN) return fail(c, VR_ERR_INVALID, "section mode must be in 0..3");
+	if (s->half_width < 0.0f) return fail(c, VR_ERR_INVALID, "section half_width must not be negative");
+	if (s->mode == VR_SECTION_POINT && s->half_width != 0.0f) return fail(c, VR_ERR_INVALID, "a POINT section has half_width 0");
+	if (s->mode != VR_SECTION_POINT && s->half_width == 0.0f) return fail(c, VR_ERR_INVALID, "a thick section needs half_width > 0");
+	if (!(s->window[0] == 0.0f && s->window[1] == 0.0f) && !(s->window[1] > s->window[0]))
+		return fail(c, VR_ERR_INVALID, "section window must be {0, 0} or hi > lo");
+	return VR_OK;
+}
+
+// One section frame (include/vr_hip.h vr_hip_render_section): what a clipped MIP frame of the same view and sampling reads and maps, with
+// esl off (every sample is fetched: no block maxima are built), another kernel.  volume_args has filled the clip words, the identity clip
+// when none is set.
+int launch_section_frame(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	vr_params q = *p;
+	q.esl = 0u;
+	SectionArgs sa;
+	memset(&sa, 0, sizeof sa);
+	for (int i = 0; i < 4; i++) sa.plane[i] = s->plane[i];
+	sa.half_width = s->half_width;
+	sa.mode = s->mode;
+	sa.windowed = (s->window[0] == 0.0f && s->window[1] == 0.0f) ? 0u : 1u;
+	sa.window_lo = s->window[0];
+	sa.window_inv = sa.windowed ? 1.0f / (s->window[1] - s->window[0]) : 0.0f;
+	const int rc = launch_full_march_frame(c, &q, stream, "section", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		return launch_section(a, sa, c->vol, brick_copy, c->bpv, c->tf, dev_rgba, dev_depth, stream);
+	});
+	if (rc == VR_OK) c->section_frames++;
+	return rc;
+}
+
+// The section in the volume (include/vr_hip.h): the section frame into dev_rgba and the depth buffer, then the backdrop frame in place, on one stream
+int launch_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	if (dev_depth == nullptr) {
+		if (const int rc = grow_buffer(c, (void **) &c->hybrid_depth, c->hybrid_depth_bytes, (size_t) p->out_width * p->out_rows * sizeof(float))) return rc;
+		dev_depth = c->hybrid_depth;
+	}
+	if (const int rc = launch_section_frame(c, p, s, dev_rgba, dev_depth, stream)) return rc;
+	const vr_backdrop layer = { dev_rgba, dev_depth };
+	return launch_frame(c, p, dev_rgba, stream, &layer);
+}
+
+// the depth buffer of the host entry points that hand a depth back (vr_hip_render_iso, vr_hip_render_section): one float per pixel of the
+// window, sized with the window (render_preamble: the frame fits), allocated on first use behind the context's frames
+int size_host_depth(vr_ctx *c) {
+	if (c->iso_depth_bytes == c->fb_bytes) return VR_OK;
+	VR_TRY(c, drain(c));
+	if (c->iso_depth) { (void) hipFree(c->iso_depth); c->iso_depth = nullptr; c->iso_depth_bytes = 0; }
+	VR_TRY(c, hipMalloc((void **) &c->iso_depth, c->fb_bytes));
+	c->iso_depth_bytes = c->fb_bytes;
+	return VR_OK;
+}
+
 // ... and what the two host-buffer ones end with: the frame in host memory (where the reference's timed region ends, GPURenderer1.cu:107-110)
 // and the time since t0
 void take_total_time(vr_ctx *c, std::chrono::steady_clock::time_point t0) {
@@ -1747,12 +1811,7 @@ int vr_hip_render_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t 
 	rc = validate_iso(c, p, iso);
 	if (rc) return rc;
 	const size_t pixels = (size_t) p->out_width * p->out_rows;
-	if (host_depth != nullptr && c->iso_depth_bytes != c->fb_bytes) {      // sized with the window (render_preamble: the frame fits)
-		VR_TRY(c, drain(c));
-		if (c->iso_depth) { (void) hipFree(c->iso_depth); c->iso_depth = nullptr; c->iso_depth_bytes = 0; }
-		VR_TRY(c, hipMalloc((void **) &c->iso_depth, c->fb_bytes));
-		c->iso_depth_bytes = c->fb_bytes;
-	}
+	if (host_depth != nullptr) { const int sized = size_host_depth(c); if (sized) return sized; }
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = launch_iso_frame(c, p, iso, c->fb, host_depth ? c->iso_depth : nullptr, c->stream);
 	if (rc) return rc;
@@ -1808,6 +1867,53 @@ int vr_hip_render_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8
 int vr_hip_backdrop_frames(vr_ctx *c, uint64_t *frames_out) {
 	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
 	*frames_out = c->backdrop_frames;
+	return VR_OK;
+}
+
+// ---- section frames (include/vr_hip.h vr_section) ----
+
+int vr_hip_render_section_device(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_section(c, p, s)) return rc;
+	return launch_section_frame(c, p, s, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_section(vr_ctx *c, const vr_params *p, const vr_section *s, uint8_t *host_rgba, float *host_depth) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_section(c, p, s);
+	if (rc) return rc;
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	if (host_depth != nullptr) { const int sized = size_host_depth(c); if (sized) return sized; }
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_section_frame(c, p, s, c->fb, host_depth ? c->iso_depth : nullptr, c->stream);
+	if (rc) return rc;
+	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->iso_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+
+int vr_hip_render_section_in_volume_device(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_section(c, p, s)) return rc;
+	return launch_section_in_volume(c, p, s, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *s, uint8_t *host_rgba, float *host_depth) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_section(c, p, s);
+	if (rc) return rc;
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_section_in_volume(c, p, s, c->fb, nullptr, c->stream);       // (the context's own depth buffer)
+	if (rc) return rc;
+	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->hybrid_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+
+int vr_hip_section_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->section_frames;
 	return VR_OK;
 }
 

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrBackdrop, VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_shadow
+from .binding import VrBackdrop, VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_section, make_shadow
 
 
 class HipRenderer:
@@ -305,6 +305,52 @@ class HipRenderer:
         """vr_hip_backdrop_frames: the composite frames this context launched on the backdrop kernels"""
         n = C.c_uint64(0)
         self._check(self._L.vr_hip_backdrop_frames(self._ctx, C.byref(n)), "backdrop_frames")
+        return int(n.value)
+
+    # -- section frames (vr_hip_render_section: the oblique slice through the interpolated field, its thick-slab MIP / MinIP / mean, with depth)
+    def render_section(self, params, plane, half_width=0.0, mode="point", window=None, depth=False):
+        """Host-buffer flavour: the section n.x*x + n.y*y + n.z*z + d = 0 (`plane` = (n.x, n.y, n.z, d), model space) as an
+        (out_rows, out_width, 4) uint8 array, or with depth=True (rgba, depth): depth is float32 (out_rows, out_width), k of the section
+        point (thick modes: of the slab's front face) on the pixel's own ray, -1 where there is none.  mode "point", or with half_width > 0
+        "max", "min", "mean" over the slab; window (lo, hi) in raw voxel units = opaque grey, None = the transfer function.
+        params.sampling must be one of the TRILINEAR modes."""
+        sec = make_section(plane, half_width, mode, window)
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
+        self._check(self._L.vr_hip_render_section(self._ctx, C.byref(params), C.byref(sec), out.ctypes.data, dep.ctypes.data if depth else None), "render_section")
+        return (out, dep) if depth else out
+
+    def render_section_device(self, params, plane, half_width, mode, window, dev_ptr, depth_ptr=None, stream=None):
+        """Device-buffer flavour: asynchronous launch into `dev_ptr` (RGBA8) and, if given, `depth_ptr` (float32) on `stream` (raw hipStream_t or None)."""
+        sec = make_section(plane, half_width, mode, window)
+        self._check(self._L.vr_hip_render_section_device(self._ctx, C.byref(params), C.byref(sec), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
+                                                         C.c_void_p(stream) if stream else None), "render_section_device")
+
+    def render_section_in_volume(self, params, plane, half_width=0.0, mode="point", window=None, depth=False):
+        """Host-buffer flavour of the section inside the volume: render_section with the same arguments seen through the translucent volume
+        in front of it (the context's clip, shadow, lighting and pre-integration apply to the composite pass).  An (out_rows, out_width, 4)
+        uint8 array, or with depth=True (rgba, depth): the section's depth."""
+        sec = make_section(plane, half_width, mode, window)
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_section_in_volume(self._ctx, C.byref(params), C.byref(sec), out.ctypes.data, dep.ctypes.data if depth else None),
+                    "render_section_in_volume")
+        return (out, dep) if depth else out
+
+    def render_section_in_volume_device(self, params, plane, half_width, mode, window, dev_ptr, depth_ptr=None, stream=None):
+        """Device-buffer flavour: the section frame into `dev_ptr` and `depth_ptr` (a context-owned buffer when None), then the backdrop frame
+        in place, both on `stream` (raw hipStream_t or None)."""
+        sec = make_section(plane, half_width, mode, window)
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_section_in_volume_device(self._ctx, C.byref(params), C.byref(sec), C.c_void_p(dev_ptr),
+                                                                   C.c_void_p(depth_ptr) if depth_ptr else None, C.c_void_p(stream) if stream else None),
+                    "render_section_in_volume_device")
+
+    def section_frames(self):
+        """vr_hip_section_frames: the section frames this context launched"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_section_frames(self._ctx, C.byref(n)), "section_frames")
         return int(n.value)
 
     # -- timing (Profiler.cpp:46-67)
