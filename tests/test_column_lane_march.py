@@ -17,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_feature import BOUNDS_LIB
 from helpers import ColumnScene, column_params, smooth_noisy_volume, voxel_windows_fit
 from test_column_edges import OBLIQUE_POSES, _check_frame, _open_tf, _oracle_frame, _policy_restored, _sample_ratio, _thin_base_tf, _what
 
@@ -26,7 +27,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from lane_march_waves import mixed_entry_waves  # noqa: E402
 
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
 LANE_DEPTH = 6                                  # kColLaneDepth (VR_COL_LANE_DEPTH) of csrc/vr_kernels.hip
 BUFFER = 128
 MIXED_POSE = (180.0, 90.0, 0.0)

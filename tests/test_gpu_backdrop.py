@@ -3,9 +3,6 @@ kernel families render is held byte for byte against backdrop_render / hybrid_re
 include/vr_hip.h restated with the CPU oracle's statics — no tolerance anywhere.  tests/test_backdrop_model.py ties that restatement to the pinned composites and shows that the frames
 compared here tell three wrong readings of the contract apart."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +10,7 @@ import pytest
 from backdrop_helpers import BACKDROP_VOLUMES, HYBRID_LEVELS, BackdropRef, synthetic_layer, tier_frames
 from clip_helpers import CLIPS, set_clip
 from feature_random import EDGE_DTYPES, EDGE_SHAPES, edge_scene
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import PATH_VOLUMES, diff, expected_bands, load, needs_bounds_lib, reset_context, run_driver, run_under_bounds_build, sweep_paths
 from iso_helpers import IsoRef, depth_bits, frame_params
 from light_helpers import LIGHTINGS, PHONG
 from light_helpers import lit_views as backdrop_views
@@ -32,27 +29,11 @@ def volumes(golden):
 
 
 @pytest.fixture(autouse=True)
-def state_off_afterwards(gpu):
-    """the context is shared by the whole session: no test leaves the pre-integration, a lighting, a shadow, a clip or a forced path behind"""
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
     yield
-    gpu.clear_preintegration()
-    gpu.clear_lighting()
-    gpu.clear_shadow()
-    gpu.clear_clip()
-    gpu.set_tile_mapping(-1)
-    gpu.set_tile_scheduling(1)
-    gpu.set_wide_addressing(0)
-    gpu.set_brick_plane(-1)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def load(gpu, vox, tf, esl, window=(128, 128)):
-    gpu.set_window_buffer(*window)
-    gpu.set_transfer_fn(tf, esl)
-    gpu.set_volume(vox)
+    reset_context(vr, gpu)
 
 
 def backdrop_launch(gpu, info):
@@ -117,7 +98,7 @@ def test_every_path_agrees(vr, gpu, golden, oracle, volumes):
     every lane order x wave shape x two phases, tile scheduling 0 / 1 / 2 — the restatement's bytes, never a run copy or a column window,
     never a measured order; u8 and u16 (oct bricks); the cue-lit family and, under a lighting, the lit one"""
     ref = BackdropRef.instance()
-    for name, expect in (("blob_40x24x56", {0, 1}), ("random_u16", {0, 1, 5})):
+    for name, expect in PATH_VOLUMES:
         views = [v for v in backdrop_views(vr, golden, name) if v[0] in ("view0", "view1", "view6")]
         cases = []
         for k, (label, view) in enumerate(views):
@@ -140,37 +121,7 @@ def test_every_path_agrees(vr, gpu, golden, oracle, volumes):
                     assert diff(out, expected) == 0, (name, what, label, sampling, lighting, diff(out, expected), info)
                     assert backdrop_launch(gpu, info), (name, what, label, sampling, info)
                     seen.add(info["layout"])
-        try:
-            for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
-                gpu.set_layout(layout)
-                check(("layout", layout))
-                if layout == vr.LAYOUT_LINEAR:
-                    gpu.set_wide_addressing(1)
-                    check(("layout", layout, "wide"))
-                    gpu.set_wide_addressing(0)
-            for plane in (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-                gpu.set_brick_plane(plane)
-                check(("plane", plane))
-            gpu.set_brick_plane(-1)
-            for wide in (0, 1, 2, 4):
-                gpu.set_wide_addressing(wide)
-                check(("wide", wide))
-            gpu.set_wide_addressing(0)
-            for order in range(3):
-                for shape in range(3):
-                    for phase in ((0, 0), (3, 5)):
-                        gpu.set_tile_mapping(order + 4 * shape, *phase)
-                        check(("mapping", order, shape, phase))
-            gpu.set_tile_mapping(-1)
-            for mode in (0, 1, 2):
-                gpu.set_tile_scheduling(mode)
-                check(("scheduling", mode))
-        finally:
-            gpu.set_tile_scheduling(1)
-            gpu.set_tile_mapping(-1)
-            gpu.set_wide_addressing(0)
-            gpu.set_brick_plane(-1)
-            gpu.set_layout(vr.LAYOUT_BRICKED)
+        sweep_paths(vr, gpu, check)
         assert seen == expect, (name, seen)
 
 
@@ -198,8 +149,7 @@ def test_bands_crop_and_in_place(vr, gpu, golden, oracle, volumes):
         band_rgba = rng.integers(0, 256, size=(rows, 120, 4), dtype=np.uint8)
         band_depth = np.where(rng.random(size=(rows, 120)) < 0.5, np.float32(1.5), np.float32(np.nan)).astype(np.float32)
         band_rgba[inside], band_depth[inside] = rgba[gy[inside]], depth[gy[inside]]
-        expected = np.zeros((rows, 120, 4), np.uint8)
-        expected[inside] = want[gy[inside]]
+        expected = expected_bands(want, first, 2, 3, rows)
         beyond = ~inside[:, None] & (band_depth >= 0)
         expected[beyond] = band_rgba[beyond]
         out = gpu.render_backdrop(p, band_rgba, band_depth)
@@ -473,45 +423,30 @@ def test_errors_and_what_ignores_it(vr, gpu, golden, oracle, volumes):
     assert gpu.backdrop_frames() == count
 
 
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
-
-
-@pytest.mark.skipif(not os.path.exists(BOUNDS_LIB), reason="build_variants/libvr_hip_bounds.so not built (scripts/build_variant.sh bounds -DVR_BOUNDS_CHECK)")
+@needs_bounds_lib
 def test_backdrop_frames_under_the_bounds_checked_build():
     """A subset of this file once in a child process with the -DVR_BOUNDS_CHECK library (tests/test_gpu_bounds.py): every gather address is
     held against its array — a violation fails the frame (VrError) — and the bytes still equal the restatement"""
-    env = dict(os.environ, VR_HIP_LIB=BOUNDS_LIB)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q",
-                        "-k", "edge_shapes or every_path or all_four_states or hybrid_with_every_state or (frames_equal and bucky)"],
-                       capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
-    assert r.returncode == 0 and "7 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    run_under_bounds_build(__file__, "edge_shapes or every_path or all_four_states or hybrid_with_every_state or (frames_equal and bucky)", 7, timeout=900)
 
 
 def test_driver_hybrid_flag(golden, tmp_path):
     """volr_bench -hybrid (HipRenderer::set_hybrid through the host mirror): Bucky.pvm, TRILINEAR, pose (-45,-45,0) at distance 2,
     256 x 256 — the restatement's frame; with -shadow 17 -phong 0.25 0.65 0.4 4 -preint the composite pass sees all three"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
     vox = np.ascontiguousarray(golden.voxels("bucky"))
     st = golden.volume_state("bucky")
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     p = golden.params(case, 1)
     ref = BackdropRef.instance()
     q = ShadowRef.instance().build(tuple(p.view.light_pos), 17, p.ray_step, vox, st["tf"])
-    header = b"P6\n256 256\n255\n"
     level = HYBRID_LEVELS["bucky"]
     for extra, mode, lighting, grid in (([], POINT, None, None), (["-shadow", "17", "-phong", "0.25", "0.65", "0.4", "4", "-preint"], SLAB, PHONG, q)):
-        ppm = tmp_path / "hybrid.ppm"
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", "-hybrid", str(level), *extra,
-                              "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+        out, rgb = run_driver(tmp_path, "-hybrid", str(level), *extra)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "Hybrid: isosurface at level" in out.stdout
-        data = ppm.read_bytes()
-        assert data.startswith(header)
-        rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
         want, _, iso = ref.hybrid(p, vox, st["tf"], st["esl"], level, 4, mode, lighting=lighting, q=grid, strength=1.0)
         assert np.array_equal(rgb, want[..., :3]), (extra, int((rgb != want[..., :3]).any(axis=-1).sum()))
         assert diff(want, iso) > 1000 and diff(want, ref.render(p, vox, st["tf"], st["esl"], None, None, mode, lighting=lighting, q=grid)) > 1000
     for bad in (["-mip"], ["-iso", "100"], ["-devices", "0,0"], ["-r", "0"]):
-        args = [a for a in ["-r", "1"] if "-r" not in bad] + bad
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), *args, "-s", "128", "128", "-hybrid", str(level)], capture_output=True, text=True, timeout=300)
+        out, _ = run_driver(tmp_path, *bad, "-hybrid", str(level), size=(128, 128), pose=None, renderer=None if "-r" in bad else "1", output=None)
         assert out.returncode != 0 and "Error: -hybrid" in out.stdout, (bad, out.stdout)

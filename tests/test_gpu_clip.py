@@ -3,14 +3,12 @@ isosurface with depth — is held byte for byte / bit for bit against the clip_*
 restated with the CPU oracle's statics and the segment of every ray narrowed as include/vr_hip.h defines it.  tests/test_clip_model.py ties that restatement to the pinned
 ones and shows that the frames compared here are neither empty nor unclipped."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from clip_helpers import BOTH, BOX, CLIPS, IDENTITY, NOTHING, PLANE, ClipRef, composite_params, parallel_plane, set_clip
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import assert_order_repeats, depth_diff, diff, expected_bands, load, multi_pair, reset_context, run_driver, sweep_paths
 from iso_helpers import PAIRS, all_volumes, depth_bits, frame_params, views_for
 from mip_helpers import ramp_tf
 
@@ -33,24 +31,11 @@ def tf():
 
 
 @pytest.fixture(autouse=True)
-def clip_off_afterwards(gpu):
-    """the context is shared by the whole session: no test leaves a clip behind"""
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
     yield
-    gpu.clear_clip()
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def depth_diff(a, b):
-    return int((depth_bits(a) != depth_bits(b)).sum())
-
-
-def load(gpu, vox, tf, esl=None):
-    gpu.set_window_buffer(128, 128)
-    gpu.set_transfer_fn(tf, np.zeros(1024, np.uint32) if esl is None else esl)
-    gpu.set_volume(vox)
+    reset_context(vr, gpu)
 
 
 @pytest.mark.parametrize("clip_name", sorted(CLIPS))
@@ -159,8 +144,8 @@ def test_axis_aligned_views_leave_the_column_march_and_return_to_it(vr, gpu, gol
 
 
 def test_every_path_agrees_under_both(vr, gpu, golden, oracle, volumes):
-    """Placement and addressing only: linear / bricked, forced planes -1 and 0-9, wide addressing 0 / 1 / 2, every lane order x wave shape
-    x two phases — the restatement's bytes, and never a run copy or a column window"""
+    """Placement and addressing only: linear / bricked, forced planes -1 and 0-9, wide addressing 0 / 1 / 2 / +4, every lane order x wave
+    shape x two phases, tile scheduling 0 / 1 / 2 — the restatement's bytes, and never a run copy or a column window"""
     name = "blob_40x24x56"
     vox, ref = volumes[name], ClipRef.instance()
     views = [v for v in views_for(vr, golden, name) if v[0] in ("view0", "view1", "view6")]
@@ -180,28 +165,7 @@ def test_every_path_agrees_under_both(vr, gpu, golden, oracle, volumes):
             assert diff(out, want) == 0, (what, label, sampling, diff(out, want), info)
             assert info["layout"] not in (2, 3, 6, 7), (what, label, sampling, info)
             seen.add(info["layout"])
-    try:
-        for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
-            gpu.set_layout(layout)
-            check(("layout", layout))
-        for plane in (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-            gpu.set_brick_plane(plane)
-            check(("plane", plane))
-        gpu.set_brick_plane(-1)
-        for wide in (0, 1, 2):
-            gpu.set_wide_addressing(wide)
-            check(("wide", wide))
-        gpu.set_wide_addressing(0)
-        for order in range(3):
-            for shape in range(3):
-                for phase in ((0, 0), (3, 5)):
-                    gpu.set_tile_mapping(order + 4 * shape, *phase)
-                    check(("mapping", order, shape, phase))
-    finally:
-        gpu.set_tile_mapping(-1)
-        gpu.set_wide_addressing(0)
-        gpu.set_brick_plane(-1)
-        gpu.set_layout(vr.LAYOUT_BRICKED)
+    sweep_paths(vr, gpu, check)
     assert seen == {0, 1, 4}, seen              # linear array, quad bricks, voxel bricks (NEAREST)
 
 
@@ -219,11 +183,7 @@ def test_tile_scheduling_repeats_and_a_second_clip(vr, gpu, golden, oracle, volu
         set_clip(gpu, clip)
         want = ref.composite(p, vox, ctf, esl, clip)
         assert want.any()
-        ordered = 0
-        for k in range(4):
-            assert diff(gpu.render_volume(p), want) == 0, (clip, k)
-            ordered += gpu.last_launch()["ordered"]
-        assert ordered >= 3, ordered                            # (the first frame of a clip runs in the estimated order or in none)
+        assert_order_repeats(gpu, lambda: gpu.render_volume(p), want, what=(clip,))
 
 
 def test_screen_partition(vr, gpu, golden, oracle, volumes, tf):
@@ -246,13 +206,12 @@ def test_screen_partition(vr, gpu, golden, oracle, volumes, tf):
     q.esl = 0                                                   # (the composite would leap by the ESL bits, which are all zero here: nothing to leap)
     out_dvr = gpu.render_volume(q)
     out_iso, depth = gpu.render_iso(p, 100.0, REFINE, depth=True)
-    assert out_dvr.shape[0] == per_rank * 16
-    for ly in range(out_dvr.shape[0]):
-        gy = ((ly // 16) * 3 + 1) * 16 + ly % 16
-        inside = gy < 72
-        assert np.array_equal(out_dvr[ly], want_dvr[gy] if inside else np.zeros_like(want_dvr[0])), (ly, gy)
-        assert np.array_equal(out_iso[ly], want_iso[gy] if inside else np.zeros_like(want_iso[0])), (ly, gy)
-        assert np.array_equal(depth_bits(depth[ly]), depth_bits(want_depth[gy] if inside else np.full(120, -1, np.float32))), (ly, gy)
+    rows = per_rank * 16
+    assert out_dvr.shape[0] == rows
+    for kind, got, whole_frame in (("composite", out_dvr, want_dvr), ("iso", out_iso, want_iso)):
+        expected = expected_bands(whole_frame, 1, 3, 16, rows)
+        assert np.array_equal(got, expected), (kind, np.flatnonzero((got != expected).any(axis=(1, 2))))      # (the local rows that differ)
+    assert depth_diff(depth, expected_bands(want_depth, 1, 3, 16, rows, beyond=-1)) == 0
     crop = unskipped.copy()
     crop.x0, crop.out_width = 24, 40
     assert np.array_equal(gpu.render_volume(crop), want_dvr[:, 24:64])
@@ -318,12 +277,7 @@ def test_multi_device_frames_are_clipped(vr, gpu, golden, oracle, volumes, monke
     name = "bucky"
     vox, ref = volumes[name], ClipRef.instance()
     view = vr.benchmark_view(120, 72, 5)
-    monkeypatch.setenv("VR_MULTI_TRANSPORT", transport)
-    monkeypatch.setenv("VR_MULTI_SELFCHECK", "1")
-    m = vr.MultiRenderer([0, 0])
-    try:
-        assert m.transport == ("peer-copy" if transport == "peer" else "rccl-self")
-        m.set_window_buffer(120, 72)
+    with multi_pair(vr, monkeypatch, transport) as m:
         for sampling in (0, 1):
             p, ctf, esl = composite_params(vr, golden, oracle, name, vox, view, sampling, False)
             if sampling == 0:
@@ -341,33 +295,23 @@ def test_multi_device_frames_are_clipped(vr, gpu, golden, oracle, volumes, monke
         with pytest.raises(vr.VrError) as e:
             m.set_clip(box_min=(0, 0, 0), box_max=(0, 1, 1))
         assert e.value.code == 1
-    finally:
-        m.close()
 
 
 def test_driver_clip_flags(golden, tmp_path):
     """volr_bench -clip-plane / -clip-box (HipRenderer::set_clip through the host mirror): Bucky.pvm, TRILINEAR, pose (-45,-45,0) at
     distance 2, 256 x 256 — the composite, and once more with -iso 100"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
     vox = np.ascontiguousarray(golden.voxels("bucky"))
     st = golden.volume_state("bucky")
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     p = golden.params(case, 1)
-    header = b"P6\n256 256\n255\n"
     for extra, expect in (([], lambda clip: ClipRef.instance().composite(p, vox, st["tf"], st["esl"], clip)),
                           (["-iso", "100"], lambda clip: ClipRef.instance().iso(p, vox, st["tf"], 100.0, 4, clip)[0])):
         for flags, clip in ((["-clip-plane"] + [repr(float(np.float32(v))) for v in PLANE[2]], PLANE),
                             (["-clip-box"] + [str(v) for v in BOX[0] + BOX[1]], BOX)):
-            ppm = tmp_path / "clip.ppm"
-            out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", *extra, *flags,
-                                  "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+            out, rgb = run_driver(tmp_path, *extra, *flags)
             assert out.returncode == 0, out.stdout + out.stderr
             assert "Clip region" in out.stdout
-            data = ppm.read_bytes()
-            assert data.startswith(header)
-            rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
             want = expect(clip)
             assert want.any() and np.array_equal(rgb, want[..., :3]), (extra, flags)
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-s", "128", "128", "-clip-box", "0", "0", "0", "0", "1", "1", "-o", str(tmp_path / "x.ppm")],
-                         capture_output=True, text=True, timeout=300)
+    out, _ = run_driver(tmp_path, "-clip-box", "0", "0", "0", "0", "1", "1", size=(128, 128), pose=None, renderer=None)
     assert out.returncode != 0 and "box_min" in out.stdout

@@ -6,16 +6,12 @@ shadow_* and light_render entry points); and, on the same frames, the pre-integr
 layer and the hybrid of isosurface and volume against its slab_render, backdrop_render and hybrid_render.  tests/feature_random.py draws
 the frames; tests/test_feature_random_model.py ties the restatements to one another on them
 and shows that they are neither empty nor untouched by the feature.  Other seeds: VR_TEST_SEED=... pytest -m gpu tests/test_gpu_feature_random.py"""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import feature_random as fr
 from clip_helpers import IDENTITY, ClipRef, set_clip
-from helpers import ROOT
+from gpu_feature import depth_diff, diff, load, needs_bounds_lib, reset_context, run_under_bounds_build
 from iso_helpers import depth_bits
 from light_helpers import LightRef
 from shadow_helpers import CUTOFF, ShadowRef
@@ -26,31 +22,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(autouse=True)
 def state_off_afterwards(vr, gpu):
-    """the context is shared by the whole session: no test leaves the pre-integration, a lighting, a shadow, a clip, a layout or a forced path behind"""
+    """the context is shared by the whole session: no test leaves a state, a layout or a forced path behind"""
     yield
-    gpu.clear_preintegration()
-    gpu.clear_lighting()
-    gpu.clear_shadow()
-    gpu.clear_clip()
-    gpu.set_layout(vr.LAYOUT_BRICKED)
-    gpu.set_wide_addressing(0)
-    gpu.set_tile_mapping(-1)
-    gpu.set_tile_scheduling(1)
-    gpu.set_brick_plane(-1)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def depth_diff(a, b):
-    return int((depth_bits(a) != depth_bits(b)).sum())
-
-
-def load(gpu, scene, window):
-    gpu.set_window_buffer(*window)
-    gpu.set_transfer_fn(scene.tf, scene.esl)
-    gpu.set_volume(scene.vox)
+    reset_context(vr, gpu)
 
 
 def set_shadow_of(gpu, f, strength=None):
@@ -98,7 +72,7 @@ def test_random_scenes_match_the_restatements(vr, gpu, oracle):
     for scene in fr.random_scenes(oracle, vr):
         gpu.set_layout(scene.layout)
         gpu.set_wide_addressing(scene.wide)
-        load(gpu, scene, (70, 50))
+        load(gpu, scene.vox, scene.tf, scene.esl, (70, 50))
         for i, f in enumerate(scene.frames):
             what = (scene.describe(), "layout", scene.layout, "wide", scene.wide, "frame", i, "persp", f.p.view.perspective)
             e = check_frame(vr, gpu, scene, f, what)
@@ -123,7 +97,7 @@ def test_edge_shapes_match_the_restatements(vr, gpu, oracle, shape, dtype):
     scene = fr.edge_scene(oracle, vr, shape, dtype)
     for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
         gpu.set_layout(layout)
-        load(gpu, scene, fr.EDGE_SIZE)
+        load(gpu, scene.vox, scene.tf, scene.esl, fr.EDGE_SIZE)
         for f in scene.frames:
             check_frame(vr, gpu, scene, f, (shape, dtype, "layout", layout, "view", f.view, f.clip_name))
     assert len(scene.frames) == 6
@@ -274,7 +248,7 @@ def test_random_scenes_slab_backdrop_hybrid(vr, gpu, oracle):
     for s, scene in enumerate(fr.random_scenes(oracle, vr)):
         gpu.set_layout(scene.layout)
         gpu.set_wide_addressing(scene.wide)
-        load(gpu, scene, (70, 50))
+        load(gpu, scene.vox, scene.tf, scene.esl, (70, 50))
         for i, f in enumerate(scene.frames):
             what = (scene.describe(), "layout", scene.layout, "wide", scene.wide, "frame", i, "persp", f.p.view.perspective, (f.p.view.width, f.p.view.height))
             e = check_layer_frame(vr, gpu, scene, f, fr.layer_salt(s, i), what, i, in_place=i == 0)
@@ -300,7 +274,7 @@ def test_holed_scenes_slab_backdrop_hybrid(vr, gpu, oracle):
     for s, scene in enumerate(fr.holed_scenes(oracle, vr)):
         gpu.set_layout(scene.layout)
         gpu.set_wide_addressing(scene.wide)
-        load(gpu, scene, (70, 50))
+        load(gpu, scene.vox, scene.tf, scene.esl, (70, 50))
         for i, f in enumerate(scene.frames):
             what = (scene.describe(), "layout", scene.layout, "wide", scene.wide, "frame", i, "persp", f.p.view.perspective, (f.p.view.width, f.p.view.height))
             e = check_layer_frame(vr, gpu, scene, f, fr.layer_salt(200 + s, i), what, i, in_place=i == 0)
@@ -317,7 +291,7 @@ def test_edge_shapes_hybrid(vr, gpu, oracle, shape, dtype):
     scene = fr.edge_scene(oracle, vr, shape, dtype)
     for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
         gpu.set_layout(layout)
-        load(gpu, scene, fr.EDGE_SIZE)
+        load(gpu, scene.vox, scene.tf, scene.esl, fr.EDGE_SIZE)
         for f in scene.frames:
             what = (shape, dtype, "layout", layout, "view", f.view, f.clip_name)
             e = fr.ExpectedLayers(scene, f)
@@ -484,7 +458,7 @@ def test_random_frames_partitioned(vr, gpu, oracle):
                 break
             f = fr.random_frame(rng, vr, scene)
         assert f.p.view.height >= 8 and e.lit.any(), n
-        load(gpu, scene, (70, 50))
+        load(gpu, scene.vox, scene.tf, scene.esl, (70, 50))
         set_clip(gpu, f.clip)
         w, h = f.p.view.width, f.p.view.height
         kinds = [("lit", f.p, e.lit, None)]
@@ -544,7 +518,7 @@ def test_random_slab_and_hybrid_frames_partitioned(vr, gpu, oracle):
                 break
             f = fr.random_frame(rng, vr, scene)
         assert f.p.view.height >= 8 and f.p.view.width >= 8 and e.slab_all.any(), n
-        load(gpu, scene, (70, 50))
+        load(gpu, scene.vox, scene.tf, scene.esl, (70, 50))
         set_clip(gpu, f.clip)
         w, h = f.p.view.width, f.p.view.height
         nothing, no_depth = np.zeros((w, 4), np.uint8), np.full(w, -1, np.float32)
@@ -589,17 +563,13 @@ def test_random_slab_and_hybrid_frames_partitioned(vr, gpu, oracle):
     assert checked >= 4 * 3 * 3
 
 
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
 EDGE_CASES = len(fr.EDGE_SHAPES) * len(fr.EDGE_DTYPES)
 
 
-@pytest.mark.skipif(not os.path.exists(BOUNDS_LIB), reason="build_variants/libvr_hip_bounds.so not built (scripts/build_variant.sh bounds -DVR_BOUNDS_CHECK)")
+@needs_bounds_lib
 def test_under_the_bounds_checked_build():
     """The random scenes and the edge shapes (the slab, backdrop and hybrid frames among them) once in a child process with the -DVR_BOUNDS_CHECK library (tests/test_gpu_bounds.py): every
     gather address — the gradient fetches at the faces, the tail bricks, the padded address tables of an extent of 1 — is held against its
     array.  A violation fails the frame (VrError); nothing faults; the bytes still equal the restatements."""
-    env = dict(os.environ, VR_HIP_LIB=BOUNDS_LIB)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q",
-                        "-k", "random_scenes_match or edge_shapes_match or random_scenes_slab or holed_scenes or edge_shapes_hybrid"],
-                       capture_output=True, text=True, env=env, timeout=1200, cwd=ROOT)
-    assert r.returncode == 0 and f"{3 + 2 * EDGE_CASES} passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    run_under_bounds_build(__file__, "random_scenes_match or edge_shapes_match or random_scenes_slab or holed_scenes or edge_shapes_hybrid", 3 + 2 * EDGE_CASES,
+                           timeout=1200)

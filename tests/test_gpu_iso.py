@@ -3,13 +3,11 @@ HIP path renders is held byte for byte / bit for bit against iso_render of tests
 which tests/test_iso_model.py holds against the MIP restatement and an analytic sphere.  Since esl on and esl off are both held against
 the same frame, they equal each other."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import MAPPINGS, depth_diff, diff, expected_bands, load, reset_context, run_driver
 from iso_helpers import NO_SURFACE, PAIRS, IsoRef, all_volumes, depth_bits, frame_params, views_for
 from mip_helpers import MipRef, ramp_tf
 
@@ -29,22 +27,16 @@ def tf():
     return ramp_tf()
 
 
+@pytest.fixture(autouse=True)
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
+    yield
+    reset_context(vr, gpu)
+
+
 def expected(vr, oracle, vox, view, sampling, tf, level, light_kd=0.7, refine=REFINE):
     return IsoRef.instance().render(frame_params(vr, oracle, vox, view, sampling, 0, light_kd), vox, tf, level, refine)
-
-
-def load(gpu, vox, tf):
-    gpu.set_window_buffer(128, 128)
-    gpu.set_transfer_fn(tf, np.zeros(1024, np.uint32))          # (the ESL bits an isosurface frame is given are unused)
-    gpu.set_volume(vox)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def depth_diff(a, b):
-    return int((depth_bits(a) != depth_bits(b)).sum())
 
 
 def check(gpu, p, level, ref, what, refine=REFINE):
@@ -116,12 +108,10 @@ def test_tile_mappings_agree(vr, gpu, golden, oracle, volumes, tf):
     try:
         ref = expected(vr, oracle, vox, view, 1, tf, 24.5)
         assert ref[2]["hits"] > 1000
-        for order in range(3):
-            for shape in range(3):
-                for phase in ((0, 0), (3, 5)):
-                    gpu.set_tile_mapping(order + 4 * shape, *phase)
-                    check(gpu, frame_params(vr, oracle, vox, view, 1, 1), 24.5, ref, (order, shape, phase))
-                    assert gpu.last_launch()["lane_map"] == order + 4 * shape
+        for lane_map, phase in MAPPINGS:
+            gpu.set_tile_mapping(lane_map, *phase)
+            check(gpu, frame_params(vr, oracle, vox, view, 1, 1), 24.5, ref, (lane_map % 4, lane_map // 4, phase))      # (lane order, wave shape)
+            assert gpu.last_launch()["lane_map"] == lane_map
     finally:
         gpu.set_tile_mapping(-1)
 
@@ -139,15 +129,10 @@ def test_screen_partition(vr, gpu, golden, oracle, volumes, tf):
         assert (p.band_rows, p.band_stride, p.band_first) == (16, 3, 1)
         out, depth = gpu.render_iso(p, 100.0, REFINE, depth=True)
         assert out.shape[0] == per_rank * 16 and depth.shape == out.shape[:2]
-        beyond = 0
-        for ly in range(out.shape[0]):
-            gy = ((ly // 16) * 3 + 1) * 16 + ly % 16
-            want = ref[gy] if gy < 72 else np.zeros_like(ref[0])
-            want_depth = ref_depth[gy] if gy < 72 else np.full(120, -1, np.float32)
-            beyond += gy >= 72
-            assert np.array_equal(out[ly], want), (sampling, ly, gy)
-            assert np.array_equal(depth_bits(depth[ly]), depth_bits(want_depth)), (sampling, ly, gy)
-        assert beyond == 8
+        want = expected_bands(ref, 1, 3, 16, per_rank * 16)
+        assert np.array_equal(out, want), (sampling, np.flatnonzero((out != want).any(axis=(1, 2))))      # (the local rows that differ)
+        assert depth_diff(depth, expected_bands(ref_depth, 1, 3, 16, per_rank * 16, beyond=-1)) == 0, sampling
+        assert (~expected_bands(np.ones(72, bool), 1, 3, 16, per_rank * 16)).sum() == 8                     # rows beyond the view
         p = frame_params(vr, oracle, vox, view, sampling, 1)
         p.x0, p.out_width = 24, 40
         out, depth = gpu.render_iso(p, 100.0, REFINE, depth=True)
@@ -268,20 +253,12 @@ def test_release_linear_copy_keeps_skipping_frames_possible(vr, golden, oracle, 
 
 def test_driver_iso_flag(golden, tmp_path):
     """volr_bench -iso (HipRenderer::set_iso through the host mirror): Bucky.pvm, TRILINEAR, pose (-45,-45,0) at distance 2"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
-    ppm = tmp_path / "iso.ppm"
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", "-iso", "100", "-refine", "4",
-                          "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+    out, rgb = run_driver(tmp_path, "-iso", "100", "-refine", "4")
     assert out.returncode == 0, out.stdout + out.stderr
     assert "Isosurface" in out.stdout
-    header = b"P6\n256 256\n255\n"
-    data = ppm.read_bytes()
-    assert data.startswith(header)
-    rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     ref = IsoRef.instance().render(golden.params(case, 1), np.ascontiguousarray(golden.voxels("bucky")), golden.volume_state("bucky")["tf"], 100.0, 4)
     assert ref[2]["hits"] > 5000
     assert np.array_equal(rgb, ref[0][..., :3])
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-s", "128", "128", "-iso", "100", "-devices", "0,0"],
-                         capture_output=True, text=True, timeout=300)
+    out, _ = run_driver(tmp_path, "-iso", "100", "-devices", "0,0", size=(128, 128), pose=None, renderer=None, output=None)
     assert out.returncode != 0 and "single device" in out.stdout

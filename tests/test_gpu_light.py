@@ -3,15 +3,13 @@ render is held byte for byte against light_render of tests/feature_ref.c, the co
 tests/test_light_model.py ties that restatement to the pinned clipped composite and shows that the frames compared here are neither
 trivial nor the cue-lit ones, and that the plateau volume takes the zero-gradient branch."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from clip_helpers import CLIPS, ClipRef, IDENTITY, composite_params, set_clip
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import (PATH_VOLUMES, assert_order_repeats, diff, expected_bands, load, multi_pair, needs_bounds_lib, reset_context, run_driver,
+                         run_under_bounds_build, sweep_paths)
 from iso_helpers import frame_params
 from light_helpers import IDENTITY_LIGHTING, LIGHTINGS, LIT_VOLUMES, PHONG, LightRef, cue, lit_views, lit_volumes
 from shadow_helpers import FRAME_SCENES, LIGHTS, ShadowRef
@@ -25,26 +23,11 @@ def volumes(golden):
 
 
 @pytest.fixture(autouse=True)
-def state_off_afterwards(gpu):
-    """the context is shared by the whole session: no test leaves a lighting, a shadow, a clip or a forced path behind"""
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
     yield
-    gpu.clear_lighting()
-    gpu.clear_shadow()
-    gpu.clear_clip()
-    gpu.set_tile_mapping(-1)
-    gpu.set_tile_scheduling(1)
-    gpu.set_wide_addressing(0)
-    gpu.set_brick_plane(-1)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def load(gpu, vox, tf, esl, window=(128, 128)):
-    gpu.set_window_buffer(*window)
-    gpu.set_transfer_fn(tf, esl)
-    gpu.set_volume(vox)
+    reset_context(vr, gpu)
 
 
 def scene(vr, golden, oracle, volumes, name, view=None, sampling=1, full_march=False):
@@ -89,7 +72,7 @@ def test_every_path_agrees_under_a_lighting(vr, gpu, golden, oracle, volumes):
     every lane order x wave shape x two phases, tile scheduling 0 / 1 / 2 — the restatement's bytes, and never a run copy or a column
     window; u8 and u16 (oct bricks)"""
     ref = LightRef.instance()
-    for name, expect in (("blob_40x24x56", {0, 1}), ("random_u16", {0, 1, 5})):
+    for name, expect in PATH_VOLUMES:
         views = [v for v in lit_views(vr, golden, name) if v[0] in ("view0", "view1", "view6")]
         cases = []
         for label, view in views:
@@ -107,37 +90,7 @@ def test_every_path_agrees_under_a_lighting(vr, gpu, golden, oracle, volumes):
                 assert diff(out, want) == 0, (name, what, label, sampling, diff(out, want), info)
                 assert info["layout"] in (0, 1, 5), (name, what, label, sampling, info)
                 seen.add(info["layout"])
-        try:
-            for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
-                gpu.set_layout(layout)
-                check(("layout", layout))
-                if layout == vr.LAYOUT_LINEAR:
-                    gpu.set_wide_addressing(1)
-                    check(("layout", layout, "wide"))
-                    gpu.set_wide_addressing(0)
-            for plane in (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-                gpu.set_brick_plane(plane)
-                check(("plane", plane))
-            gpu.set_brick_plane(-1)
-            for wide in (0, 1, 2, 4):
-                gpu.set_wide_addressing(wide)
-                check(("wide", wide))
-            gpu.set_wide_addressing(0)
-            for order in range(3):
-                for shape in range(3):
-                    for phase in ((0, 0), (3, 5)):
-                        gpu.set_tile_mapping(order + 4 * shape, *phase)
-                        check(("mapping", order, shape, phase))
-            gpu.set_tile_mapping(-1)
-            for mode in (0, 1, 2):
-                gpu.set_tile_scheduling(mode)
-                check(("scheduling", mode))
-        finally:
-            gpu.set_tile_scheduling(1)
-            gpu.set_tile_mapping(-1)
-            gpu.set_wide_addressing(0)
-            gpu.set_brick_plane(-1)
-            gpu.set_layout(vr.LAYOUT_BRICKED)
+        sweep_paths(vr, gpu, check)
         assert seen == expect, (name, seen)
 
 
@@ -148,11 +101,7 @@ def test_tile_order_repeats(vr, gpu, golden, oracle, volumes):
     load(gpu, vox, tf, esl, (256, 256))
     gpu.set_lighting(*PHONG)
     want = ref.render(p, vox, tf, esl, PHONG)
-    ordered = 0
-    for k in range(4):
-        assert diff(gpu.render_volume(p), want) == 0, k
-        ordered += gpu.last_launch()["ordered"]
-    assert ordered >= 3, ordered
+    assert_order_repeats(gpu, lambda: gpu.render_volume(p), want)
 
 
 def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
@@ -169,9 +118,8 @@ def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
     p, per_rank = vr.band_partition(whole.copy(), 1, 3, 16)
     out = gpu.render_volume(p)
     assert out.shape[0] == per_rank * 16
-    for ly in range(out.shape[0]):
-        gy = ((ly // 16) * 3 + 1) * 16 + ly % 16
-        assert np.array_equal(out[ly], want[gy] if gy < 72 else np.zeros_like(want[0])), (ly, gy)
+    expected = expected_bands(want, 1, 3, 16, per_rank * 16)
+    assert np.array_equal(out, expected), np.flatnonzero((out != expected).any(axis=(1, 2)))      # (the local rows that differ)
     crop = whole.copy()
     crop.x0, crop.out_width = 24, 40
     assert np.array_equal(gpu.render_volume(crop), want[:, 24:64])
@@ -297,19 +245,12 @@ def test_errors_and_what_ignores_the_lighting(vr, gpu, golden, oracle, volumes):
         assert L.vr_hip_set_lighting(gpu._ctx, C.byref(good)) == 0
 
 
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
-
-
-@pytest.mark.skipif(not os.path.exists(BOUNDS_LIB), reason="build_variants/libvr_hip_bounds.so not built (scripts/build_variant.sh bounds -DVR_BOUNDS_CHECK)")
+@needs_bounds_lib
 def test_lit_frames_under_the_bounds_checked_build():
     """The frames, paths, clip and shadow tests of this file once in a child process with the -DVR_BOUNDS_CHECK library (tests/test_gpu_bounds.py):
     every gather address of the six gradient fetches is held against its array — a violation fails the frame (VrError) — and the bytes
     still equal the restatement"""
-    env = dict(os.environ, VR_HIP_LIB=BOUNDS_LIB)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q",
-                        "-k", "frames_equal_the_restatement or every_path or with_clip or with_shadow"],
-                       capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
-    assert r.returncode == 0 and "15 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    run_under_bounds_build(__file__, "frames_equal_the_restatement or every_path or with_clip or with_shadow", 15, timeout=600)
 
 
 @pytest.mark.parametrize("transport", ("peer", "rccl-self"))
@@ -318,12 +259,7 @@ def test_multi_device_frames_are_lit(vr, gpu, golden, oracle, volumes, monkeypat
     with one communicator"""
     name = "bucky"
     ref = LightRef.instance()
-    monkeypatch.setenv("VR_MULTI_TRANSPORT", transport)
-    monkeypatch.setenv("VR_MULTI_SELFCHECK", "1")
-    m = vr.MultiRenderer([0, 0])
-    try:
-        assert m.transport == ("peer-copy" if transport == "peer" else "rccl-self")
-        m.set_window_buffer(120, 72)
+    with multi_pair(vr, monkeypatch, transport) as m:
         for sampling in (1, 2):
             vox, p, tf, esl = scene(vr, golden, oracle, volumes, name, vr.benchmark_view(120, 72, 5), sampling, False)
             if sampling == 1:
@@ -342,33 +278,23 @@ def test_multi_device_frames_are_lit(vr, gpu, golden, oracle, volumes, monkeypat
         with pytest.raises(vr.VrError) as e:
             m.set_lighting(0.5, 1.5, 0.0, 0)
         assert e.value.code == 1
-    finally:
-        m.close()
 
 
 def test_driver_phong_flag(golden, tmp_path):
     """volr_bench -phong ka kd ks n (HipRenderer::set_lighting through the host mirror): Bucky.pvm, TRILINEAR, pose (-45,-45,0) at distance
     2, 256 x 256 — the frame the library call gives; with -shadow 17 the two compose; a refused lighting ends the driver"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
     vox = np.ascontiguousarray(golden.voxels("bucky"))
     st = golden.volume_state("bucky")
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     p = golden.params(case, 1)
     ref = LightRef.instance()
     q = ShadowRef.instance().build(tuple(p.view.light_pos), 17, p.ray_step, vox, st["tf"])
-    header = b"P6\n256 256\n255\n"
     for extra, grid in (([], None), (["-shadow", "17"], q)):
-        ppm = tmp_path / "phong.ppm"
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", "-phong", "0.25", "0.65", "0.4", "4", *extra,
-                              "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+        out, rgb = run_driver(tmp_path, "-phong", "0.25", "0.65", "0.4", "4", *extra)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "Lighting: ambient 0.25, diffuse 0.65, specular 0.4, shininess 2^4" in out.stdout
-        data = ppm.read_bytes()
-        assert data.startswith(header)
-        rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
         want = ref.render(p, vox, st["tf"], st["esl"], PHONG, grid, 1.0)
         assert np.array_equal(rgb, want[..., :3]), (extra, int((rgb != want[..., :3]).any(axis=-1).sum()))
         assert diff(want, ClipRef.instance().composite(p, vox, st["tf"], st["esl"], IDENTITY)) > 1000
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "128", "128", "-phong", "0.25", "0.65", "0.4", "11", "-o", str(tmp_path / "x.ppm")],
-                         capture_output=True, text=True, timeout=300)
+    out, _ = run_driver(tmp_path, "-phong", "0.25", "0.65", "0.4", "11", size=(128, 128), pose=None)
     assert out.returncode != 0 and "shininess_log2" in out.stdout

@@ -2,13 +2,11 @@
 held byte for byte against mip_render of tests/feature_ref.c — the MIP loop restated with the CPU oracle's statics, which tests/test_mip_model.py
 pins against the unmodified oracle.  Since esl on and esl off are both held against the same frame, they equal each other."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import MAPPINGS, diff, expected_bands, load, reset_context, run_driver
 from mip_helpers import MipRef, ramp_tf, synthetic_volumes
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +27,14 @@ def volumes(golden):
 @pytest.fixture(scope="module")
 def tf():
     return ramp_tf()
+
+
+@pytest.fixture(autouse=True)
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
+    yield
+    reset_context(vr, gpu)
 
 
 def frame_params(vr, oracle, vox, view, sampling, esl):
@@ -56,16 +62,6 @@ def views_of(vr, golden, index):
 
 def expected(vr, oracle, vox, view, sampling, tf):
     return MipRef.instance().render(frame_params(vr, oracle, vox, view, sampling, 0), vox, tf)[0]
-
-
-def load(gpu, vox, tf):
-    gpu.set_window_buffer(128, 128)
-    gpu.set_transfer_fn(tf, np.zeros(1024, np.uint32))          # (the ESL bits a MIP frame is given are unused)
-    gpu.set_volume(vox)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
 
 
 @pytest.mark.parametrize("name", VOLUMES)
@@ -120,13 +116,11 @@ def test_tile_mappings_agree(vr, gpu, golden, oracle, volumes, tf):
     try:
         for sampling in (0, 1):
             ref = expected(vr, oracle, vox, view, sampling, tf)
-            for order in range(3):
-                for shape in range(3):
-                    for phase in ((0, 0), (3, 5)):
-                        gpu.set_tile_mapping(order + 4 * shape, *phase)
-                        out = gpu.render_mip(frame_params(vr, oracle, vox, view, sampling, 1))
-                        assert diff(out, ref) == 0, (sampling, order, shape, phase)
-                        assert gpu.last_launch()["lane_map"] == order + 4 * shape
+            for lane_map, phase in MAPPINGS:
+                gpu.set_tile_mapping(lane_map, *phase)
+                out = gpu.render_mip(frame_params(vr, oracle, vox, view, sampling, 1))
+                assert diff(out, ref) == 0, (sampling, lane_map % 4, lane_map // 4, phase)      # (lane order, wave shape)
+                assert gpu.last_launch()["lane_map"] == lane_map
     finally:
         gpu.set_tile_mapping(-1)
 
@@ -142,10 +136,8 @@ def test_screen_partition(vr, gpu, golden, oracle, volumes, tf):
         assert (p.band_rows, p.band_stride, p.band_first) == (16, 3, 1)
         out = gpu.render_mip(p)
         assert out.shape[0] == per_rank * 16
-        for ly in range(out.shape[0]):
-            gy = ((ly // 16) * 3 + 1) * 16 + ly % 16
-            want = ref[gy] if gy < 80 else np.zeros_like(ref[0])
-            assert np.array_equal(out[ly], want), (sampling, ly, gy)
+        want = expected_bands(ref, 1, 3, 16, per_rank * 16)
+        assert np.array_equal(out, want), (sampling, np.flatnonzero((out != want).any(axis=(1, 2))))      # (the local rows that differ)
         p = frame_params(vr, oracle, vox, view, sampling, 1)
         p.x0, p.out_width = 24, 40
         assert np.array_equal(gpu.render_mip(p), ref[:, 24:64]), sampling
@@ -251,20 +243,12 @@ def test_release_linear_copy_keeps_skipping_frames_possible(vr, golden, oracle, 
 
 def test_driver_mip_flag(golden, tmp_path):
     """volr_bench -mip (HipRenderer::set_mip through the host mirror): Bucky.pvm, NEAREST, pose (-45,-45,0) at distance 2"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
-    ppm = tmp_path / "mip.ppm"
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "0", "-s", "256", "256", "-mip",
-                          "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+    out, rgb = run_driver(tmp_path, "-mip", renderer="0")
     assert out.returncode == 0, out.stdout + out.stderr
     assert "Maximum-intensity projection" in out.stdout
-    header = b"P6\n256 256\n255\n"
-    data = ppm.read_bytes()
-    assert data.startswith(header)
-    rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     ref = MipRef.instance().render(golden.params(case, 0), golden.voxels("bucky"), golden.volume_state("bucky")["tf"])[0]
     assert np.array_equal(rgb, ref[..., :3])
     assert not np.array_equal(ref, golden.frame(case))     # ... and it is not the composite
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-s", "128", "128", "-mip", "-devices", "0,0"],
-                         capture_output=True, text=True, timeout=300)
+    out, _ = run_driver(tmp_path, "-mip", "-devices", "0,0", size=(128, 128), pose=None, renderer=None, output=None)
     assert out.returncode != 0 and "single device" in out.stdout

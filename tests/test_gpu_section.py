@@ -3,9 +3,6 @@ is held byte for byte — RGBA and depth bits, no tolerance anywhere — against
 tests/section_ref.c, the contract of include/vr_hip.h restated with the CPU oracle's statics.  tests/test_section_model.py ties that
 restatement to the clipped MIP and shows that the frames compared here carry sections and tell four wrong readings of the contract apart."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,8 +10,9 @@ import pytest
 import feature_random as fr
 from backdrop_helpers import BackdropRef
 from clip_helpers import CLIPS, IDENTITY, set_clip
-from helpers import GOLDEN_DIR, ROOT
-from iso_helpers import IsoRef, depth_bits, frame_params
+from gpu_feature import (PATH_VOLUMES, depth_diff, diff, expected_bands, load, needs_bounds_lib, reset_context, run_driver, run_under_bounds_build,
+                         sweep_paths)
+from iso_helpers import IsoRef, frame_params
 from light_helpers import PHONG, lit_views, lit_volumes
 from mip_helpers import MipRef
 from section_helpers import MODES, SECTION_VOLUMES, WINDOWS, SectionRef, half_width_of, planes_of, tier_frames, unit
@@ -31,31 +29,9 @@ def volumes(golden):
 
 @pytest.fixture(autouse=True)
 def state_off_afterwards(vr, gpu):
-    """the context is shared by the whole session: no test leaves the pre-integration, a lighting, a shadow, a clip, a layout or a forced path behind"""
+    """the context is shared by the whole session: no test leaves a state, a layout or a forced path behind"""
     yield
-    gpu.clear_preintegration()
-    gpu.clear_lighting()
-    gpu.clear_shadow()
-    gpu.clear_clip()
-    gpu.set_layout(vr.LAYOUT_BRICKED)
-    gpu.set_tile_mapping(-1)
-    gpu.set_tile_scheduling(1)
-    gpu.set_wide_addressing(0)
-    gpu.set_brick_plane(-1)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def depth_diff(a, b):
-    return int((depth_bits(a) != depth_bits(b)).sum())
-
-
-def load(gpu, vox, tf, esl, window=(128, 128)):
-    gpu.set_window_buffer(*window)
-    gpu.set_transfer_fn(tf, esl)
-    gpu.set_volume(vox)
+    reset_context(vr, gpu)
 
 
 def section_launch(info):
@@ -87,7 +63,7 @@ def test_frames_equal_the_restatement(vr, gpu, golden, oracle, volumes, name, sa
     start = gpu.section_frames()
     for what, vox, p, tf, plane, h, mode, window, clip in tier_frames(vr, golden, oracle, volumes, name, sampling):
         if loaded is None:
-            load(gpu, vox, tf, np.zeros(1024, np.uint32))
+            load(gpu, vox, tf)
         if clip != loaded:
             set_clip(gpu, clip)
             loaded = clip
@@ -150,7 +126,7 @@ def test_every_path_agrees(vr, gpu, golden, oracle, volumes):
     shape x two phases, tile scheduling 0 / 1 / 2 — the restatement's bytes and depth bits, never a run copy or a column window, never a
     measured order; u8 and u16 (oct bricks); a POINT frame coloured by the transfer function and a MEAN frame under the window"""
     ref = SectionRef.instance()
-    for name, expect in (("blob_40x24x56", {0, 1}), ("random_u16", {0, 1, 5})):
+    for name, expect in PATH_VOLUMES:
         views = [v for v in lit_views(vr, golden, name) if v[0] in ("view0", "view1", "view6")]
         cases = []
         for k, (label, view) in enumerate(views):
@@ -165,31 +141,7 @@ def test_every_path_agrees(vr, gpu, golden, oracle, volumes):
             for label, p, plane, h, mode, window in cases:
                 check(gpu, ref, (name, what, label, mode), vox, p, tf, plane, h, mode, window)
                 seen.add(gpu.last_launch()["layout"])
-        for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
-            gpu.set_layout(layout)
-            check_all(("layout", layout))
-            if layout == vr.LAYOUT_LINEAR:
-                gpu.set_wide_addressing(1)
-                check_all(("layout", layout, "wide"))
-                gpu.set_wide_addressing(0)
-        for plane_forced in (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-            gpu.set_brick_plane(plane_forced)
-            check_all(("plane", plane_forced))
-        gpu.set_brick_plane(-1)
-        for wide in fr.WIDE:
-            gpu.set_wide_addressing(wide)
-            check_all(("wide", wide))
-        gpu.set_wide_addressing(0)
-        for order in range(3):
-            for shape in range(3):
-                for phase in ((0, 0), (3, 5)):
-                    gpu.set_tile_mapping(order + 4 * shape, *phase)
-                    check_all(("mapping", order, shape, phase))
-        gpu.set_tile_mapping(-1)
-        for scheduling in (0, 1, 2):
-            gpu.set_tile_scheduling(scheduling)
-            check_all(("scheduling", scheduling))
-        gpu.set_tile_scheduling(1)
+        sweep_paths(vr, gpu, check_all)
         assert seen == expect, (name, seen)
 
 
@@ -211,11 +163,8 @@ def test_bands_crop_and_device_entry_point(vr, gpu, golden, oracle, volumes):
             p, per_rank = vr.band_partition(whole.copy(), first, 2, 3)
             rows = per_rank * 3
             assert p.out_rows == rows == 36
-            gy = np.array([((ly // 3) * 2 + first) * 3 + ly % 3 for ly in range(rows)])
-            inside = gy < 70
-            assert inside.all() == (first == 0)
-            expected, expected_depth = np.zeros((rows, 120, 4), np.uint8), np.full((rows, 120), -1.0, np.float32)
-            expected[inside], expected_depth[inside] = want[gy[inside]], want_depth[gy[inside]]
+            expected, expected_depth = expected_bands(want, first, 2, 3, rows), expected_bands(want_depth, first, 2, 3, rows, beyond=-1)
+            assert expected_bands(np.ones(70, bool), first, 2, 3, rows).all() == (first == 0)      # (rank 1 holds rows beyond the view)
             out, depth = gpu.render_section(p, plane, hw, mode, window, depth=True)
             assert np.array_equal(out, expected) and depth_diff(depth, expected_depth) == 0, (mode, first, diff(out, expected))
         crop = whole.copy()
@@ -412,45 +361,31 @@ def test_errors(vr, gpu, golden, oracle, volumes):
     assert diff(buf.cpu().numpy(), SectionRef.instance().render(p, vox, tf, (0.0, 0.0, 1.0, 0.1), 0.0, "point", (0.0, 255.0))[0]) == 0
 
 
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
-
-
-@pytest.mark.skipif(not os.path.exists(BOUNDS_LIB), reason="build_variants/libvr_hip_bounds.so not built (scripts/build_variant.sh bounds -DVR_BOUNDS_CHECK)")
+@needs_bounds_lib
 def test_section_frames_under_the_bounds_checked_build():
     """A subset of this file once in a child process with the -DVR_BOUNDS_CHECK library (tests/test_gpu_bounds.py): every gather address is
     held against its array — a violation fails the frame (VrError) — and the bytes still equal the restatement"""
-    env = dict(os.environ, VR_HIP_LIB=BOUNDS_LIB)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q",
-                        "-k", "edge_shapes or every_path or random_scenes or in_volume_with_every_state or (frames_equal and random_u16)"],
-                       capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
-    assert r.returncode == 0 and "7 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    run_under_bounds_build(__file__, "edge_shapes or every_path or random_scenes or in_volume_with_every_state or (frames_equal and random_u16)", 7, timeout=900)
 
 
 def test_driver_section_flags(golden, tmp_path):
     """volr_bench -section (HipRenderer::set_section through the host mirror): Bucky.pvm, TRILINEAR, pose (-45,-45,0) at distance 2,
     256 x 256 — the restatement's frame for a POINT section under a window, and for the slab mean inside the volume with -shadow 17
     -preint, which the composite pass sees; what -section excludes is refused, and so are its options without it"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
     vox = np.ascontiguousarray(golden.voxels("bucky"))
     st = golden.volume_state("bucky")
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     p = golden.params(case, 1)
     ref = SectionRef.instance()
     q = ShadowRef.instance().build(tuple(p.view.light_pos), 17, p.ray_step, vox, st["tf"])
-    header = b"P6\n256 256\n255\n"
     plane = (0.5, 0.5, 0.70703125, 0.125)              # (exact in fp32 and in the driver's decimal arguments)
     args = ["-section"] + [repr(c) for c in plane]
     alone = args + ["-section-window", "10", "250"]
     inside = args + ["-section-half", "0.125", "-section-mode", "mean", "-section-in-volume", "-shadow", "17", "-preint"]
     for extra in (alone, inside):
-        ppm = tmp_path / "section.ppm"
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", *extra,
-                              "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+        out, rgb = run_driver(tmp_path, *extra)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "Section: plane" in out.stdout
-        data = ppm.read_bytes()
-        assert data.startswith(header)
-        rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
         if extra is alone:
             want = ref.render(p, vox, st["tf"], plane, 0.0, "point", (10.0, 250.0))[0]
             assert (want[..., 3] == 255).sum() > 5000
@@ -459,9 +394,8 @@ def test_driver_section_flags(golden, tmp_path):
             assert diff(want, section) > 1000
         assert np.array_equal(rgb, want[..., :3]), (extra, int((rgb != want[..., :3]).any(axis=-1).sum()))
     for bad in (["-mip"], ["-iso", "100"], ["-hybrid", "100"], ["-devices", "0,0"], ["-r", "0"]):
-        flags = [a for a in ["-r", "1"] if "-r" not in bad] + bad
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), *flags, "-s", "128", "128", *args], capture_output=True, text=True, timeout=300)
+        out, _ = run_driver(tmp_path, *bad, *args, size=(128, 128), pose=None, renderer=None if "-r" in bad else "1", output=None)
         assert out.returncode != 0 and "Error: -section" in out.stdout, (bad, out.stdout)
     for orphan in (["-section-window", "10", "250"], ["-section-half", "0.1"], ["-section-mode", "min"], ["-section-in-volume"]):
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "128", "128", *orphan], capture_output=True, text=True, timeout=300)
+        out, _ = run_driver(tmp_path, *orphan, size=(128, 128), pose=None, output=None)
         assert out.returncode != 0 and "need -section" in out.stdout, (orphan, out.stdout)

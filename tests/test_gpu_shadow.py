@@ -3,14 +3,12 @@ shadowed composite frame is held byte for byte against shadow_build / shadow_ren
 include/vr_hip.h restated with the CPU oracle's statics.  tests/test_shadow_model.py ties that restatement to the pinned clipped composite and shows that the grids and frames compared
 here are neither trivial nor unshadowed."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from clip_helpers import BOTH, CLIPS, ClipRef, IDENTITY, composite_params, set_clip
-from helpers import GOLDEN_DIR, ROOT
+from gpu_feature import PATH_VOLUMES, assert_order_repeats, diff, expected_bands, load, multi_pair, reset_context, run_driver, sweep_paths
 from iso_helpers import all_volumes, frame_params, views_for
 from shadow_helpers import COMPOSITE_VOLUMES, CUTOFF, FRAME_SCENES, GRID_SCENES, LIGHTS, SMALLEST, ShadowRef, unlit
 
@@ -23,25 +21,11 @@ def volumes(golden):
 
 
 @pytest.fixture(autouse=True)
-def state_off_afterwards(gpu):
-    """the context is shared by the whole session: no test leaves a shadow, a clip or a forced path behind"""
+def state_off_afterwards(vr, gpu):
+    """the context is shared by the whole session: no test leaves a state or a forced path behind.  (Setting the layout drops the brick
+    copies; every test that renders through the shared context begins with load or set_volume, which drops them anyway.)"""
     yield
-    gpu.clear_shadow()
-    gpu.clear_clip()
-    gpu.set_tile_mapping(-1)
-    gpu.set_tile_scheduling(1)
-    gpu.set_wide_addressing(0)
-    gpu.set_brick_plane(-1)
-
-
-def diff(a, b):
-    return int((a != b).any(axis=-1).sum())
-
-
-def load(gpu, vox, tf, esl, window=(128, 128)):
-    gpu.set_window_buffer(*window)
-    gpu.set_transfer_fn(tf, esl)
-    gpu.set_volume(vox)
+    reset_context(vr, gpu)
 
 
 def scene(vr, golden, oracle, volumes, name, view=None, sampling=1, full_march=False):
@@ -136,7 +120,7 @@ def test_every_path_agrees_under_a_shadow(vr, gpu, golden, oracle, volumes):
     """Placement and addressing only: linear / bricked, forced planes -1 and 0-9, wide addressing 0 / 1 / 2 / +4, every lane order x wave
     shape x two phases, tile scheduling 0 / 1 / 2 — the restatement's bytes, and never a run copy or a column window; u8 and u16 (oct bricks)"""
     ref = ShadowRef.instance()
-    for name, expect in (("blob_40x24x56", {0, 1}), ("random_u16", {0, 1, 5})):
+    for name, expect in PATH_VOLUMES:
         light, S = FRAME_SCENES[name]
         views = [v for v in views_for(vr, golden, name) if v[0] in ("view0", "view1", "view6")]
         cases = []
@@ -156,33 +140,7 @@ def test_every_path_agrees_under_a_shadow(vr, gpu, golden, oracle, volumes):
                 assert diff(out, want) == 0, (name, what, label, sampling, diff(out, want), info)
                 assert info["layout"] in (0, 1, 5) and info["shadowed"] == 1, (name, what, label, sampling, info)
                 seen.add(info["layout"])
-        try:
-            for layout in (vr.LAYOUT_LINEAR, vr.LAYOUT_BRICKED):
-                gpu.set_layout(layout)
-                check(("layout", layout))
-            for plane in (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-                gpu.set_brick_plane(plane)
-                check(("plane", plane))
-            gpu.set_brick_plane(-1)
-            for wide in (0, 1, 2, 4):
-                gpu.set_wide_addressing(wide)
-                check(("wide", wide))
-            gpu.set_wide_addressing(0)
-            for order in range(3):
-                for shape in range(3):
-                    for phase in ((0, 0), (3, 5)):
-                        gpu.set_tile_mapping(order + 4 * shape, *phase)
-                        check(("mapping", order, shape, phase))
-            gpu.set_tile_mapping(-1)
-            for mode in (0, 1, 2):
-                gpu.set_tile_scheduling(mode)
-                check(("scheduling", mode))
-        finally:
-            gpu.set_tile_scheduling(1)
-            gpu.set_tile_mapping(-1)
-            gpu.set_wide_addressing(0)
-            gpu.set_brick_plane(-1)
-            gpu.set_layout(vr.LAYOUT_BRICKED)
+        sweep_paths(vr, gpu, check)
         assert seen == expect, (name, seen)
 
 
@@ -195,11 +153,7 @@ def test_tile_order_repeats(vr, gpu, golden, oracle, volumes):
     load(gpu, vox, tf, esl, (256, 256))
     gpu.set_shadow(LIGHTS[light], S, p.ray_step)
     want = ref.render(p, vox, tf, esl, ref.build(LIGHTS[light], S, p.ray_step, vox, tf), 1.0)
-    ordered = 0
-    for k in range(4):
-        assert diff(gpu.render_volume(p), want) == 0, k
-        ordered += gpu.last_launch()["ordered"]
-    assert ordered >= 3, ordered
+    assert_order_repeats(gpu, lambda: gpu.render_volume(p), want)
 
 
 def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
@@ -219,9 +173,8 @@ def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
     p, per_rank = vr.band_partition(whole.copy(), 1, 3, 16)
     out = gpu.render_volume(p)
     assert out.shape[0] == per_rank * 16
-    for ly in range(out.shape[0]):
-        gy = ((ly // 16) * 3 + 1) * 16 + ly % 16
-        assert np.array_equal(out[ly], want[gy] if gy < 72 else np.zeros_like(want[0])), (ly, gy)
+    expected = expected_bands(want, 1, 3, 16, per_rank * 16)
+    assert np.array_equal(out, expected), np.flatnonzero((out != expected).any(axis=(1, 2)))      # (the local rows that differ)
     crop = whole.copy()
     crop.x0, crop.out_width = 24, 40
     assert np.array_equal(gpu.render_volume(crop), want[:, 24:64])
@@ -397,12 +350,7 @@ def test_multi_device_frames_are_shadowed(vr, gpu, golden, oracle, volumes, monk
     name = "bucky"
     light, S = FRAME_SCENES[name]
     ref = ShadowRef.instance()
-    monkeypatch.setenv("VR_MULTI_TRANSPORT", transport)
-    monkeypatch.setenv("VR_MULTI_SELFCHECK", "1")
-    m = vr.MultiRenderer([0, 0])
-    try:
-        assert m.transport == ("peer-copy" if transport == "peer" else "rccl-self")
-        m.set_window_buffer(120, 72)
+    with multi_pair(vr, monkeypatch, transport) as m:
         for sampling in (1, 2):
             vox, p, tf, esl = scene(vr, golden, oracle, volumes, name, vr.benchmark_view(120, 72, 5), sampling, False)
             if sampling == 1:
@@ -421,33 +369,23 @@ def test_multi_device_frames_are_shadowed(vr, gpu, golden, oracle, volumes, monk
         with pytest.raises(vr.VrError) as e:
             m.set_shadow(LIGHTS[light], 1)
         assert e.value.code == 1
-    finally:
-        m.close()
 
 
 def test_driver_shadow_flag(golden, tmp_path):
     """volr_bench -shadow 17 (HipRenderer::set_shadow through the host mirror, the light taken from the view): Bucky.pvm, TRILINEAR, pose
     (-45,-45,0) at distance 2, 256 x 256 — the frame the library call gives; and -shadow-strength"""
-    exe = os.path.join(ROOT, "volume-rendering_amd", "volr_bench")
     vox = np.ascontiguousarray(golden.voxels("bucky"))
     st = golden.volume_state("bucky")
     case = next(c for c in golden.cases(True) if c["label"] == "bench256_view1_default")
     p = golden.params(case, 1)
     ref = ShadowRef.instance()
     q = ref.build(tuple(p.view.light_pos), 17, p.ray_step, vox, st["tf"])
-    header = b"P6\n256 256\n255\n"
     for extra, strength in (([], 1.0), (["-shadow-strength", "0.5"], 0.5)):
-        ppm = tmp_path / "shadow.ppm"
-        out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "256", "256", "-shadow", "17", *extra,
-                              "-pose", "-45", "-45", "0", "2", "-o", str(ppm)], capture_output=True, text=True, timeout=300)
+        out, rgb = run_driver(tmp_path, "-shadow", "17", *extra)
         assert out.returncode == 0, out.stdout + out.stderr
         assert "Shadow: 17^3 nodes" in out.stdout
-        data = ppm.read_bytes()
-        assert data.startswith(header)
-        rgb = np.frombuffer(data[len(header):], np.uint8).reshape(256, 256, 3)[::-1]
         want = ref.render(p, vox, st["tf"], st["esl"], q, strength)
         assert np.array_equal(rgb, want[..., :3]), (extra, int((rgb != want[..., :3]).any(axis=-1).sum()))
         assert diff(want, ref.render(p, vox, st["tf"], st["esl"])) > 1000
-    out = subprocess.run([exe, "-f", os.path.join(GOLDEN_DIR, "Bucky.pvm"), "-r", "1", "-s", "128", "128", "-shadow", "1", "-o", str(tmp_path / "x.ppm")],
-                         capture_output=True, text=True, timeout=300)
+    out, _ = run_driver(tmp_path, "-shadow", "1", size=(128, 128), pose=None)
     assert out.returncode != 0 and "dims" in out.stdout

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import test_column_edges as edges
+from gpu_feature import BOUNDS_LIB
 from helpers import ColumnScene, axis_view, column_params, voxel_windows_fit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,6 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from lane_march_waves import mixed_entry_waves, pixel_segments  # noqa: E402
 
 gpu_test = pytest.mark.gpu
-BOUNDS_LIB = os.path.join(ROOT, "build_variants", "libvr_hip_bounds.so")
 BUFFER = 128
 F = np.float32
 
