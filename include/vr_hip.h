@@ -539,6 +539,68 @@ int vr_hip_render_section_in_volume(vr_ctx *ctx, const vr_params *params, const 
 int vr_hip_render_section_in_volume_device(vr_ctx *ctx, const vr_params *params, const vr_section *section, void *dev_rgba, void *dev_depth /* may be NULL */, void *stream);
 int vr_hip_section_frames(vr_ctx *ctx, uint64_t *frames_out);          /* testing aid: section frames launched */
 
+/* ---- depth frames of the composite, and pixel picking.  No reference counterpart. ----
+ * A depth frame says where along its ray the thing a composite pixel shows lies: the depth k of the pixel's own ray, the interpolated raw
+ * value there and the pixel's final alpha, three float buffers laid out exactly like the isosurface's depth buffer (x0, out_width, out_rows,
+ * band_*; rows with gy >= height hold -1 / -1 / 0).  The composite's alpha depends only on the sampling mode, the clip, the leaping and the
+ * classification — the shadow's and the lighting's contracts both leave alpha untouched — so one alpha-only march mirrors every composite
+ * frame a context can launch.  The depth buffer is the third producer of the layer a backdrop frame takes.  vr_depth is a per-call argument,
+ * not context state: vr_params and every other struct keep their size and layout.
+ *  1. Ray.  get_ray + intersect, then steps 1-3 of the clip contract under the context's clip; with no clip set the identity clip, always
+ *     run, as for backdrop and section frames.  A miss gives depth -1, value -1, alpha 0.
+ *  2. Leaping.  The composite's leaping loop in front of the accumulation loop, under params.esl with the ESL bits of
+ *     vr_hip_set_transfer_fn.  If no sample is left (kx > ky) the pixel is a miss.
+ *  3. Accumulation.  For each sample of `while (kx <= ky)`, in this order: raw = the TRILINEAR (or _Q8) value at fma(kx, A, B); a = the .w of
+ *     the sample's classified colour — the filtered lookup, or under vr_hip_set_preintegration(1) the slab colour of that contract (narrow /
+ *     wide, tp of the previous sample of this loop, the first sample's tp = tb), the composite's arithmetic —; t = 1 - acc, g = a * t (a plain
+ *     product, rounded on its own), acc = fmaf(a, t, acc); the record of step 4; `if (acc > ray_threshold) break;` — the sample that
+ *     terminates the ray is recorded —; kx += ray_step.
+ *  4. Record.  FIRST: at the first sample whose acc >= opacity (ordered compare, acc after the update) depth = that kx, value = that raw.
+ *     PEAK: `if (g > best) { best = g; depth = kx; value = raw; }`, best starting at 0: the first of equal peaks wins, a sample with g = 0
+ *     never does.  MEAN: sg = sg + g; sk = fmaf(kx, g, sk); sv = fmaf(raw, g, sv), in sample order.
+ *  5. Result.  FIRST / PEAK: as recorded, else depth -1 and value -1.  MEAN: if sg > 0, depth = sk / sg and value = sv / sg (IEEE division),
+ *     else -1 / -1.  alpha = the final acc, in every mode.
+ *  6. Consequences.  map_float_int(alpha, 256) is the alpha byte of the composite frame of the same params under the same clip and
+ *     pre-integration state, whatever shadow and lighting are set.  Every surface has depth >= 0: the depth buffer is a valid backdrop layer.
+ *  7. What it ignores.  light_kd, light_pos, shadow and lighting.  The two guards on ray_step look at the unclipped segment.
+ *  8. Exact acceleration.  The kernel may take the composite's transparent-sample shortcuts (under pre-integration a sample whose tp is above
+ *     tf_zero_below is not transparent) and may stop a FIRST ray at its surface when no alpha buffer is asked for.  Results do not depend on
+ *     which buffers are asked for.
+ *  9. What it reads.  What a clipped MIP frame of that view and sampling reads — linear array, quad or oct bricks, never a run copy or a
+ *     column window: vr_launch_info::layout is 0, 1 or 5; vr_hip_set_layout and vr_hip_set_brick_plane apply.  Tiles start in grid order.
+ *     Frames are counted by vr_hip_timing, described by vr_hip_last_launch and counted by vr_hip_depth_frames (testing aid).  Single device:
+ *     the vr_hip_multi_* path has no depth frame.
+ * 10. Errors.  VR_ERR_INVALID for a NULL struct, a NULL depth buffer, mode > 2, a non-finite opacity, an opacity outside [0, 1], FIRST with
+ *     opacity 0 (a transparent sample would be a surface), and VR_SAMPLE_NEAREST.  Everything else as for vr_hip_render_iso*.
+ * Pick.  out[i] is by definition what a whole-frame depth frame stores at frame pixel (xy[2i], xy[2i+1]) (y up; the partition fields of
+ * params are ignored): hit = depth >= 0, and k, value, alpha are that pixel's values.  For a hit, with that pixel's own ray,
+ * position = fma(dir, k, origin) per axis and voxel = fma(k, A, B) per axis — a continuous voxel index: voxel i's centre is at i.  Without
+ * a hit k = -1, value = -1, position and voxel 0.  Synchronous, on the context's stream.  n = 0 is fine; n > 256, a pixel outside the
+ * window or a NULL pointer with n > 0 give VR_ERR_INVALID. */
+typedef enum vr_depth_mode { VR_DEPTH_FIRST = 0, VR_DEPTH_PEAK = 1, VR_DEPTH_MEAN = 2 } vr_depth_mode;
+typedef struct vr_depth {
+	float    opacity;     /* FIRST: the accumulated alpha a surface lies at, (0, 1]; PEAK, MEAN: in [0, 1], not looked at */
+	uint32_t mode;        /* vr_depth_mode */
+} vr_depth;               /* 8 bytes */
+typedef struct vr_depth_out {
+	void *depth;          /* out_width * out_rows floats */
+	void *value;          /* likewise, or NULL */
+	void *alpha;          /* likewise, or NULL */
+} vr_depth_out;           /* 24 bytes */
+typedef struct vr_pick {
+	uint32_t hit;
+	float    k;
+	float    position[3]; /* model space, cube [-1,1]^3 */
+	float    voxel[3];    /* continuous voxel index */
+	float    value;       /* raw voxel units */
+	float    alpha;
+} vr_pick;                /* 40 bytes */
+#define VR_PICK_MAX 256
+int vr_hip_render_depth_device(vr_ctx *ctx, const vr_params *params, const vr_depth *depth, const vr_depth_out *dev, void *stream);
+int vr_hip_render_depth(vr_ctx *ctx, const vr_params *params, const vr_depth *depth, const vr_depth_out *host);
+int vr_hip_pick(vr_ctx *ctx, const vr_params *params, const vr_depth *depth, uint32_t n, const uint32_t *xy /* 2n */, vr_pick *out);
+int vr_hip_depth_frames(vr_ctx *ctx, uint64_t *frames_out);            /* testing aid: depth frames launched (a pick counts one per query) */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

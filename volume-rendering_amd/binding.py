@@ -121,6 +121,34 @@ def make_section(plane, half_width=0.0, mode="point", window=None):
     return sec
 
 
+DEPTH_FIRST, DEPTH_PEAK, DEPTH_MEAN = 0, 1, 2
+DEPTH_MODES = {"first": DEPTH_FIRST, "peak": DEPTH_PEAK, "mean": DEPTH_MEAN}
+PICK_MAX = 256
+
+
+class VrDepth(C.Structure):
+    """vr_depth: the accumulated alpha a FIRST surface lies at, and the mode (DEPTH_*)"""
+    _fields_ = [("opacity", C.c_float), ("mode", C.c_uint32)]
+
+
+class VrDepthOut(C.Structure):
+    """vr_depth_out: the three float buffers of a depth frame; value and alpha may be NULL"""
+    _fields_ = [("depth", C.c_void_p), ("value", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class VrPick(C.Structure):
+    """vr_pick: what a depth frame stores at one pixel, with the model-space position and the continuous voxel index of a hit"""
+    _fields_ = [("hit", C.c_uint32), ("k", C.c_float), ("position", C.c_float * 3), ("voxel", C.c_float * 3), ("value", C.c_float), ("alpha", C.c_float)]
+
+
+def make_depth(opacity, mode="first"):
+    """A VrDepth; mode by name ("first", "peak", "mean") or number."""
+    d = VrDepth()
+    d.opacity = float(opacity)
+    d.mode = DEPTH_MODES[mode] if isinstance(mode, str) else int(mode)
+    return d
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -206,6 +234,10 @@ def lib():
         "vr_hip_render_section_in_volume": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp]),
         "vr_hip_render_section_in_volume_device": (C.c_int, [vp, P(VrParams), P(VrSection), vp, vp, vp]),
         "vr_hip_section_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_render_depth": (C.c_int, [vp, P(VrParams), P(VrDepth), P(VrDepthOut)]),
+        "vr_hip_render_depth_device": (C.c_int, [vp, P(VrParams), P(VrDepth), P(VrDepthOut), vp]),
+        "vr_hip_pick": (C.c_int, [vp, P(VrParams), P(VrDepth), u32, P(u32), P(VrPick)]),
+        "vr_hip_depth_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

@@ -171,4 +171,31 @@ int HipRenderer::render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop 
 	return rc == 0 ? 0 : 1;
 }
 
+int HipRenderer::render_depth(Raycaster r, const vr_depth &depth, const vr_depth_out *out) {
+	if (!ok() || out == nullptr)
+		return 1;
+	mirror_error_ = nullptr;
+	if (multi_) {
+		mirror_error_ = "a depth frame renders on a single device (vr_hip_render_depth): construct the renderer without a device list";
+		return 1;
+	}
+	vr_params p;
+	to_params(r, sampling_, &p);
+	const int rc = device_buffer_ ? vr_hip_render_depth_device(ctx_, &p, &depth, out, nullptr) : vr_hip_render_depth(ctx_, &p, &depth, out);
+	return rc == 0 ? 0 : 1;
+}
+
+int HipRenderer::pick(Raycaster r, const vr_depth &depth, uint32_t n, const uint32_t *xy, vr_pick *out) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	if (multi_) {
+		mirror_error_ = "a pick renders on a single device (vr_hip_pick): construct the renderer without a device list";
+		return 1;
+	}
+	vr_params p;
+	to_params(r, sampling_, &p);
+	return vr_hip_pick(ctx_, &p, &depth, n, xy, out) == 0 ? 0 : 1;
+}
+
 }  // namespace volr

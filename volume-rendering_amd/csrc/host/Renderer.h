@@ -108,6 +108,13 @@ class HipRenderer : public Renderer {
 		// renderer): `layer` holds host or device pointers accordingly, view.dims pixels each.  Whatever set_mip / set_iso / set_hybrid say,
 		// this is a composite frame.  Single device only.  0 = ok, 1 = failure.
 		int render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop *layer);
+		// One depth frame of the composite (vr_hip_render_depth / vr_hip_render_depth_device by the buffer flavour of this renderer): `out`
+		// holds host or device pointers accordingly, view.dims floats each; value and alpha may be NULL.  The clip and the pre-integration
+		// of this renderer apply.  Needs a TRILINEAR sampling mode.  Single device only.  0 = ok, 1 = failure.
+		int render_depth(Raycaster r, const vr_depth &depth, const vr_depth_out *out);
+		// What that depth frame stores at each of the n pixels xy[2i], xy[2i + 1] (y up), with the position and the voxel index of a hit
+		// (vr_hip_pick: host arrays, synchronous, at most 256 pixels).  Single device only.  0 = ok, 1 = failure.
+		int pick(Raycaster r, const vr_depth &depth, uint32_t n, const uint32_t *xy, vr_pick *out);
 		// The clip region of every later frame of this renderer — composite, set_mip and set_iso alike, and with a device list every device's
 		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
 		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.

@@ -6,7 +6,8 @@
 //              [-s <width> <height>] [-d <device>] [-devices <a,b,..>] [-b|-bg] [-pose <ax> <ay> <az> <dist>] [-persp] [-mip] [-iso <level> [-refine <n>]]
 //              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
 //              [-phong <ka> <kd> <ks> <n>] [-preint] [-hybrid <level> [-refine <n>]]
-//              [-section <nx> <ny> <nz> <d> [-section-half <h>] [-section-mode max|min|mean] [-section-window <lo> <hi>] [-section-in-volume]] [-o <frame.ppm>]
+//              [-section <nx> <ny> <nz> <d> [-section-half <h>] [-section-mode max|min|mean] [-section-window <lo> <hi>] [-section-in-volume]]
+//              [-depth <opacity> [-depth-mode first|peak|mean] [-pick <x> <y>]] [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -60,6 +61,11 @@ void print_usage() {
 	       "         or mean over the slab of that half width; -section-window: opaque grey between lo and hi (raw voxel units) instead of the transfer\n"
 	       "         function; -section-in-volume: the section seen through the translucent volume in front of it (the composite pass sees the clip,\n"
 	       "         -shadow, -phong and -preint); from the trilinear renderer (-r 1); single device; excludes -mip, -iso, -hybrid and -devices\n"
+	       "  -depth <opacity> [-depth-mode first|peak|mean] [-pick <x> <y>] : the depth frame of the composite instead of its colours: where along\n"
+	       "         its ray the thing a pixel shows lies — the first sample at which the accumulated alpha reaches <opacity> (default), the sample\n"
+	       "         that contributes most, or the contribution-weighted mean; -o writes the depth of the hits as a normalised grey image (near =\n"
+	       "         bright, no surface = black); -pick prints position, voxel index, value and alpha of pixel (x, y), y up; the clip and -preint\n"
+	       "         apply; from the trilinear renderer (-r 1); single device, single frame; excludes -mip, -iso, -hybrid and -section\n"
 	       "  -b | -bg : benchmark mode\n  -pose <ax> <ay> <az> <dist> [-persp] -o <frame.ppm> : render one frame to a PPM file\n");
 }
 
@@ -255,6 +261,47 @@ int write_ppm(const char *path) {
 	return 0;
 }
 
+// the depth of the hits as a grey image: near = 255, far = 1 over the range of the frame's surfaces, no surface = 0; top row first
+int write_depth_ppm(const char *path, const std::vector<float> &depth) {
+	FILE *f = fopen(path, "wb");
+	if (f == NULL) return 1;
+	const int w = ViewBase::view.dims.x, h = ViewBase::view.dims.y;
+	float lo = 0.0f, hi = 0.0f;
+	bool any = false;
+	for (float d : depth)
+		if (d >= 0.0f) { lo = any ? (d < lo ? d : lo) : d; hi = any ? (d > hi ? d : hi) : d; any = true; }
+	fprintf(f, "P6\n%d %d\n255\n", w, h);
+	for (int y = h - 1; y >= 0; y--)
+		for (int x = 0; x < w; x++) {
+			const float d = depth[(size_t) y * w + x];
+			unsigned char g = 0;
+			if (d >= 0.0f) {
+				const float s = hi > lo ? (d - lo) / (hi - lo) : 0.0f;
+				g = (unsigned char) (255.0f - s * 254.0f + 0.5f);
+			}
+			const unsigned char rgb[3] = { g, g, g };
+			fwrite(rgb, 1, 3, f);
+		}
+	fclose(f);
+	return 0;
+}
+
+// one depth frame of the trilinear renderer into `depth` (HipRenderer::render_depth), timed like draw_volume's frame
+int draw_depth(const vr_depth &d, std::vector<float> &depth) {
+	const size_t pixels = (size_t) ViewBase::view.dims.x * ViewBase::view.dims.y;
+	if (frame.size() != pixels) {
+		frame.resize(pixels);
+		for (int i = 0; i < PROFILER_RENDERERS; i++) renderers[i]->set_window_buffer(ViewBase::view);
+	}
+	depth.assign(pixels, -1.0f);
+	RaycasterBase::set_view(ViewBase::view);
+	const vr_depth_out out = { depth.data(), nullptr, nullptr };
+	Profiler::start(renderer_id);
+	const int rc = renderers[1]->render_depth(RaycasterBase::raycaster, d, &out);
+	Profiler::stop();
+	return rc;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -262,6 +309,9 @@ int main(int argc, char **argv) {
 	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false, hybrid = false;
 	float iso_level = 0.0f;
 	int iso_refine = 4;
+	bool depth_on = false, depth_mode_given = false, pick_on = false;
+	vr_depth depth_params = { 0.5f, VR_DEPTH_FIRST };
+	uint32_t pick_xy[2] = { 0u, 0u };
 	bool section_on = false, section_in_volume = false, section_mode_given = false, section_window_given = false;
 	vr_section section = { { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f, VR_SECTION_POINT, { 0.0f, 0.0f } };
 	bool clip_box = false, clip_plane = false;
@@ -322,6 +372,18 @@ int main(int argc, char **argv) {
 		}
 		else if (strcmp(arg, "-section-window") == 0) { if (need(2)) { section.window[0] = (float) atof(argv[++i]); section.window[1] = (float) atof(argv[++i]); section_window_given = true; } }
 		else if (strcmp(arg, "-section-in-volume") == 0) section_in_volume = true;
+		else if (strcmp(arg, "-depth") == 0) { if (need(1)) { depth_params.opacity = (float) atof(argv[++i]); depth_on = true; } }
+		else if (strcmp(arg, "-depth-mode") == 0) {
+			if (need(1)) {
+				const char *m = argv[++i];
+				if (strcmp(m, "first") == 0) depth_params.mode = VR_DEPTH_FIRST;
+				else if (strcmp(m, "peak") == 0) depth_params.mode = VR_DEPTH_PEAK;
+				else if (strcmp(m, "mean") == 0) depth_params.mode = VR_DEPTH_MEAN;
+				else { printf("Error: -depth-mode takes first, peak or mean\n"); return EXIT_FAILURE; }
+				depth_mode_given = true;
+			}
+		}
+		else if (strcmp(arg, "-pick") == 0) { if (need(2)) { pick_xy[0] = (uint32_t) atoi(argv[++i]); pick_xy[1] = (uint32_t) atoi(argv[++i]); pick_on = true; } }
 		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
 		else if (strcmp(arg, "-clip-box") == 0) {
 			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
@@ -398,6 +460,16 @@ int main(int argc, char **argv) {
 		printf("Error: -section-half, -section-mode, -section-window and -section-in-volume need -section\n"); return EXIT_FAILURE;
 	}
 
+	static const char *const depth_mode_names[] = { "first", "peak", "mean" };
+	if (depth_on) {
+		if (!device_list.empty()) { printf("Error: -depth renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		if (mip || iso || hybrid || section_on) { printf("Error: -depth excludes -mip, -iso, -hybrid and -section\n"); return EXIT_FAILURE; }
+		if (renderer_id != 1) { printf("Error: -depth needs the trilinear renderer (-r 1): a depth frame is defined on the interpolated field\n"); return EXIT_FAILURE; }
+		if (benchmark_mode) { printf("Error: -depth renders single frames (drop -b)\n"); return EXIT_FAILURE; }
+	} else if (depth_mode_given || pick_on) {
+		printf("Error: -depth-mode and -pick need -depth\n"); return EXIT_FAILURE;
+	}
+
 	if (clip_box || clip_plane) {
 		for (int i = 0; i < PROFILER_RENDERERS; i++)
 			if (renderers[i]->set_clip(&clip) != 0) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }
@@ -439,6 +511,22 @@ int main(int argc, char **argv) {
 	if (benchmark_mode) {
 		benchmark();
 		print_profiler();
+	} else if (depth_on) {
+		std::vector<float> depth;
+		if (draw_depth(depth_params, depth) != 0) { printf("Error: %s\n", renderers[1]->last_error()); rc = EXIT_FAILURE; }
+		else {
+			size_t surfaces = 0;
+			for (float d : depth) surfaces += d >= 0.0f ? 1u : 0u;
+			printf("Depth: mode %s, opacity %g: %zu of %zu pixels carry a surface\n", depth_mode_names[depth_params.mode], depth_params.opacity, surfaces, depth.size());
+			printf("%s: %dx%d depth frame in %.2f ms\n", renderers[1]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);
+			if (pick_on) {
+				vr_pick pk;
+				if (renderers[1]->pick(RaycasterBase::raycaster, depth_params, 1u, pick_xy, &pk) != 0) { printf("Error: %s\n", renderers[1]->last_error()); rc = EXIT_FAILURE; }
+				else printf("Pick (%u, %u): hit %u k %.9g position (%.9g, %.9g, %.9g) voxel (%.9g, %.9g, %.9g) value %.9g alpha %.9g\n", pick_xy[0], pick_xy[1], pk.hit, pk.k,
+				            pk.position[0], pk.position[1], pk.position[2], pk.voxel[0], pk.voxel[1], pk.voxel[2], pk.value, pk.alpha);
+			}
+			if (!out_ppm.empty() && write_depth_ppm(out_ppm.c_str(), depth) != 0) { printf("Error: cannot write %s\n", out_ppm.c_str()); rc = EXIT_FAILURE; }
+		}
 	} else {
 		draw_volume();
 		printf("%s: %dx%d frame in %.2f ms\n", renderers[renderer_id]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);

@@ -399,6 +399,24 @@ struct SectionArgs {
 hipError_t launch_section(const RayKernelArgs &a, const SectionArgs &section, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
                           const float *tf_premult, void *out_rgba, void *out_depth, hipStream_t stream);
 
+// ---- depth frames of the composite and picking (include/vr_hip.h vr_hip_render_depth) ----
+// The depth of one frame, a kernel argument of its own behind the ones a composite frame takes.
+struct DepthArgs {
+	float    opacity;                  // FIRST: the accumulated alpha a surface lies at
+	uint32_t mode;                     // vr_depth_mode
+	uint32_t slab;                     // 1: slab classification (vr_hip_set_preintegration), 0: the filtered lookup
+	uint32_t want_alpha;               // 0: no alpha buffer is asked for — a FIRST ray may stop at its surface
+};
+// One depth frame.  `a`, `linear` and `bricked` as for launch_section (the same rows), the clip words of `a` filled; a.p.esl != 0 = leap with
+// esl_bits (1024 words) and the block grid of a.esl_div_*, the caller's params'; a.skip_mask / skip_cmp / tf_zero_below as launch_raymarch takes
+// them.  tf_premult: the 128 entries and K behind them.  out_value and out_alpha may be NULL.
+hipError_t launch_depth(const RayKernelArgs &a, const DepthArgs &depth, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
+                        const float *tf_premult, const uint32_t *esl_bits, void *out_depth, void *out_value, void *out_alpha, hipStream_t stream);
+// The pick's finishing kernel: query i's pixel (xy[2i], xy[2i+1]) of the view of a.p, its depth / value / alpha at element i of the three
+// arrays -> out[i] (vr_pick), position and voxel index formed on the device from pixel_ray of that pixel.
+hipError_t launch_pick_finish(const RayKernelArgs &a, uint32_t n, const uint32_t *xy, const float *depth, const float *value, const float *alpha,
+                              vr_pick *out, hipStream_t stream);
+
 // ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
 // What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
 struct ShadowBuildArgs {

@@ -122,6 +122,12 @@ struct vr_ctx {
 	uint64_t section_frames = 0;
 	float *hybrid_depth = nullptr; size_t hybrid_depth_bytes = 0;
 	void *backdrop_stage = nullptr; size_t backdrop_stage_bytes = 0;
+	// depth frames (vr_hip_render_depth*, vr_hip_pick): the frames launched on the depth kernels (a pick counts one per query); the three
+	// float buffers of the host entry point, grown on demand; and the pick's buffers, allocated on first use for VR_PICK_MAX queries: the
+	// pixels, depth / value / alpha per query, and the answers
+	uint64_t depth_frames = 0;
+	void *depth_stage = nullptr; size_t depth_stage_bytes = 0;
+	void *pick_stage = nullptr; size_t pick_stage_bytes = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -406,6 +412,19 @@ void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 	}
 }
 
+// the corner test of the transparent-sample shortcut (RayKernelArgs::skip_mask / skip_cmp) for the resident transfer function: the largest
+// power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below — raw < P implies a transparent sample
+void transparent_corner_test(const vr_ctx *c, RayKernelArgs &a) {
+	uint32_t below = 0;
+	const uint32_t top = c->bpv == 1 ? 256u : 65536u;
+	for (uint32_t P = 1; P <= top; P <<= 1)
+		if (c->tf_zero_below >= 0.0f && std::fmaf((float) P, a.tf_scale, -0.5f) <= c->tf_zero_below) below = P;
+	a.skip_cmp = below == 0 ? 1u : 0u;
+	if (below == 0) a.skip_mask = 0u;
+	else if (c->bpv == 1) a.skip_mask = ((0xffu & ~(below - 1u)) * 0x01010101u);
+	else a.skip_mask = ((0xffffu & ~(below - 1u)) * 0x00010001u);
+}
+
 // index / block edge of the ESL grid, prepared as shift or multiply-high (RaycasterBase.h:59-63)
 void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
 	const uint32_t bd = block_dims ? block_dims : 1u;
@@ -605,16 +624,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	}
 	const float half[3] = { a.half_x, a.half_y, a.half_z };
 	const ViewAxis va = view_axis(p, half);
-	{   // largest power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below: raw < P implies a transparent sample
-		uint32_t below = 0;
-		const uint32_t top = c->bpv == 1 ? 256u : 65536u;
-		for (uint32_t P = 1; P <= top; P <<= 1)
-			if (c->tf_zero_below >= 0.0f && std::fmaf((float) P, a.tf_scale, -0.5f) <= c->tf_zero_below) below = P;
-		a.skip_cmp = below == 0 ? 1u : 0u;
-		if (below == 0) a.skip_mask = 0u;
-		else if (c->bpv == 1) a.skip_mask = ((0xffu & ~(below - 1u)) * 0x01010101u);
-		else a.skip_mask = ((0xffffu & ~(below - 1u)) * 0x00010001u);
-	}
+	transparent_corner_test(c, a);
 	{   // fp32 sample coordinates that are not exact to a fraction of a cell: clamp every sample
 		const float omax = max_abs_origin(p), nmax = (float) max_dim_of(c);
 		a.clamp_fetch = fetch_coordinates_exact(c, p) ? 0u : 1u;
@@ -1366,6 +1376,37 @@ int launch_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *s,
 	return launch_frame(c, p, dev_rgba, stream, &layer);
 }
 
+// what the depth entry points check beyond render_preamble (include/vr_hip.h, step 10 of the depth contract)
+int validate_depth(vr_ctx *c, const vr_params *p, const vr_depth *d) {
+	if (d == nullptr) return fail(c, VR_ERR_INVALID, "depth is NULL");
+	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
+		return fail(c, VR_ERR_INVALID, "a depth frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (d->mode > VR_DEPTH_MEAN) return fail(c, VR_ERR_INVALID, "depth mode must be in 0..2");
+	if (!std::isfinite(d->opacity) || d->opacity < 0.0f || d->opacity > 1.0f) return fail(c, VR_ERR_INVALID, "depth opacity must be finite and in [0, 1]");
+	if (d->mode == VR_DEPTH_FIRST && d->opacity == 0.0f) return fail(c, VR_ERR_INVALID, "a FIRST depth needs opacity > 0: a transparent sample would be a surface");
+	return VR_OK;
+}
+
+// One depth frame (include/vr_hip.h vr_hip_render_depth): what a clipped MIP frame of the same view and sampling reads and maps — the frame
+// goes through launch_full_march_frame with esl off, so no block maxima are built and the volume's own grid is not looked at —, then the
+// composite's leaping (params.esl, the ESL bits of vr_hip_set_transfer_fn, the block grid of the params) and its transparent-sample test are
+// put back into the kernel argument, and the classification is the context's.  volume_args has filled the clip words.
+int launch_depth_frame(vr_ctx *c, const vr_params *p, const vr_depth *d, const vr_depth_out *out, hipStream_t stream) {
+	vr_params q = *p;
+	q.esl = 0u;
+	DepthArgs da;
+	da.opacity = d->opacity; da.mode = d->mode; da.slab = c->preint_on ? 1u : 0u; da.want_alpha = out->alpha != nullptr ? 1u : 0u;
+	const int rc = launch_full_march_frame(c, &q, stream, "depth", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		RayKernelArgs b = a;
+		b.p.esl = p->esl;
+		esl_divisor(b, p->esl_block_dims);
+		transparent_corner_test(c, b);
+		return launch_depth(b, da, c->vol, brick_copy, c->bpv, c->tf, c->esl, out->depth, out->value, out->alpha, stream);
+	});
+	if (rc == VR_OK) c->depth_frames++;
+	return rc;
+}
+
 // the depth buffer of the host entry points that hand a depth back (vr_hip_render_iso, vr_hip_render_section): one float per pixel of the
 // window, sized with the window (render_preamble: the frame fits), allocated on first use behind the context's frames
 int size_host_depth(vr_ctx *c) {
@@ -1454,6 +1495,8 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->iso_depth) (void) hipFree(c->iso_depth);
 	if (c->hybrid_depth) (void) hipFree(c->hybrid_depth);
 	if (c->backdrop_stage) (void) hipFree(c->backdrop_stage);
+	if (c->depth_stage) (void) hipFree(c->depth_stage);
+	if (c->pick_stage) (void) hipFree(c->pick_stage);
 	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
@@ -1914,6 +1957,79 @@ int vr_hip_render_section_in_volume(vr_ctx *c, const vr_params *p, const vr_sect
 int vr_hip_section_frames(vr_ctx *c, uint64_t *frames_out) {
 	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
 	*frames_out = c->section_frames;
+	return VR_OK;
+}
+
+// ---- depth frames of the composite and picking (include/vr_hip.h vr_depth) ----
+
+int vr_hip_render_depth_device(vr_ctx *c, const vr_params *p, const vr_depth *d, const vr_depth_out *dev, void *stream) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (dev == nullptr) return fail(c, VR_ERR_INVALID, "depth_out is NULL");
+	if (const int rc = render_preamble(c, p, dev->depth, false)) return rc;
+	if (const int rc = validate_depth(c, p, d)) return rc;
+	return launch_depth_frame(c, p, d, dev, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_depth(vr_ctx *c, const vr_params *p, const vr_depth *d, const vr_depth_out *host) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (host == nullptr) return fail(c, VR_ERR_INVALID, "depth_out is NULL");
+	int rc = render_preamble(c, p, host->depth, false);
+	if (rc) return rc;
+	rc = validate_depth(c, p, d);
+	if (rc) return rc;
+	// one launch, and one copy back per buffer asked for, out of one context-owned staging buffer: depth, value, alpha
+	const size_t bytes = (size_t) p->out_width * p->out_rows * sizeof(float);
+	if (const int grow = grow_buffer(c, &c->depth_stage, c->depth_stage_bytes, 3 * bytes)) return grow;
+	uint8_t *stage = (uint8_t *) c->depth_stage;
+	const vr_depth_out dev = { stage, host->value ? stage + bytes : nullptr, host->alpha ? stage + 2 * bytes : nullptr };
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_depth_frame(c, p, d, &dev, c->stream);
+	if (rc) return rc;
+	VR_TRY(c, hipMemcpyAsync(host->depth, dev.depth, bytes, hipMemcpyDeviceToHost, c->stream));
+	if (host->value) VR_TRY(c, hipMemcpyAsync(host->value, dev.value, bytes, hipMemcpyDeviceToHost, c->stream));
+	if (host->alpha) VR_TRY(c, hipMemcpyAsync(host->alpha, dev.alpha, bytes, hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	take_total_time(c, t0);
+	return VR_OK;
+}
+
+int vr_hip_pick(vr_ctx *c, const vr_params *p, const vr_depth *d, uint32_t n, const uint32_t *xy, vr_pick *out) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (n == 0u) return VR_OK;
+	if (n > VR_PICK_MAX) return fail(c, VR_ERR_INVALID, "at most VR_PICK_MAX (256) pixels per pick");
+	if (xy == nullptr) return fail(c, VR_ERR_INVALID, "xy is NULL");
+	int rc = render_preamble(c, p, out, false);
+	if (rc) return rc;
+	rc = validate_depth(c, p, d);
+	if (rc) return rc;
+	for (uint32_t i = 0; i < n; i++)
+		if (xy[2u * i] >= p->view.width || xy[2u * i + 1u] >= p->view.height) return fail(c, VR_ERR_INVALID, "pick: a pixel lies outside the window");
+	// one launch per query with a one-pixel crop into element i of the context's three arrays, the finishing kernel over all of them, one copy back
+	constexpr size_t kXy = 0, kDepth = kXy + VR_PICK_MAX * 2 * sizeof(uint32_t), kValue = kDepth + VR_PICK_MAX * sizeof(float),
+	                 kAlpha = kValue + VR_PICK_MAX * sizeof(float), kOut = kAlpha + VR_PICK_MAX * sizeof(float), kBytes = kOut + VR_PICK_MAX * sizeof(vr_pick);
+	if (const int grow = grow_buffer(c, &c->pick_stage, c->pick_stage_bytes, kBytes)) return grow;
+	uint8_t *stage = (uint8_t *) c->pick_stage;
+	VR_TRY(c, hipMemcpyAsync(stage + kXy, xy, (size_t) n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	vr_params q = *p;
+	q.out_width = 1; q.out_rows = 1; q.band_rows = 1; q.band_stride = p->view.height;       // row band_first of bands of one row: frame_row(0) = y
+	for (uint32_t i = 0; i < n; i++) {
+		q.x0 = xy[2u * i]; q.band_first = xy[2u * i + 1u];
+		const vr_depth_out dev = { stage + kDepth + i * sizeof(float), stage + kValue + i * sizeof(float), stage + kAlpha + i * sizeof(float) };
+		rc = launch_depth_frame(c, &q, d, &dev, c->stream);
+		if (rc) return rc;
+	}
+	RayKernelArgs a;
+	volume_args(c, p, a);
+	VR_TRY(c, launch_pick_finish(a, n, (const uint32_t *) (stage + kXy), (const float *) (stage + kDepth), (const float *) (stage + kValue),
+	                             (const float *) (stage + kAlpha), (vr_pick *) (stage + kOut), c->stream));
+	VR_TRY(c, hipMemcpyAsync(out, stage + kOut, (size_t) n * sizeof(vr_pick), hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	return VR_OK;
+}
+
+int vr_hip_depth_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->depth_frames;
 	return VR_OK;
 }
 

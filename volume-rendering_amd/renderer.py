@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import VrBackdrop, VrError, VrIso, VrLaunchInfo, VrParams, VrTiming, lib, make_clip, make_lighting, make_section, make_shadow
+from .binding import (VrBackdrop, VrDepthOut, VrError, VrIso, VrLaunchInfo, VrParams, VrPick, VrTiming, lib, make_clip, make_depth, make_lighting, make_section,
+                      make_shadow)
 
 
 class HipRenderer:
@@ -351,6 +352,51 @@ class HipRenderer:
         """vr_hip_section_frames: the section frames this context launched"""
         n = C.c_uint64(0)
         self._check(self._L.vr_hip_section_frames(self._ctx, C.byref(n)), "section_frames")
+        return int(n.value)
+
+    # -- depth frames of the composite and picking (vr_hip_render_depth, vr_hip_pick)
+    def render_depth(self, params, opacity, mode="first", value=False, alpha=False):
+        """Host-buffer flavour: where along its ray the thing a composite pixel shows lies, float32 (out_rows, out_width): k of the pixel's own
+        ray, -1 where there is no surface.  mode "first" (the first sample at which the accumulated alpha reaches `opacity`), "peak" (the
+        sample that contributes most) or "mean" (the contribution-weighted mean).  value=True adds the interpolated raw value there, alpha=True
+        the pixel's final alpha — the alpha channel of the composite frame before it becomes a byte: (depth[, value][, alpha]).  The
+        context's clip and pre-integration apply; shadow and lighting are ignored.  params.sampling must be one of the TRILINEAR modes."""
+        d = make_depth(opacity, mode)
+        shape = (params.out_rows, params.out_width)
+        dep = np.empty(shape, dtype=np.float32)
+        val = np.empty(shape, dtype=np.float32) if value else None
+        alp = np.empty(shape, dtype=np.float32) if alpha else None
+        out = VrDepthOut(dep.ctypes.data, val.ctypes.data if value else None, alp.ctypes.data if alpha else None)
+        self._check(self._L.vr_hip_render_depth(self._ctx, C.byref(params), C.byref(d), C.byref(out)), "render_depth")
+        got = (dep,) + ((val,) if value else ()) + ((alp,) if alpha else ())
+        return got if len(got) > 1 else dep
+
+    def render_depth_device(self, params, opacity, mode, depth_ptr, value_ptr=None, alpha_ptr=None, stream=None):
+        """Device-buffer flavour: asynchronous launch into `depth_ptr` and, if given, `value_ptr` and `alpha_ptr` (float32 each) on `stream`
+        (raw hipStream_t or None)."""
+        d = make_depth(opacity, mode)
+        out = VrDepthOut(depth_ptr if depth_ptr else None, value_ptr if value_ptr else None, alpha_ptr if alpha_ptr else None)
+        self._check(self._L.vr_hip_render_depth_device(self._ctx, C.byref(params), C.byref(d), C.byref(out), C.c_void_p(stream) if stream else None),
+                    "render_depth_device")
+
+    def pick(self, params, pixels, opacity, mode="first"):
+        """What a whole-frame depth frame of `params` stores at each of `pixels` ((x, y) pairs of the view, y up; at most 256), as a list of
+        dicts: hit, k, position (model space), voxel (continuous voxel index), value, alpha.  The partition fields of params are ignored."""
+        d = make_depth(opacity, mode)
+        xy = np.ascontiguousarray(np.asarray(pixels, dtype=np.int64).reshape(-1, 2))
+        n = xy.shape[0]
+        if (xy < 0).any() or (xy > 0xffffffff).any():
+            raise VrError(1, "pick: a pixel lies outside the window")
+        xy = xy.astype(np.uint32)
+        out = (VrPick * max(n, 1))()
+        self._check(self._L.vr_hip_pick(self._ctx, C.byref(params), C.byref(d), n, xy.ctypes.data_as(C.POINTER(C.c_uint32)), out), "pick")
+        return [{"hit": bool(o.hit), "k": float(o.k), "position": tuple(o.position), "voxel": tuple(o.voxel), "value": float(o.value), "alpha": float(o.alpha)}
+                for o in out[:n]]
+
+    def depth_frames(self):
+        """vr_hip_depth_frames: the depth frames this context launched (a pick counts one per pixel)"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_depth_frames(self._ctx, C.byref(n)), "depth_frames")
         return int(n.value)
 
     # -- timing (Profiler.cpp:46-67)
