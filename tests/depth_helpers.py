@@ -1,6 +1,9 @@
 """Test-side helpers of the depth tests: depth_render of tests/depth_ref.c (the depth frames of include/vr_hip.h vr_hip_render_depth /
 vr_hip_pick, restated with the CPU oracle's own statics on top of tests/feature_ref.c), built through ref_library.compile_test_library,
-and the opacities and the frame list both tiers walk."""
+the opacities and the frame list both tiers walk, and what the GPU tiers do with one frame (check, classify, depth_launch).
+The `cmode` of DepthRef.render is slab_helpers' POINT or SLAB — and SLAB_SKIPPED_IS_NONE, slab_colour's wrong reading "a sample the
+library may skip unresolved counts as no predecessor", which depth_render passes to slab_colour unchanged: the sensitivity of the holed
+scenes of tests/feature_random.py (tests/test_depth_random_model.py)."""
 import atexit
 import ctypes as C
 import shutil
@@ -9,6 +12,7 @@ import tempfile
 import numpy as np
 
 from clip_helpers import CLIPS, IDENTITY
+from gpu_feature import depth_diff
 from light_helpers import LIT_VOLUMES, PHONG, lit_views
 from ref_library import Ref, SceneArgs, compile_test_library, frame_array, ptr
 from slab_helpers import POINT, SLAB, slab_scene
@@ -69,7 +73,7 @@ class DepthFrame:
 
 
 class DepthRef(Ref):
-    """depth_render of tests/depth_ref.c on WHOLE frames; cached per argument set."""
+    """depth_render of tests/depth_ref.c on WHOLE frames; cached per argument set.  cmode: POINT, SLAB or SLAB_SKIPPED_IS_NONE."""
 
     def __init__(self):
         super().__init__()
@@ -92,6 +96,33 @@ def alpha_byte(alpha):
     """map_float_int(alpha, 256): (int) (alpha * 256.0f) clamped to 0..255"""
     scaled = (np.asarray(alpha, np.float32) * np.float32(256.0)).astype(np.float32)
     return np.clip(scaled.astype(np.int64), 0, 255).astype(np.uint8)
+
+
+# ---- what the GPU tiers (tests/test_gpu_depth.py, tests/test_gpu_depth_random.py) do with one frame ----
+
+def depth_launch(info):
+    """what every depth frame's launch looks like: what a clipped MIP frame reads, tiles in grid order"""
+    return info["layout"] in (0, 1, 5) and info["ordered"] == 0
+
+
+def classify(gpu, cmode):
+    if cmode == SLAB:
+        gpu.set_preintegration()
+    else:
+        gpu.clear_preintegration()
+
+
+def check(gpu, ref, what, vox, p, tf, esl, opacity, mode, cmode=POINT, clip=IDENTITY):
+    """the host entry point with all three buffers (depth, value and alpha bits) against depth_render; returns the restatement's frame.
+    The context's clip and classification are the caller's business."""
+    want = ref.render(p, vox, tf, esl, opacity, mode, cmode, clip)
+    depth, value, alpha = gpu.render_depth(p, opacity, mode, value=True, alpha=True)
+    info = gpu.last_launch()
+    wrong = depth_diff(depth, want.depth), depth_diff(value, want.value), depth_diff(alpha, want.alpha)
+    assert wrong == (0, 0, 0), (what, opacity, mode, wrong, info)
+    assert depth_launch(info), (what, info)
+    assert (depth[depth != -1.0] >= 0.0).all(), (what, "every surface reads as a surface to a backdrop frame")
+    return want
 
 
 def tier_frames(vr, golden, oracle, volumes, name, sampling):

@@ -9,7 +9,8 @@
  * contract, and the position and voxel index of a pick, nothing else.
  *
  * Whole frames only.  clip: the ten floats of vr_clip, never NULL (a depth frame always runs the clip's arithmetic: the identity clip when
- * none is set).  cmode: 0 = point classification, 1 = slab classification.  mode: vr_depth_mode.
+ * none is set).  cmode: 0 = point classification, 1 = slab classification, 3 = slab_colour's wrong reading "a skipped predecessor is none" (sensitivity;
+ * passed to slab_colour unchanged).  mode: vr_depth_mode.
  * perturb: 0 = the contract.  The sensitivity test's wrong readings of it: 1 = FIRST tests acc before the update; 2 = the sample that
  * terminates the ray is not recorded; 3 = MEAN divides by the final alpha; 4 = PEAK takes the last of equal peaks (`g >= best`).
  */
@@ -26,7 +27,7 @@ enum { DEPTH_ACC_BEFORE = 1, DEPTH_TERMINATOR_LOST = 2, DEPTH_MEAN_BY_ALPHA = 3,
 int depth_render(const vr_params *p, const void *voxels, const uint32_t dims[3], uint32_t bpv, const float *tf, const uint32_t *esl, const float *clip,
                  uint32_t cmode, float opacity, uint32_t mode, uint32_t perturb, float *depth_out, float *value_out, float *alpha_out, uint32_t *count_out,
                  float *last_out, float *pick_out, uint64_t *wide_out) {
-	if (!trilinear_mode(p) || cmode > 1 || mode > DEPTH_MEAN || perturb > 4 || clip == NULL)
+	if (!trilinear_mode(p) || (cmode > 1 && cmode != 3) || mode > DEPTH_MEAN || perturb > 4 || clip == NULL)
 		return 1;
 	const scene s = scene_of(p, voxels, dims, bpv, tf, esl);
 	slab_tables tables;

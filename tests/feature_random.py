@@ -5,7 +5,8 @@ direction, the four-fold ray step); this module adds a clip, a light, a grid siz
 hand-made EDGE_SHAPES.  Everything is drawn from numpy generators seeded from VR_TEST_SEED (default 20261019), one per list of frames, so
 that both tiers see the same frames whatever the order of the tests.  The slab, backdrop and hybrid frames (ExpectedLayers) reuse those
 frames as they are — nothing more is drawn from the scene generators — and take their depth layers from backdrop_helpers.synthetic_layer
-under salts of 2000 and above.  A plain module: no fixtures."""
+under salts of 2000 and above.  The depth frames and picks (ExpectedDepth, depth_draws) reuse them too: their opacities follow from
+the frames' indices, and the pixels of the picks and the partitions come from a stream of their own.  A plain module: no fixtures."""
 import os
 
 import numpy as np
@@ -319,3 +320,98 @@ class ExpectedLayers:
         self.rgba, self.depth = synthetic_layer(ref, f.p, v, tf, esl, f.clip, salt=salt)
         self.backdrop = ref.render(f.p, v, tf, esl, self.rgba, self.depth, POINT, f.clip)
         self.backdrop_all = ref.render(f.p, v, tf, esl, self.rgba, self.depth, *states)
+
+
+# ---- the depth frames and picks on the same lists (tests/test_depth_random_model.py, tests/test_gpu_depth_random.py) ----
+# Nothing here draws from the streams of the lists above: the opacity of a frame follows from its indices, and the pixels of the picks and
+# the partitions come from DEPTH_STREAM, which no other list uses (0-7, 99, 411 + 1000 * salt, 412 and 611 are taken).
+
+DEPTH_STREAM = 8
+DEPTH_OPACITIES = (0.1, 0.5, 0.9)
+DEPTH_MODES = ("first", "peak", "mean")              # depth_helpers.MODES
+PICK_MAX, PICK_DRAWN = 256, 60                       # vr_hip_pick takes 256 pixels a call; the larger frames: four corners and 60 drawn pixels
+THRESHOLD, ABOVE_THRESHOLD = "threshold", "above"
+# FIRST at the edges of (0, 1]: the smallest subnormal, the smallest normal, 1, and — on the frames that terminate early — the frame's
+# ray_threshold and the next float32 above it
+EDGE_OPACITIES = (float(np.float32(1e-45)), float(np.finfo(np.float32).tiny), 1.0, THRESHOLD, ABOVE_THRESHOLD)
+
+
+def depth_opacity(scene_index, frame_index):
+    return DEPTH_OPACITIES[(scene_index + frame_index) % 3]
+
+
+def edge_opacities(p):
+    """EDGE_OPACITIES for the frame `p` as (label, float32 value) pairs: the last two only where ray_threshold < 1"""
+    t = np.float32(p.ray_threshold)
+    out = [("subnormal", EDGE_OPACITIES[0]), ("tiny", EDGE_OPACITIES[1]), ("one", EDGE_OPACITIES[2])]
+    if t < np.float32(1.0):
+        out += [(THRESHOLD, float(t)), (ABOVE_THRESHOLD, float(np.nextafter(t, np.float32(2.0))))]
+    return out
+
+
+def full_march(p):
+    """a copy of the params without leaping and early termination: the march itself meets whatever the volume holds"""
+    q = p.copy()
+    q.esl, q.ray_threshold = 0, 1.0
+    return q
+
+
+def depth_list(oracle, vr, which):
+    """[(n, scene index, frame index, scene, frame, opacity)] of the "random" (56) or "holed" (24) frames, n counting the frames"""
+    scenes = random_scenes(oracle, vr) if which == "random" else holed_scenes(oracle, vr)
+    return [(s * len(scene.frames) + i, s, i, scene, f, depth_opacity(s, i)) for s, scene in enumerate(scenes) for i, f in enumerate(scene.frames)]
+
+
+class ExpectedDepth:
+    """depth_render's answers for one (scene, frame) under the frame's clip, beside Expected and ExpectedLayers: what the GPU tier compares
+    with and the CPU tier holds the caps on.  `p`: other params for the same view (full_march); the frames are the restatement's cached ones."""
+
+    def __init__(self, scene, f, opacity, p=None):
+        from depth_helpers import DepthRef
+        self.ref, self.scene, self.f, self.p, self.opacity = DepthRef.instance(), scene, f, (f.p if p is None else p), opacity
+
+    def frame(self, cmode, mode, opacity=None, perturb=0):
+        s = self.scene
+        return self.ref.render(self.p, s.vox, s.tf, s.esl, self.opacity if opacity is None else opacity, mode, cmode, self.f.clip, perturb)
+
+
+def pick_state(n):
+    """(classification, mode) of the picks on the n-th frame of a list: the classification alternates, the modes rotate"""
+    return n % 2, DEPTH_MODES[n % 3]
+
+
+_depth_draws = None
+
+
+def depth_draws(oracle, vr):
+    """Everything the depth tests draw, once, in a fixed order from DEPTH_STREAM: {"picks": {(list, n): [(x, y), ...]}, "partitions":
+    [(n, mode, world, band_rows, x0, crop width)]}.  Picks: every pixel of a random frame of at most PICK_MAX pixels (nothing drawn), else
+    the four corners and PICK_DRAWN drawn pixels.  Partitions: the first four random frames of a drawn permutation that are at least
+    8 x 8 and have a surface in the frame's mode under both classifications; 2 or 3 ranks, bands of 1, 3 or 16 rows, a crop in x."""
+    global _depth_draws
+    if _depth_draws is None:
+        rng = generator(DEPTH_STREAM)
+        picks = {}
+        for which in ("random", "holed"):
+            for n, s, i, scene, f, opacity in depth_list(oracle, vr, which):
+                w, h = f.p.view.width, f.p.view.height
+                if which == "random" and w * h <= PICK_MAX:
+                    picks[which, n] = [(x, y) for y in range(h) for x in range(w)]
+                else:
+                    picks[which, n] = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1)] + \
+                        [(int(x), int(y)) for x, y in zip(rng.integers(0, w, PICK_DRAWN), rng.integers(0, h, PICK_DRAWN))]
+        frames = depth_list(oracle, vr, "random")
+        partitions = []
+        for n in (int(k) for k in rng.permutation(len(frames))):
+            _, s, i, scene, f, opacity = frames[n]
+            w, h = f.p.view.width, f.p.view.height
+            mode = DEPTH_MODES[len(partitions) % 3]
+            e = ExpectedDepth(scene, f, opacity)
+            if w < 8 or h < 8 or not all(e.frame(cmode, mode).surface.any() for cmode in (0, 1)):
+                continue
+            x0 = int(rng.integers(0, w - 3))
+            partitions.append((n, mode, int(rng.choice([2, 3])), int(rng.choice([1, 3, 16])), x0, int(rng.integers(1, w - x0 + 1))))
+            if len(partitions) == 4:
+                break
+        _depth_draws = {"picks": picks, "partitions": partitions}
+    return _depth_draws

@@ -161,6 +161,7 @@ def test_bands_crop_and_in_place(vr, gpu, golden, oracle, volumes):
     dlayer = torch.from_numpy(np.array(depth)).cuda()
     buf = torch.full((70, 120, 4), 77, dtype=torch.uint8, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()                            # (the uploads and the fill run on torch's stream, the frame on the context's)
     gpu.timing_reset()
     before = gpu.backdrop_frames()
     gpu.render_backdrop_device(whole, layer.data_ptr(), dlayer.data_ptr(), buf.data_ptr(), stream)
@@ -303,13 +304,16 @@ def test_hybrid_equals_the_restatement(vr, gpu, golden, oracle, volumes, name):
                 want, want_depth, want_iso = ref.hybrid(p, vox, tf, esl, level, refine)
                 two = torch.full(shape + (4,), 77, dtype=torch.uint8, device="cuda")
                 two_depth = torch.full(shape, 123.0, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()                # (the fills run on torch's stream, the frame on the context's)
                 gpu.render_iso_device(p, level, refine, two.data_ptr(), two_depth.data_ptr(), stream)
                 gpu.render_backdrop_device(p, two.data_ptr(), two_depth.data_ptr(), two.data_ptr(), stream)
                 one = torch.full(shape + (4,), 78, dtype=torch.uint8, device="cuda")
                 one_depth = torch.full(shape, 124.0, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()                # (the fills run on torch's stream, the frame on the context's)
                 before = gpu.backdrop_frames()
                 gpu.render_hybrid_device(p, level, refine, one.data_ptr(), one_depth.data_ptr(), stream)
                 own = torch.full(shape + (4,), 79, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()                # (the fill runs on torch's stream, the frame on the context's)
                 gpu.render_hybrid_device(p, level, refine, own.data_ptr(), None, stream)
                 torch.cuda.synchronize()
                 what = (name, label, sampling, full_march, refine)

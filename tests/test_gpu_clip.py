@@ -260,6 +260,7 @@ def test_errors_and_entry_points(vr, gpu, golden, oracle, volumes, tf):
     bufs = [torch.full((72, 120, 4), 77, dtype=torch.uint8, device="cuda") for _ in range(3)]
     dbuf = torch.full((72, 120), 123.0, dtype=torch.float32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()                            # (the fills run on torch's stream, the frame on the context's)
     gpu.timing_reset()
     gpu.render_volume_device(p, bufs[0].data_ptr(), stream)
     gpu.render_mip_device(q, bufs[1].data_ptr(), stream)

@@ -9,8 +9,8 @@ import pytest
 
 import feature_random as fr
 from backdrop_helpers import BackdropRef
-from clip_helpers import CLIPS, IDENTITY, set_clip
-from depth_helpers import DEPTH_VOLUMES, MODES, OPACITIES, DepthRef, alpha_byte, tier_frames
+from clip_helpers import CLIPS, set_clip
+from depth_helpers import DEPTH_VOLUMES, MODES, OPACITIES, DepthRef, alpha_byte, check, classify, depth_launch, tier_frames
 from gpu_feature import PATH_VOLUMES, depth_diff, diff, expected_bands, load, needs_bounds_lib, reset_context, run_driver, run_under_bounds_build, sweep_paths
 from light_helpers import PHONG, lit_views, lit_volumes
 from shadow_helpers import LIGHTS
@@ -29,31 +29,6 @@ def state_off_afterwards(vr, gpu):
     """the context is shared by the whole session: no test leaves a state, a layout or a forced path behind"""
     yield
     reset_context(vr, gpu)
-
-
-def depth_launch(info):
-    """what every depth frame's launch looks like: what a clipped MIP frame reads, tiles in grid order"""
-    return info["layout"] in (0, 1, 5) and info["ordered"] == 0
-
-
-def classify(gpu, cmode):
-    if cmode == SLAB:
-        gpu.set_preintegration()
-    else:
-        gpu.clear_preintegration()
-
-
-def check(gpu, ref, what, vox, p, tf, esl, opacity, mode, cmode=POINT, clip=IDENTITY):
-    """the host entry point with all three buffers (depth, value and alpha bits) against depth_render; returns the restatement's frame.
-    The context's clip and classification are the caller's business."""
-    want = ref.render(p, vox, tf, esl, opacity, mode, cmode, clip)
-    depth, value, alpha = gpu.render_depth(p, opacity, mode, value=True, alpha=True)
-    info = gpu.last_launch()
-    wrong = depth_diff(depth, want.depth), depth_diff(value, want.value), depth_diff(alpha, want.alpha)
-    assert wrong == (0, 0, 0), (what, opacity, mode, wrong, info)
-    assert depth_launch(info), (what, info)
-    assert (depth[depth != -1.0] >= 0.0).all(), (what, "every surface reads as a surface to a backdrop frame")
-    return want
 
 
 @pytest.mark.parametrize("sampling", (1, 2))

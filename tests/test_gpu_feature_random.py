@@ -211,6 +211,7 @@ def check_layer_frame(vr, gpu, scene, f, salt, what, frame_index, in_place):
         import torch
         layer = torch.from_numpy(np.array(e.rgba)).cuda()
         dlayer = torch.from_numpy(np.array(e.depth)).cuda()
+        torch.cuda.synchronize()                        # (the uploads run on torch's stream, the frame on the context's)
         gpu.render_backdrop_device(f.p, layer.data_ptr(), dlayer.data_ptr(), layer.data_ptr(), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         assert diff(layer.cpu().numpy(), e.backdrop) == 0, (what, "backdrop in place", diff(layer.cpu().numpy(), e.backdrop))

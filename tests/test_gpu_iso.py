@@ -151,6 +151,7 @@ def test_entry_points_and_error_conventions(vr, gpu, golden, oracle, volumes, tf
     assert np.array_equal(gpu.render_iso(p, 100.0, REFINE), host)             # the same RGBA without a depth buffer
     buf = torch.full((72, 120, 4), 77, dtype=torch.uint8, device="cuda")
     dbuf = torch.full((72, 120), 123.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()                            # (the fills run on torch's stream, the frame on the context's)
     gpu.timing_reset()
     stream = torch.cuda.current_stream().cuda_stream
     for _ in range(3):
@@ -160,6 +161,7 @@ def test_entry_points_and_error_conventions(vr, gpu, golden, oracle, volumes, tf
     assert np.array_equal(buf.cpu().numpy(), host) and depth_diff(dbuf.cpu().numpy(), host_depth) == 0
     buf.fill_(77)
     dbuf.fill_(123.0)
+    torch.cuda.synchronize()                            # (the fills run on torch's stream, the frame on the context's)
     gpu.render_iso_device(p, 100.0, REFINE, buf.data_ptr(), None, stream)
     torch.cuda.synchronize()
     assert np.array_equal(buf.cpu().numpy(), host) and bool((dbuf == 123.0).all())

@@ -124,6 +124,7 @@ def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
     crop.x0, crop.out_width = 24, 40
     assert np.array_equal(gpu.render_volume(crop), want[:, 24:64])
     buf = torch.full((72, 120, 4), 77, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                            # (the fill runs on torch's stream, the frame on the context's)
     gpu.timing_reset()
     before = gpu.lighting_frames()
     gpu.render_volume_device(whole, buf.data_ptr(), torch.cuda.current_stream().cuda_stream)

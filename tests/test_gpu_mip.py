@@ -152,6 +152,7 @@ def test_entry_points_and_error_conventions(vr, gpu, golden, oracle, volumes, tf
     ref = expected(vr, oracle, vox, view, 1, tf)
     host = gpu.render_mip(p)
     buf = torch.full((72, 120, 4), 77, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                            # (the fill runs on torch's stream, the frame on the context's)
     gpu.timing_reset()
     for _ in range(3):
         gpu.render_mip_device(p, buf.data_ptr(), torch.cuda.current_stream().cuda_stream)

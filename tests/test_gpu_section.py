@@ -175,6 +175,7 @@ def test_bands_crop_and_device_entry_point(vr, gpu, golden, oracle, volumes):
         dbuf = torch.full((70, 120), 123.0, dtype=torch.float32, device="cuda")
         alone = torch.full((70, 120, 4), 78, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()                        # (the fills run on torch's stream, the frame on the context's)
         gpu.timing_reset()
         before = gpu.section_frames()
         gpu.render_section_device(whole, plane, hw, mode, window, buf.data_ptr(), dbuf.data_ptr(), stream)
@@ -228,13 +229,16 @@ def test_in_volume_equals_the_restatement(vr, gpu, golden, oracle, volumes, name
             want, want_depth, want_section = ref.in_volume(p, vox, tf, esl, plane, h, mode, window)
             two = torch.full(shape + (4,), 77, dtype=torch.uint8, device="cuda")
             two_depth = torch.full(shape, 123.0, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()                    # (the fills run on torch's stream, the frame on the context's)
             gpu.render_section_device(p, plane, h, mode, window, two.data_ptr(), two_depth.data_ptr(), stream)
             gpu.render_backdrop_device(p, two.data_ptr(), two_depth.data_ptr(), two.data_ptr(), stream)
             one = torch.full(shape + (4,), 78, dtype=torch.uint8, device="cuda")
             one_depth = torch.full(shape, 124.0, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()                    # (the fills run on torch's stream, the frame on the context's)
             before = gpu.backdrop_frames(), gpu.section_frames()
             gpu.render_section_in_volume_device(p, plane, h, mode, window, one.data_ptr(), one_depth.data_ptr(), stream)
             own = torch.full(shape + (4,), 79, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()                    # (the fill runs on torch's stream, the frame on the context's)
             gpu.render_section_in_volume_device(p, plane, h, mode, window, own.data_ptr(), None, stream)
             torch.cuda.synchronize()
             what = (name, label, sampling, full_march, section_label, mode)

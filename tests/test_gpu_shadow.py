@@ -180,6 +180,7 @@ def test_screen_partition_and_entry_points(vr, gpu, golden, oracle, volumes):
     assert np.array_equal(gpu.render_volume(crop), want[:, 24:64])
     # the device-pointer entry point on the caller's stream: one launch
     buf = torch.full((72, 120, 4), 77, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                            # (the fill runs on torch's stream, the frame on the context's)
     gpu.timing_reset()
     gpu.render_volume_device(whole, buf.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
