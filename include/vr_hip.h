@@ -601,6 +601,58 @@ int vr_hip_render_depth(vr_ctx *ctx, const vr_params *params, const vr_depth *de
 int vr_hip_pick(vr_ctx *ctx, const vr_params *params, const vr_depth *depth, uint32_t n, const uint32_t *xy /* 2n */, vr_pick *out);
 int vr_hip_depth_frames(vr_ctx *ctx, uint64_t *frames_out);            /* testing aid: depth frames launched (a pick counts one per query) */
 
+/* ---- label volumes: per-segment colour and visibility for composite frames.  No reference counterpart. ----
+ * A second volume of one byte per voxel names the segment a voxel belongs to; a table of 256 entries says what a segment does to the colour
+ * the transfer function returns for a sample inside it: tint it, replace it, fade it or hide it.  Two structures of the same density can
+ * then differ in colour, and a structure can be removed without a box or a plane.
+ *  1. State.  Labels are context state: dx * dy * dz bytes, x fastest, with the dims of the resident volume (other dims: VR_ERR_INVALID; no
+ *     volume: VR_ERR_NOT_READY).  The bytes are copied; the host entry is synchronous, the device entry copies on the context's stream.  NULL
+ *     drops them.  vr_hip_set_volume*, vr_hip_generate_volume drop them too: vr_hip_render_labelled* then returns VR_ERR_NOT_READY.  The
+ *     table survives until it is replaced: entries [0, count) as given, the rest — and all 256 after NULL / 0, and before the first call —
+ *     the identity { colour anything, mix 0, opacity 1 }.  Setting labels or a table changes no other frame of the context: every other entry
+ *     point ignores both.  Every existing struct keeps its size; the frames are counted by vr_hip_labelled_frames (testing aid).
+ *  2. Frame.  The composite frame vr_hip_render_device defines for a TRILINEAR or _Q8 frame under the context's clip (the identity clip when
+ *     none is set, always run), gradient lighting and shadow — leaping by params.esl, the cue, early termination, the band and crop
+ *     partition — with one insertion, directly behind the filtered lookup c of a sample at tb and in front of the `c.w > 0.05f` test.
+ *     (xb, yb, zb) = fma(k, A, B) are the sample's texel coordinates.
+ *  3. Nearest label.  ix = (uint32_t) fmed3(xb + 0.5f, 0.0f, (float) (Nx - 1)), the add one plain IEEE add; iy, iz likewise;
+ *     l = labels[(iz * Ny + iy) * Nx + ix].
+ *  4. Table.  e = table[l].  Per colour channel c.x = fmaf(e.mix, fmaf(e.colour[0], c.w, -c.x), c.x), with the unscaled c.w (c is
+ *     premultiplied, colour is straight); then all four channels are multiplied by e.opacity, plain products.
+ *  5. Everything behind the insertion sees this c: the dense test, the cue (with the sample's own raw and raw_l), lighting steps 1-5, the
+ *     shadow's factor, the accumulation and `acc.w > ray_threshold`.
+ *  6. Exact acceleration.  Both transparency shortcuts of the composite stay: c == 0 stays 0 under every entry.  The label of a sample the
+ *     wave skips need not be fetched.  A sample whose entry has opacity 0 contributes exactly nothing.
+ *  7. Consequences.  (a) With an all-identity table the bytes equal vr_hip_render of the same context state (fmaf(0, x, c) == c, c * 1 == c).
+ *     (b) With every opacity 0 the frame is all zero bytes.  (c) One constant label with { mix 0, opacity 0.5 } and no shadow: the bytes equal
+ *     the unlabelled frame rendered with every transfer-function entry halved — scaling by a power of two commutes with every rounding of
+ *     the lookup.
+ *  8. Shadow.  The light grid is built from the unlabelled classification: a hidden segment still casts its shadow.  Label-aware light rays
+ *     are a follow-up.
+ *  9. Pre-integration.  VR_ERR_INVALID while vr_hip_set_preintegration(1) holds: a slab between two samples with different labels has no
+ *     single entry.  A follow-up.
+ * 10. What it reads.  The field as a depth frame reads it — linear array, quad or oct bricks, never a run copy or a column window:
+ *     vr_launch_info::layout is 0, 1 or 5; vr_hip_set_layout and vr_hip_set_wide_addressing apply.  The labels are read from the linear
+ *     array, or — 1-byte voxels in quad bricks behind address tables — from a copy in the 1-byte voxel-brick order of chunk plane (x,y),
+ *     built on first use, which the field's own address tables address: such a frame reads the (x,y) quad copy whatever the view.  Tiles
+ *     start in grid order.  Frames are counted by vr_hip_timing and described by vr_hip_last_launch.
+ * 11. Errors.  VR_ERR_INVALID for VR_SAMPLE_NEAREST, for count > 256, for NULL entries with count > 0, for a table member that is not
+ *     finite or outside [0, 1], and while pre-integration is on.  Everything else as for vr_hip_render*.
+ * Out of scope: the device list (vr_hip_multi_*), a backdrop under a labelled frame, interpolated label boundaries, labels in MIP,
+ * isosurface, section and depth frames. */
+#define VR_LABEL_COUNT 256
+typedef struct vr_label_entry {
+	float colour[3];      /* 0..1, straight (not premultiplied) */
+	float mix;            /* 0..1: 0 keeps the transfer function's colour, 1 replaces it by `colour` */
+	float opacity;        /* 0..1: scales the sample; 0 hides the segment */
+} vr_label_entry;         /* 20 bytes */
+int vr_hip_set_labels(vr_ctx *ctx, const uint8_t *host_labels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z);    /* NULL = drop */
+int vr_hip_set_labels_device(vr_ctx *ctx, const void *dev_labels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z);
+int vr_hip_set_label_table(vr_ctx *ctx, const vr_label_entry *entries, uint32_t count);
+int vr_hip_render_labelled(vr_ctx *ctx, const vr_params *params, uint8_t *host_rgba);
+int vr_hip_render_labelled_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
+int vr_hip_labelled_frames(vr_ctx *ctx, uint64_t *frames_out);         /* testing aid: labelled frames launched */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

@@ -1,0 +1,181 @@
+"""CPU tier of the labelled composite frames (include/vr_hip.h vr_hip_render_labelled): label_render of tests/label_ref.c — the bytes the GPU
+tier expects — is tied to the composite restatements through the three consequences of the contract, the frames of the GPU tier's main test
+are shown to reach every kind of table entry and to tell four wrong readings of the contract apart, and the label kernels are held to 8
+waves per SIMD."""
+import ctypes as C
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+from clip_helpers import ClipRef
+from label_helpers import (KINDS, LABEL_VOLUMES, PERTURBATIONS, SHADINGS, LabelRef, constant_table, identity_table, labels_for, random_labels, structured_labels,
+                           table, tier_frames)
+from light_helpers import LightRef, lit_volumes
+from shadow_helpers import ShadowRef
+
+NEW_SYMBOLS = ("vr_hip_set_labels", "vr_hip_set_labels_device", "vr_hip_set_label_table", "vr_hip_render_labelled", "vr_hip_render_labelled_device",
+               "vr_hip_labelled_frames")
+
+
+@pytest.fixture(scope="module")
+def volumes(golden):
+    return lit_volumes(golden)
+
+
+def unlabelled(case, tf=None):
+    """the composite restatement of the case's frame without labels: light_render, shadow_render or clip_render — three entry points, the
+    independent composite text among them"""
+    tf = case.tf if tf is None else tf
+    if case.lighting is not None:
+        return LightRef.instance().render(case.p, case.vox, tf, case.esl, case.lighting, case.q, case.strength, clip=case.clip)
+    if case.q is not None:
+        return ShadowRef.instance().render(case.p, case.vox, tf, case.esl, case.q, case.strength, case.clip)
+    return ClipRef.instance().composite(case.p, case.vox, tf, case.esl, case.clip)
+
+
+def test_the_label_volumes_and_the_table():
+    """The structured volume carries five labels on every test shape and its stripes change along every axis; the random volume uses all
+    256; the table holds the five kinds, every member an exact float in [0, 1]"""
+    for shape in ((32, 32, 32), (56, 24, 40), (24, 24, 24), (7, 9, 11)):
+        lab = structured_labels(np.zeros(shape, np.uint8))
+        assert set(np.unique(lab)) == {0, 1, 2, 3, 4}, shape
+        assert (lab[1:] != lab[:-1]).any() and (lab[:, 1:] != lab[:, :-1]).any() and (lab[:, :, 1:] != lab[:, :, :-1]).any()
+    assert len(np.unique(random_labels(np.zeros((24, 24, 24), np.uint8)))) == 256
+    t = table()
+    assert t.shape == (256, 5) and (t >= 0).all() and (t <= 1).all() and np.array_equal(t * 64, np.round(t * 64))
+    assert (t[0::5, 3] == 0).all() and (t[0::5, 4] == 1).all() and (t[1::5, 4] == 0).all() and (t[2::5, 3] == 1).all() and (t[2::5, 4] == 1).all()
+    assert ((t[3::5, 3] > 0) & (t[3::5, 3] < 1)).all() and (t[3::5, 4] == 1).all() and ((t[4::5, 4] > 0) & (t[4::5, 4] < 1)).all()
+    assert (t[4::10, 3] > 0).all() and (t[9::10, 3] == 0).all()
+
+
+def test_every_pair_of_settings_meets(vr, golden, oracle, volumes):
+    """the 18 frames of a list: any two of shading, clip, mode and ray step meet in every combination"""
+    rows = [c.settings for c in tier_frames(vr, golden, oracle, volumes, "plateau", 1)]
+    assert len(rows) == 18 and {r[0] for r in rows} == set(range(len(SHADINGS)))
+    for a, b in itertools.combinations(range(4), 2):
+        assert len({(r[a], r[b]) for r in rows}) == len({r[a] for r in rows}) * len({r[b] for r in rows}), (a, b)
+
+
+@pytest.mark.parametrize("name", LABEL_VOLUMES)
+def test_consequences(vr, golden, oracle, volumes, name):
+    """On every frame of the list.  (a) an all-identity table: the bytes of the unlabelled composite restatement (clip_render, light_render or
+    shadow_render).  (b) every opacity 0: all zero bytes.  (c) one constant label with { mix 0, opacity 0.5 } — every other entry hidden — and no
+    shadow: the bytes of the unlabelled frame under the halved transfer function."""
+    ref = LabelRef.instance()
+    frames = nonzero = halved = 0
+    hidden = constant_table(0.75, 0.0, (0.5, 0.25, 1.0))
+    half = hidden.copy()
+    half[7] = (0.0, 0.0, 0.0, 0.0, 0.5)
+    for sampling in (1, 2):
+        for case in tier_frames(vr, golden, oracle, volumes, name, sampling):
+            labels = labels_for(name, case.vox)
+            plain = unlabelled(case)
+            got = ref.render(case.p, case.vox, case.tf, case.esl, labels, identity_table(), case.lighting, case.q, case.strength, case.clip)
+            assert np.array_equal(got.frame, plain), (case.what, "a", int((got.frame != plain).any(axis=-1).sum()))
+            zero = ref.render(case.p, case.vox, case.tf, case.esl, labels, hidden, case.lighting, case.q, case.strength, case.clip)
+            assert not zero.frame.any() and zero.count.sum() >= got.count.sum() > 0, (case.what, "b")      # (no ray terminates early: none accumulates)
+            frames, nonzero = frames + 1, nonzero + int(plain[..., 3].astype(bool).sum())
+            if case.q is None:
+                sevens = np.full(case.vox.shape, 7, np.uint8)
+                want = unlabelled(case, np.asarray(case.tf, np.float32) * np.float32(0.5))
+                faded = ref.render(case.p, case.vox, case.tf, case.esl, sevens, half, case.lighting, None, 1.0, case.clip)
+                assert np.array_equal(faded.frame, want), (case.what, "c", int((faded.frame != want).any(axis=-1).sum()))
+                halved += int(want[..., 3].astype(bool).sum())
+    assert frames == 36 and nonzero > 36 * 300 and halved > 16 * 300, (frames, nonzero, halved)
+
+
+@pytest.mark.parametrize("name", LABEL_VOLUMES)
+def test_the_main_tests_frames_reach_every_entry_kind_and_tell_wrong_readings_apart(vr, golden, oracle, volumes, name):
+    """The list tier_frames gives tests/test_gpu_label.py, on the restatement alone, with the volume's labels and the table of label_helpers.
+    Each of the five kinds of entry — identity, hidden, mix 1, fractional mix, fractional opacity — receives samples with a non-zero
+    looked-up alpha (the shares are printed); the labelled frames differ from the unlabelled ones; and each wrong reading — the index
+    without the + 0.5f, the entry applied behind the dense test and the shading, opacity on alpha only, mix towards colour times the scaled
+    alpha — changes bytes over the list."""
+    ref = LabelRef.instance()
+    entries = table()
+    kinds = np.zeros(5, np.int64)
+    changed = dict.fromkeys(PERTURBATIONS, 0)
+    differs = frames = 0
+    for sampling in (1, 2):
+        for case in tier_frames(vr, golden, oracle, volumes, name, sampling):
+            labels = labels_for(name, case.vox)
+            got = ref.render(case.p, case.vox, case.tf, case.esl, labels, entries, case.lighting, case.q, case.strength, case.clip)
+            kinds += got.by_kind()
+            differs += int((got.frame != unlabelled(case)).any(axis=-1).sum())
+            frames += 1
+            for perturb in PERTURBATIONS:
+                wrong = ref.render(case.p, case.vox, case.tf, case.esl, labels, entries, case.lighting, case.q, case.strength, case.clip, perturb=perturb)
+                changed[perturb] += int((wrong.frame != got.frame).any(axis=-1).sum())
+    print(f"{name}: {frames} frames; samples with alpha by entry kind: " + ", ".join(f"{k} {n / kinds.sum():.3f}" for k, n in zip(KINDS, kinds)) +
+          f"; pixels that differ from the unlabelled frames {differs}; pixels changed by the wrong readings {changed}")
+    assert frames == 36 and (kinds > 0).all() and (20 * kinds >= kinds.sum() // 5).all(), kinds
+    assert differs > 36 * 100 and all(n > 0 for n in changed.values()), (differs, changed)
+
+
+def _kernels(text, pattern):
+    out = {}
+    for m in re.finditer(r"Function Name: (\S*?" + pattern + r"\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+                         r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", text, flags=re.S):
+        out[m.group(1)] = tuple(int(g) for g in m.groups()[1:])
+    return out
+
+
+ROWS = r"ILi(\d)ELi(\d)ELi(\d)ELi(\d)E"
+
+
+def test_label_kernels_keep_eight_waves(vr):
+    """The eighth log, resource_usage_label.log: its names appear once each and in no other log — label_kernel over the 24 rows of the
+    isosurface (lit or unlit is a wave-uniform argument: one family).  No scratch, no SGPR or VGPR spilled, <= 80 SGPRs and <= 64 VGPRs, 8
+    waves per SIMD on every row.  The seven older logs keep their 269 / 36 / 24 / 48 / 96 / 24 / 25 names."""
+    import subprocess
+    from test_abi import ROOT
+    csrc = os.path.join(ROOT, "volume-rendering_amd", "csrc")
+    logs = [os.path.join(csrc, n) for n in ("resource_usage.log", "resource_usage_shadow.log", "resource_usage_light.log", "resource_usage_slab.log",
+                                            "resource_usage_backdrop.log", "resource_usage_section.log", "resource_usage_depth.log", "resource_usage_label.log")]
+    if not all(os.path.exists(p) for p in logs):
+        subprocess.check_call(["make", "-B", "-C", csrc])
+    texts = [open(p).read() for p in logs]
+    names = [re.findall(r"Function Name: (\S+)", t) for t in texts]
+    assert [len(n) for n in names[:7]] == [269, 36, 24, 48, 96, 24, 25], [len(n) for n in names]
+    assert len(names[7]) == 24 and len(set(sum(names, []))) == 269 + 36 + 24 + 48 + 96 + 24 + 25 + 24
+    assert all("label_kernel" in n for n in names[7]) and not [n for n in sum(names[:7], []) if "label_kernel" in n]
+    key = lambda name: tuple(int(g) for g in re.search(ROWS, name).groups())      # noqa: E731
+    mine = {key(n): v for n, v in _kernels(texts[7], r"\d+label_kernel" + ROWS.replace("(", "(?:")).items()}
+    depth_rows = {key(n) for n in names[6] if re.search(r"\d+depth_kernel" + ROWS, n)}
+    assert len(mine) == 24 and set(mine) == depth_rows
+    for row, (sgprs, vgprs, scratch, occupancy, sspill, vspill) in mine.items():
+        assert scratch == 0 and sspill == 0 and vspill == 0, (row, scratch, sspill, vspill)
+        assert sgprs <= 80 and vgprs <= 64 and occupancy == 8, (row, sgprs, vgprs, occupancy)
+
+
+def test_binding_and_header(vr):
+    """vr_label_entry is 20 bytes (colour, mix, opacity at 0 / 12 / 16); vr_params keeps its 132 bytes, VrLaunchInfo its 13 members and 52
+    bytes, VrVolumeInfo its 128 bytes; the six entry points are declared in include/vr_hip.h, exported and resolved by the binding; without
+    a context they return VR_ERR_INVALID; the renderer has the methods, the device list does not."""
+    from test_abi import ROOT
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vr_hip.h")).read(), flags=re.S)
+    L = vr.lib()
+    raw = C.CDLL(vr.library_path())
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint\s+" + name + r"\(", text), name
+        assert hasattr(L, name) and hasattr(raw, name), name
+    assert re.search(r"typedef struct vr_label_entry \{\s*float\s+colour\[3\];\s*float\s+mix;\s*float\s+opacity;\s*\} vr_label_entry;", text)
+    assert re.search(r"#define VR_LABEL_COUNT 256", text) and vr.binding.LABEL_COUNT == 256
+    E = vr.VrLabelEntry
+    assert C.sizeof(E) == 20 and (E.colour.offset, E.mix.offset, E.opacity.offset) == (0, 12, 16)
+    assert C.sizeof(vr.VrParams) == 132 and len(vr.VrLaunchInfo._fields_) == 13 and C.sizeof(vr.VrLaunchInfo) == 52 and C.sizeof(vr.binding.VrVolumeInfo) == 128
+    e = vr.binding.make_label_entry()
+    assert (tuple(e.colour), e.mix, e.opacity) == ((0.0, 0.0, 0.0), 0.0, 1.0)
+    p, count = vr.VrParams(), C.c_uint64(0)
+    buf = (C.c_uint8 * 64)()
+    entries = (E * 1)()
+    assert L.vr_hip_set_labels(None, buf, 4, 4, 4) == 1 and L.vr_hip_set_labels_device(None, buf, 4, 4, 4) == 1
+    assert L.vr_hip_set_label_table(None, entries, 1) == 1
+    assert L.vr_hip_render_labelled(None, C.byref(p), buf) == 1 and L.vr_hip_render_labelled_device(None, C.byref(p), buf, None) == 1
+    assert L.vr_hip_labelled_frames(None, C.byref(count)) == 1
+    for method in ("set_labels", "set_label_table", "clear_labels", "render_labelled", "render_labelled_device", "labelled_frames"):
+        assert callable(getattr(vr.HipRenderer, method)), method
+        assert not hasattr(vr.MultiRenderer, method), method       # single device: the device list stays without them

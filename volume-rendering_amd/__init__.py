@@ -10,7 +10,7 @@ The directory name contains a hyphen, so import it with
 ``importlib.import_module("volume-rendering_amd")`` (``__graft_entry__.load_package()`` does that).
 """
 from .binding import (  # noqa: F401
-    VrError, VrParams, VrView, VrTiming, VrIso, VrClip, VrShadow, VrLighting, VrBackdrop, VrSection, VrDepth, VrDepthOut, VrPick, VrLaunchInfo, lib, library_path,
+    VrError, VrParams, VrView, VrTiming, VrIso, VrClip, VrShadow, VrLighting, VrBackdrop, VrSection, VrDepth, VrDepthOut, VrPick, VrLabelEntry, VrLaunchInfo, lib, library_path,
     SAMPLE_NEAREST, SAMPLE_TRILINEAR, SAMPLE_TRILINEAR_Q8, TF_SIZE, ESL_VOLUME_SIZE, LAYOUT_LINEAR, LAYOUT_BRICKED,
     COPY_QUAD_XY, COPY_QUAD_XZ, COPY_QUAD_YZ, COPY_RUN_Z, COPY_RUN_Y, COPY_VOXEL, COPY_OCT, COPY_COL_X, COPY_COL_Y, COPY_COL_Z, COPY_COLV_X, COPY_COLV_Y, COPY_COLV_Z, COPY_ALL, COPY_NAMES, COPY_KINDS,
 )
@@ -18,7 +18,7 @@ from .scene import Scene, benchmark_view, custom_view, whole_frame, band_partiti
 from .renderer import HipRenderer, MultiRenderer  # noqa: F401
 
 __all__ = [
-    "VrError", "VrParams", "VrView", "VrTiming", "VrIso", "VrClip", "VrShadow", "VrLighting", "VrBackdrop", "VrSection", "VrDepth", "VrDepthOut", "VrPick", "VrLaunchInfo", "lib", "library_path", "SAMPLE_NEAREST", "SAMPLE_TRILINEAR", "SAMPLE_TRILINEAR_Q8",
+    "VrError", "VrParams", "VrView", "VrTiming", "VrIso", "VrClip", "VrShadow", "VrLighting", "VrBackdrop", "VrSection", "VrDepth", "VrDepthOut", "VrPick", "VrLabelEntry", "VrLaunchInfo", "lib", "library_path", "SAMPLE_NEAREST", "SAMPLE_TRILINEAR", "SAMPLE_TRILINEAR_Q8",
     "TF_SIZE", "ESL_VOLUME_SIZE", "LAYOUT_LINEAR", "LAYOUT_BRICKED", "COPY_QUAD_XY", "COPY_QUAD_XZ", "COPY_QUAD_YZ", "COPY_RUN_Z", "COPY_RUN_Y",
     "COPY_VOXEL", "COPY_OCT", "COPY_COL_X", "COPY_COL_Y", "COPY_COL_Z", "COPY_COLV_X", "COPY_COLV_Y", "COPY_COLV_Z", "COPY_ALL", "COPY_NAMES", "COPY_KINDS", "Scene", "benchmark_view", "custom_view", "whole_frame", "band_partition", "HipRenderer", "MultiRenderer",
 ]

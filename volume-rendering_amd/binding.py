@@ -149,6 +149,24 @@ def make_depth(opacity, mode="first"):
     return d
 
 
+LABEL_COUNT = 256
+
+
+class VrLabelEntry(C.Structure):
+    """vr_label_entry: what a segment does to a sample's classified colour — the straight colour (0..1), how far it replaces the transfer
+    function's (mix 0 keeps it, 1 replaces it) and the factor on the sample (opacity 0 hides the segment)"""
+    _fields_ = [("colour", C.c_float * 3), ("mix", C.c_float), ("opacity", C.c_float)]
+
+
+def make_label_entry(colour=(0.0, 0.0, 0.0), mix=0.0, opacity=1.0):
+    """A VrLabelEntry; the defaults are the identity entry."""
+    e = VrLabelEntry()
+    for i in range(3):
+        e.colour[i] = float(colour[i])
+    e.mix, e.opacity = float(mix), float(opacity)
+    return e
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -238,6 +256,12 @@ def lib():
         "vr_hip_render_depth_device": (C.c_int, [vp, P(VrParams), P(VrDepth), P(VrDepthOut), vp]),
         "vr_hip_pick": (C.c_int, [vp, P(VrParams), P(VrDepth), u32, P(u32), P(VrPick)]),
         "vr_hip_depth_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_set_labels": (C.c_int, [vp, vp, u32, u32, u32]),
+        "vr_hip_set_labels_device": (C.c_int, [vp, vp, u32, u32, u32]),
+        "vr_hip_set_label_table": (C.c_int, [vp, P(VrLabelEntry), u32]),
+        "vr_hip_render_labelled": (C.c_int, [vp, P(VrParams), vp]),
+        "vr_hip_render_labelled_device": (C.c_int, [vp, P(VrParams), vp, vp]),
+        "vr_hip_labelled_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

@@ -32,14 +32,14 @@ void HipRenderer::to_params(const Raycaster &r, vr_sampling sampling, vr_params 
 }
 
 HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, labelled_(false), mirror_error_(nullptr) {
 	create_status_ = vr_hip_create(device, &ctx_);
 	if (create_status_ == 0)
 		prime(r);
 }
 
 HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, mirror_error_(nullptr) {
+	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, labelled_(false), mirror_error_(nullptr) {
 	create_status_ = vr_hip_multi_create(n_devices, devices, &multi_);
 	if (create_status_ == 0)
 		prime(r);
@@ -147,7 +147,12 @@ int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
 		mirror_error_ = "a section frame renders on a single device (vr_hip_render_section): construct the renderer without a device list";
 		return 1;
 	}
-	if (section_ && section_in_volume_) rc = device_buffer_ ? vr_hip_render_section_in_volume_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section_in_volume(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
+	if (labelled_ && multi_) {
+		mirror_error_ = "a labelled frame renders on a single device (vr_hip_render_labelled): construct the renderer without a device list";
+		return 1;
+	}
+	if (labelled_) rc = device_buffer_ ? vr_hip_render_labelled_device(ctx_, &p, buffer, nullptr) : vr_hip_render_labelled(ctx_, &p, (uint8_t *) buffer);
+	else if (section_ && section_in_volume_) rc = device_buffer_ ? vr_hip_render_section_in_volume_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section_in_volume(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
 	else if (section_) rc = device_buffer_ ? vr_hip_render_section_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
 	else if (hybrid_) rc = device_buffer_ ? vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_hybrid(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
 	else if (iso_) rc = device_buffer_ ? vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_iso(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
@@ -169,6 +174,28 @@ int HipRenderer::render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop 
 	to_params(r, sampling_, &p);
 	const int rc = device_buffer_ ? vr_hip_render_backdrop_device(ctx_, &p, layer, buffer, nullptr) : vr_hip_render_backdrop(ctx_, &p, layer, (uint8_t *) buffer);
 	return rc == 0 ? 0 : 1;
+}
+
+int HipRenderer::set_labels(const uint8_t *labels, const uint32_t dims[3]) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	if (multi_) {
+		mirror_error_ = "label volumes belong to a single device (vr_hip_set_labels): construct the renderer without a device list";
+		return 1;
+	}
+	return vr_hip_set_labels(ctx_, labels, dims ? dims[0] : 0u, dims ? dims[1] : 0u, dims ? dims[2] : 0u) == 0 ? 0 : 1;
+}
+
+int HipRenderer::set_label_table(const vr_label_entry *entries, uint32_t count) {
+	if (!ok())
+		return 1;
+	mirror_error_ = nullptr;
+	if (multi_) {
+		mirror_error_ = "label tables belong to a single device (vr_hip_set_label_table): construct the renderer without a device list";
+		return 1;
+	}
+	return vr_hip_set_label_table(ctx_, entries, count) == 0 ? 0 : 1;
 }
 
 int HipRenderer::render_depth(Raycaster r, const vr_depth &depth, const vr_depth_out *out) {

@@ -88,22 +88,22 @@ class HipRenderer : public Renderer {
 		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
 		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
 		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
-		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = section_ = false; }
+		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = section_ = labelled_ = false; }
 		// on: render_volume() produces the shaded isosurface at `level` (raw voxel units) with `refine` bisection steps (vr_hip_render_iso;
 		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
-		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = section_ = false; }
+		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = section_ = labelled_ = false; }
 		// on: render_volume() produces the hybrid (vr_hip_render_hybrid): that isosurface seen through the translucent volume in front of it —
 		// the isosurface frame, then the composite frame stopped at its depth and blended over it; the composite pass sees the clip, the
 		// shadow, the lighting and the pre-integration of this renderer.  Needs a TRILINEAR sampling mode.  Excludes set_mip and set_iso:
 		// the one set last holds.  Single device only, like them.
-		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = section_ = false; }
+		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = section_ = labelled_ = false; }
 		// on: render_volume() produces the section frame (vr_hip_render_section): the oblique slice `section` through the interpolated field, or
 		// its thick-slab maximum, minimum or mean, coloured by the transfer function or the section's grey window; in_volume: that section seen
 		// through the translucent volume in front of it (vr_hip_render_section_in_volume: the composite pass sees the clip, the shadow, the
 		// lighting and the pre-integration of this renderer).  No depth comes back through this interface.  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip, set_iso and set_hybrid: the one set last holds.  Single device only, like them.
-		void set_section(bool on, const vr_section &section, bool in_volume) { section_ = on; section_in_volume_ = in_volume; section_params_ = section; if (on) mip_ = iso_ = hybrid_ = false; }
+		void set_section(bool on, const vr_section &section, bool in_volume) { section_ = on; section_in_volume_ = in_volume; section_params_ = section; if (on) mip_ = iso_ = hybrid_ = labelled_ = false; }
 		// One composite frame over an opaque layer (vr_hip_render_backdrop / vr_hip_render_backdrop_device by the buffer flavour of this
 		// renderer): `layer` holds host or device pointers accordingly, view.dims pixels each.  Whatever set_mip / set_iso / set_hybrid say,
 		// this is a composite frame.  Single device only.  0 = ok, 1 = failure.
@@ -115,6 +115,14 @@ class HipRenderer : public Renderer {
 		// What that depth frame stores at each of the n pixels xy[2i], xy[2i + 1] (y up), with the position and the voxel index of a hit
 		// (vr_hip_pick: host arrays, synchronous, at most 256 pixels).  Single device only.  0 = ok, 1 = failure.
 		int pick(Raycaster r, const vr_depth &depth, uint32_t n, const uint32_t *xy, vr_pick *out);
+		// Label volumes (vr_hip_set_labels, vr_hip_set_label_table, vr_hip_render_labelled*): one byte per voxel with the dims of the resident
+		// volume (NULL drops them; a new volume drops them too), and what each of the 256 labels does to a sample's classified colour (entries
+		// beyond `count`, and all of them for NULL / 0, are the identity).  set_labelled(true): render_volume() produces the labelled composite
+		// frame — the clip, the shadow and the lighting of this renderer apply; it needs a TRILINEAR sampling mode and excludes the
+		// pre-integration, set_mip, set_iso, set_hybrid and set_section: the one set last holds.  Single device only.  0 = ok, 1 = failure.
+		int set_labels(const uint8_t *labels, const uint32_t dims[3]);
+		int set_label_table(const vr_label_entry *entries, uint32_t count);
+		void set_labelled(bool on) { labelled_ = on; if (on) mip_ = iso_ = hybrid_ = section_ = false; }
 		// The clip region of every later frame of this renderer — composite, set_mip and set_iso alike, and with a device list every device's
 		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
 		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.
@@ -149,6 +157,7 @@ class HipRenderer : public Renderer {
 		bool section_;
 		bool section_in_volume_;
 		vr_section section_params_;
+		bool labelled_;
 		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
 };
 

@@ -7,7 +7,8 @@
 //              [-clip-box <x0> <y0> <z0> <x1> <y1> <z1>] [-clip-plane <nx> <ny> <nz> <d>] [-shadow <S> [-shadow-strength <s>] [-shadow-step <t>]]
 //              [-phong <ka> <kd> <ks> <n>] [-preint] [-hybrid <level> [-refine <n>]]
 //              [-section <nx> <ny> <nz> <d> [-section-half <h>] [-section-mode max|min|mean] [-section-window <lo> <hi>] [-section-in-volume]]
-//              [-depth <opacity> [-depth-mode first|peak|mean] [-pick <x> <y>]] [-o <frame.ppm>]
+//              [-depth <opacity> [-depth-mode first|peak|mean] [-pick <x> <y>]] [-labels <file.raw> | -labels-octants] [-label <id> <r> <g> <b> <mix> <opacity>]...
+//              [-o <frame.ppm>]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -61,6 +62,11 @@ void print_usage() {
 	       "         or mean over the slab of that half width; -section-window: opaque grey between lo and hi (raw voxel units) instead of the transfer\n"
 	       "         function; -section-in-volume: the section seen through the translucent volume in front of it (the composite pass sees the clip,\n"
 	       "         -shadow, -phong and -preint); from the trilinear renderer (-r 1); single device; excludes -mip, -iso, -hybrid and -devices\n"
+	       "  -labels <file.raw> | -labels-octants, -label <id> <r> <g> <b> <mix> <opacity> (repeatable) : the labelled composite frame: a second volume\n"
+	       "         of one byte per voxel (a raw file of the volume's dims, x fastest, or the voxel's octant 0..7) names each voxel's segment, and the\n"
+	       "         table entry of a label tints (mix), replaces (mix 1), fades (opacity) or hides (opacity 0) what the transfer function returns\n"
+	       "         there; labels without an entry stay as they are; from the trilinear renderer (-r 1); single device; works with the clip, -shadow\n"
+	       "         and -phong; excludes -mip, -iso, -hybrid, -section, -depth, -preint and -devices\n"
 	       "  -depth <opacity> [-depth-mode first|peak|mean] [-pick <x> <y>] : the depth frame of the composite instead of its colours: where along\n"
 	       "         its ray the thing a pixel shows lies — the first sample at which the accumulated alpha reaches <opacity> (default), the sample\n"
 	       "         that contributes most, or the contribution-weighted mean; -o writes the depth of the hits as a normalised grey image (near =\n"
@@ -312,6 +318,10 @@ int main(int argc, char **argv) {
 	bool depth_on = false, depth_mode_given = false, pick_on = false;
 	vr_depth depth_params = { 0.5f, VR_DEPTH_FIRST };
 	uint32_t pick_xy[2] = { 0u, 0u };
+	std::string labels_file;
+	bool labels_octants = false;
+	uint32_t label_entries = 0;                 // entries of the table given so far: the highest -label id + 1
+	std::vector<vr_label_entry> label_table(VR_LABEL_COUNT, vr_label_entry{ { 0.0f, 0.0f, 0.0f }, 0.0f, 1.0f });
 	bool section_on = false, section_in_volume = false, section_mode_given = false, section_window_given = false;
 	vr_section section = { { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f, VR_SECTION_POINT, { 0.0f, 0.0f } };
 	bool clip_box = false, clip_plane = false;
@@ -384,6 +394,18 @@ int main(int argc, char **argv) {
 			}
 		}
 		else if (strcmp(arg, "-pick") == 0) { if (need(2)) { pick_xy[0] = (uint32_t) atoi(argv[++i]); pick_xy[1] = (uint32_t) atoi(argv[++i]); pick_on = true; } }
+		else if (strcmp(arg, "-labels") == 0) { if (need(1)) labels_file = argv[++i]; }
+		else if (strcmp(arg, "-labels-octants") == 0) labels_octants = true;
+		else if (strcmp(arg, "-label") == 0) {
+			if (!need(6)) continue;
+			const int id = atoi(argv[++i]);
+			vr_label_entry e;
+			for (int k = 0; k < 3; k++) e.colour[k] = (float) atof(argv[++i]);
+			e.mix = (float) atof(argv[++i]); e.opacity = (float) atof(argv[++i]);
+			if (id < 0 || id >= VR_LABEL_COUNT) { printf("Error: -label takes an id in 0..255\n"); return EXIT_FAILURE; }
+			label_table[(size_t) id] = e;
+			if ((uint32_t) id + 1u > label_entries) label_entries = (uint32_t) id + 1u;
+		}
 		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
 		else if (strcmp(arg, "-clip-box") == 0) {
 			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
@@ -470,6 +492,35 @@ int main(int argc, char **argv) {
 		printf("Error: -depth-mode and -pick need -depth\n"); return EXIT_FAILURE;
 	}
 
+	const bool labels_on = labels_octants || !labels_file.empty();
+	if (labels_on) {
+		if (!device_list.empty()) { printf("Error: -labels renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
+		if (mip || iso || hybrid || section_on || depth_on) { printf("Error: -labels excludes -mip, -iso, -hybrid, -section and -depth\n"); return EXIT_FAILURE; }
+		if (renderer_id != 1) { printf("Error: -labels needs the trilinear renderer (-r 1): a labelled frame is defined on the interpolated field\n"); return EXIT_FAILURE; }
+		if (preint) { printf("Error: -labels excludes -preint: a slab between two labels has no single table entry\n"); return EXIT_FAILURE; }
+		if (labels_octants && !labels_file.empty()) { printf("Error: -labels and -labels-octants exclude each other\n"); return EXIT_FAILURE; }
+		if (!loaded) { printf("Error: -labels needs a volume\n"); return EXIT_FAILURE; }
+		const uint32_t dims[3] = { ModelBase::volume.dims.x, ModelBase::volume.dims.y, ModelBase::volume.dims.z };
+		const size_t voxels = (size_t) dims[0] * dims[1] * dims[2];
+		std::vector<uint8_t> labels(voxels);
+		if (labels_octants) {                   // the label of a voxel is its octant: bit 0 the upper half in x, bit 1 in y, bit 2 in z
+			for (uint32_t z = 0; z < dims[2]; z++) for (uint32_t y = 0; y < dims[1]; y++) for (uint32_t x = 0; x < dims[0]; x++)
+				labels[((size_t) z * dims[1] + y) * dims[0] + x] = (uint8_t) ((x >= dims[0] / 2u ? 1u : 0u) | (y >= dims[1] / 2u ? 2u : 0u) | (z >= dims[2] / 2u ? 4u : 0u));
+		} else {
+			FILE *f = fopen(labels_file.c_str(), "rb");
+			const size_t got = f ? fread(labels.data(), 1, voxels, f) : 0;
+			const bool more = f && fgetc(f) != EOF;
+			if (f) fclose(f);
+			if (got != voxels || more) { printf("Error: -labels %s does not hold the %zu bytes of the volume's dims\n", labels_file.c_str(), voxels); return EXIT_FAILURE; }
+		}
+		if (renderers[1]->set_labels(labels.data(), dims) != 0 || renderers[1]->set_label_table(label_table.data(), label_entries) != 0) {
+			printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE;
+		}
+		renderers[1]->set_labelled(true);
+		printf("Labels: %s, %u table entr%s\n", labels_octants ? "octants" : labels_file.c_str(), label_entries, label_entries == 1u ? "y" : "ies");
+	} else if (label_entries != 0u) {
+		printf("Error: -label entries need -labels or -labels-octants\n"); return EXIT_FAILURE;
+	}
 	if (clip_box || clip_plane) {
 		for (int i = 0; i < PROFILER_RENDERERS; i++)
 			if (renderers[i]->set_clip(&clip) != 0) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }

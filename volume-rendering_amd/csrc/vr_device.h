@@ -417,6 +417,22 @@ hipError_t launch_depth(const RayKernelArgs &a, const DepthArgs &depth, const vo
 hipError_t launch_pick_finish(const RayKernelArgs &a, uint32_t n, const uint32_t *xy, const float *depth, const float *value, const float *alpha,
                               vr_pick *out, hipStream_t stream);
 
+// ---- labelled composite frames (include/vr_hip.h vr_hip_render_labelled) ----
+// The labels of one frame, a kernel argument of its own behind the ones a composite frame takes.
+struct LabelArgs {
+	uint64_t labels;                   // the label array the frame reads: one byte per voxel
+	uint32_t bricked;                  // 1: `labels` is in the 1-byte voxel-brick order of chunk plane (x,y) (launch_brickify_voxel) and the frame
+	                                   // reads the (x,y) quad copy of 1-byte voxels behind address tables, whose entries address it too; 0: linear
+	uint32_t reserved;
+};
+// One labelled frame.  `a`, `linear` and `bricked` as for launch_depth (the same rows), the clip words of `a` filled, the lighting and shadow
+// words as launch_raymarch takes them (a.light_on, a.shadow_on: wave-uniform arguments of the one family); a.p.esl, a.esl_div_*,
+// a.skip_mask / skip_cmp / tf_zero_below likewise.  labels_linear: the label array in the volume's linear order (+ its tail slack);
+// labels_xy_bricks: its 1-byte voxel-brick copy, or NULL — read instead where the row the frame runs addresses the (x,y) quad copy of 1-byte
+// voxels through tables (the launcher decides: the selector is its own).  table: VR_LABEL_COUNT entries of 5 floats (vr_label_entry) on the device.
+hipError_t launch_labelled(const RayKernelArgs &a, const void *labels_linear, const void *labels_xy_bricks, const void *linear, const void *bricked,
+                           uint32_t bytes_per_voxel, const float *tf_premult, const uint32_t *esl_bits, const float *table, void *out_rgba, hipStream_t stream);
+
 // ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
 // What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
 struct ShadowBuildArgs {

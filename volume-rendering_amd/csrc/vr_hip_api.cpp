@@ -128,6 +128,13 @@ struct vr_ctx {
 	uint64_t depth_frames = 0;
 	void *depth_stage = nullptr; size_t depth_stage_bytes = 0;
 	void *pick_stage = nullptr; size_t pick_stage_bytes = 0;
+	// label volumes (vr_hip_set_labels, vr_hip_set_label_table, vr_hip_render_labelled*): one byte per voxel of the resident volume in the
+	// linear order (+ the volume's zeroed tail slack), dropped with the volume; its copy in the 1-byte voxel-brick order of chunk plane (x,y),
+	// built by the first frame that reads it (label_bricks_failed: refused, not retried until the labels change); the table, VR_LABEL_COUNT
+	// entries of 5 floats on the device, identity until set; the frames launched on the label kernels
+	uint8_t *labels = nullptr, *label_bricks = nullptr; bool label_bricks_failed = false;
+	float *label_table = nullptr;
+	uint64_t labelled_frames = 0;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -1094,6 +1101,13 @@ const void *copy_for(vr_ctx *c, uint32_t kind) {
 	return c->copy[kind];
 }
 
+// the labels belong to one volume (and one set of dims): nothing of them may be in flight here
+void drop_labels(vr_ctx *c) {
+	if (c->labels) { (void) hipFree(c->labels); c->labels = nullptr; }
+	if (c->label_bricks) { (void) hipFree(c->label_bricks); c->label_bricks = nullptr; }
+	c->label_bricks_failed = false;
+}
+
 int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	if (x == 0 || y == 0 || z == 0 || x > 65535u || y > 65535u || z > 65535u)       // Model::dims is ushort3
 		return fail(c, VR_ERR_INVALID, "volume dims out of range (1..65535)");
@@ -1101,6 +1115,7 @@ int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	VR_TRY(c, drain(c));                         // frames still reading the volume we are about to free
 	if (c->vol) { (void) hipFree(c->vol); c->vol = nullptr; }
 	free_bricks(c);
+	drop_labels(c);                              // vr_hip_set_labels: the labels go with the volume they were set for
 	forget_tile_mappings(c);                     // cached tile mappings belong to the previous volume
 	c->mip_mapped = 0; c->mip_map_next = 0; c->mip_bounds_ready = false;       // ... and so do the block maxima of the MIP frames
 	c->shadow_ready = false;                     // ... and the light grid of a shadow
@@ -1407,6 +1422,75 @@ int launch_depth_frame(vr_ctx *c, const vr_params *p, const vr_depth *d, const v
 	return rc;
 }
 
+// the label table on the device: allocated on first use, the identity until vr_hip_set_label_table replaces it
+int ensure_label_table(vr_ctx *c) {
+	if (c->label_table != nullptr) return VR_OK;
+	std::vector<float> identity(5u * VR_LABEL_COUNT, 0.0f);
+	for (uint32_t i = 0; i < VR_LABEL_COUNT; i++) identity[5u * i + 4u] = 1.0f;
+	VR_TRY(c, hipMalloc((void **) &c->label_table, identity.size() * sizeof(float)));
+	VR_TRY(c, hipMemcpy(c->label_table, identity.data(), identity.size() * sizeof(float), hipMemcpyHostToDevice));
+	return VR_OK;
+}
+
+// the labels in the 1-byte voxel-brick order (launch_brickify_voxel: the builder of the NEAREST copy, on the label array), on the context's
+// stream and synchronous like a brick copy's first use; NULL where it cannot be had — the frame then reads the linear labels
+const uint8_t *label_bricks_for(vr_ctx *c) {
+	if (c->label_bricks != nullptr || c->label_bricks_failed) return c->label_bricks;
+	uint8_t *dst = nullptr;
+	const uint64_t bytes = bricked_elems(c->dim[0], c->dim[1], c->dim[2]);
+	hipError_t e = hipMalloc((void **) &dst, bytes);
+	if (e == hipSuccess) e = launch_brickify_voxel(c->labels, dst, 1u, c->dim[0], c->dim[1], c->dim[2], c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) { (void) hipGetLastError(); if (dst) (void) hipFree(dst); c->label_bricks_failed = true; return nullptr; }
+	c->label_bricks = dst;
+	return dst;
+}
+
+// what the two labelled entry points check beyond render_preamble (include/vr_hip.h, step 11 of the label contract)
+int validate_labelled(vr_ctx *c, const vr_params *p) {
+	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
+		return fail(c, VR_ERR_INVALID, "a labelled frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (c->preint_on)
+		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab between two samples with different labels has no single table entry "
+		                               "(vr_hip_set_preintegration(ctx, 0) switches it off)");
+	if (c->labels == nullptr) return fail(c, VR_ERR_NOT_READY, "no labels are set for the resident volume (vr_hip_set_labels)");
+	return VR_OK;
+}
+
+// One labelled frame (include/vr_hip.h vr_hip_render_labelled): what a depth frame of the same view and sampling reads and maps — through
+// launch_full_march_frame with esl off —, then the composite's leaping, its transparent-sample test, the lighting and the shadow are put into
+// the kernel argument as launch_frame does.  1-byte voxels read the (x,y) quad copy whatever the view (unless a plane is forced): the label
+// bricks follow that order, and the kernel addresses them with the field's tables.  volume_args has filled the clip words.
+int launch_labelled_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	if (c->shadow_on) { if (const int rc = build_shadow(c)) return rc; }
+	if (const int rc = ensure_label_table(c)) return rc;
+	vr_params q = *p;
+	q.esl = 0u;
+	const int32_t plane_force = c->brick_plane_force;
+	if (c->bpv == 1u && plane_force < 0) c->brick_plane_force = (int32_t) kPlaneXY;
+	const int rc = launch_full_march_frame(c, &q, stream, "labelled", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		RayKernelArgs b = a;
+		b.p.esl = p->esl;
+		esl_divisor(b, p->esl_block_dims);
+		transparent_corner_test(c, b);
+		if (c->lighting_on) {
+			b.light_on = 1u; b.light_ka = c->lighting.ambient; b.light_kd = c->lighting.diffuse; b.light_ks = c->lighting.specular;
+			b.light_n = c->lighting.shininess_log2;
+		}
+		if (c->shadow_on) {
+			const uint32_t S = c->shadow.dims;
+			b.shadow_on = 1u; b.shadow_last = S - 2u; b.shadow_hs = 0.5f * (float) (S - 1u); b.shadow_max = (float) (S - 1u);
+			b.shadow_scale = c->shadow.strength * (1.0f / 255.0f); b.shadow_base = 1.0f - c->shadow.strength;
+			b.shadow_row = S; b.shadow_slab = S * S; b.shadow_q = (uint64_t) (uintptr_t) c->shadow_q;
+		}
+		const bool xy_quads = brick_copy != nullptr && c->bpv == 1u && b.layout == kLayoutBricked && b.brick_plane == kPlaneXY;
+		return launch_labelled(b, c->labels, xy_quads ? label_bricks_for(c) : nullptr, c->vol, brick_copy, c->bpv, c->tf, c->esl, c->label_table, dev_rgba, stream);
+	});
+	c->brick_plane_force = plane_force;
+	if (rc == VR_OK) c->labelled_frames++;
+	return rc;
+}
+
 // the depth buffer of the host entry points that hand a depth back (vr_hip_render_iso, vr_hip_render_section): one float per pixel of the
 // window, sized with the window (render_preamble: the frame fits), allocated on first use behind the context's frames
 int size_host_depth(vr_ctx *c) {
@@ -1497,6 +1581,8 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->backdrop_stage) (void) hipFree(c->backdrop_stage);
 	if (c->depth_stage) (void) hipFree(c->depth_stage);
 	if (c->pick_stage) (void) hipFree(c->pick_stage);
+	drop_labels(c);
+	if (c->label_table) (void) hipFree(c->label_table);
 	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
@@ -2030,6 +2116,85 @@ int vr_hip_pick(vr_ctx *c, const vr_params *p, const vr_depth *d, uint32_t n, co
 int vr_hip_depth_frames(vr_ctx *c, uint64_t *frames_out) {
 	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
 	*frames_out = c->depth_frames;
+	return VR_OK;
+}
+
+// ---- label volumes (include/vr_hip.h vr_label_entry) ----
+
+namespace {
+int set_labels_from(vr_ctx *c, const void *src, bool host, uint32_t x, uint32_t y, uint32_t z) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	VR_TRY(c, hipSetDevice(c->device));
+	if (src == nullptr) {                          // drop
+		VR_TRY(c, drain(c));
+		drop_labels(c);
+		return VR_OK;
+	}
+	if (c->dim[0] == 0) return fail(c, VR_ERR_NOT_READY, "no volume is resident: labels carry the dims of the volume they belong to (vr_hip_set_volume)");
+	if (x != c->dim[0] || y != c->dim[1] || z != c->dim[2]) return fail(c, VR_ERR_INVALID, "label dims differ from the dims of the resident volume");
+	VR_TRY(c, drain(c));                         // frames still reading the labels we are about to replace
+	const uint64_t elems = (uint64_t) x * y * z, slack = volume_tail_slack(x, y);
+	if (c->label_bricks) { (void) hipFree(c->label_bricks); c->label_bricks = nullptr; }
+	c->label_bricks_failed = false;
+	if (c->labels == nullptr) {
+		VR_TRY(c, hipMalloc((void **) &c->labels, elems + slack));
+		VR_TRY(c, hipMemsetAsync(c->labels + elems, 0, slack, c->stream));
+	}
+	const hipError_t e = hipMemcpyAsync(c->labels, src, elems, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream);
+	const hipError_t w = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess || w != hipSuccess) {
+		(void) hipGetLastError();
+		drop_labels(c);
+		return fail(c, VR_ERR_HIP, "copying the labels failed", e != hipSuccess ? e : w);
+	}
+	return VR_OK;
+}
+}  // namespace
+
+int vr_hip_set_labels(vr_ctx *c, const uint8_t *host_labels, uint32_t x, uint32_t y, uint32_t z) { return set_labels_from(c, host_labels, true, x, y, z); }
+
+int vr_hip_set_labels_device(vr_ctx *c, const void *dev_labels, uint32_t x, uint32_t y, uint32_t z) { return set_labels_from(c, dev_labels, false, x, y, z); }
+
+int vr_hip_set_label_table(vr_ctx *c, const vr_label_entry *entries, uint32_t count) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (count > VR_LABEL_COUNT) return fail(c, VR_ERR_INVALID, "a label table has at most 256 entries");
+	if (entries == nullptr && count != 0u) return fail(c, VR_ERR_INVALID, "label entries is NULL");
+	std::vector<float> table(5u * VR_LABEL_COUNT, 0.0f);
+	for (uint32_t i = 0; i < VR_LABEL_COUNT; i++) table[5u * i + 4u] = 1.0f;
+	for (uint32_t i = 0; i < count; i++) {
+		const float m[5] = { entries[i].colour[0], entries[i].colour[1], entries[i].colour[2], entries[i].mix, entries[i].opacity };
+		for (int k = 0; k < 5; k++) {
+			if (!std::isfinite(m[k]) || m[k] < 0.0f || m[k] > 1.0f) return fail(c, VR_ERR_INVALID, "label table members must be finite and in [0, 1]");
+			table[5u * i + (uint32_t) k] = m[k];
+		}
+	}
+	VR_TRY(c, hipSetDevice(c->device));
+	if (const int rc = ensure_label_table(c)) return rc;
+	VR_TRY(c, drain(c));                         // frames still reading the table we are about to rewrite
+	VR_TRY(c, hipMemcpy(c->label_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+	return VR_OK;
+}
+
+int vr_hip_render_labelled_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate_labelled(c, p)) return rc;
+	return launch_labelled_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
+}
+
+int vr_hip_render_labelled(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate_labelled(c, p);
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch_labelled_frame(c, p, c->fb, c->stream);
+	if (rc) return rc;
+	return frame_to_host(c, host_rgba, (size_t) p->out_width * p->out_rows * 4, t0);
+}
+
+int vr_hip_labelled_frames(vr_ctx *c, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->labelled_frames;
 	return VR_OK;
 }
 

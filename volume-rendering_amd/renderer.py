@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import (VrBackdrop, VrDepthOut, VrError, VrIso, VrLaunchInfo, VrParams, VrPick, VrTiming, lib, make_clip, make_depth, make_lighting, make_section,
-                      make_shadow)
+from .binding import (VrBackdrop, VrDepthOut, VrError, VrIso, VrLabelEntry, VrLaunchInfo, VrParams, VrPick, VrTiming, lib, make_clip, make_depth, make_label_entry,
+                      make_lighting, make_section, make_shadow)
 
 
 class HipRenderer:
@@ -397,6 +397,60 @@ class HipRenderer:
         """vr_hip_depth_frames: the depth frames this context launched (a pick counts one per pixel)"""
         n = C.c_uint64(0)
         self._check(self._L.vr_hip_depth_frames(self._ctx, C.byref(n)), "depth_frames")
+        return int(n.value)
+
+    # -- label volumes (vr_hip_set_labels, vr_hip_set_label_table, vr_hip_render_labelled: per-segment colour and visibility for composite frames)
+    def set_labels(self, labels):
+        """vr_hip_set_labels: the segment of every voxel, one byte each, with the dims of the resident volume.  `labels` is a numpy array
+        shaped (z, y, x) of uint8, or a contiguous uint8 device tensor of that shape (copied on the context's stream).  A new volume drops them."""
+        if hasattr(labels, "data_ptr"):
+            if str(labels.dtype) != "torch.uint8" or labels.dim() != 3 or not labels.is_contiguous() or not labels.is_cuda:
+                raise VrError(1, "labels must be a contiguous 3-D uint8 device tensor")
+            z, y, x = (int(n) for n in labels.shape)
+            self._check(self._L.vr_hip_set_labels_device(self._ctx, C.c_void_p(labels.data_ptr()), x, y, z), "set_labels")
+            return
+        v = np.ascontiguousarray(labels)
+        if v.dtype != np.uint8 or v.ndim != 3:
+            raise VrError(1, "labels must be a 3-D uint8 array")
+        z, y, x = v.shape
+        self._check(self._L.vr_hip_set_labels(self._ctx, v.ctypes.data, x, y, z), "set_labels")
+
+    def clear_labels(self):
+        """Drops the labels: render_labelled is VR_ERR_NOT_READY until they are set again.  The table stays."""
+        self._check(self._L.vr_hip_set_labels(self._ctx, None, 0, 0, 0), "clear_labels")
+
+    def set_label_table(self, entries=None):
+        """vr_hip_set_label_table: what each label does to a sample's classified colour.  `entries`: at most 256 of VrLabelEntry, dict(colour,
+        mix, opacity) or (r, g, b, mix, opacity), entry i for label i; the rest — and everything for None — are the identity (mix 0, opacity 1)."""
+        items = list(entries) if entries is not None else []
+        table = (VrLabelEntry * max(len(items), 1))()
+        for i, e in enumerate(items):
+            if isinstance(e, VrLabelEntry):
+                table[i] = e
+            elif isinstance(e, dict):
+                table[i] = make_label_entry(**e)
+            else:
+                table[i] = make_label_entry(e[0:3], e[3], e[4])
+        self._check(self._L.vr_hip_set_label_table(self._ctx, table if items else None, len(items)), "set_label_table")
+
+    def render_labelled(self, params):
+        """Host-buffer flavour: the composite frame with every sample's colour passed through the table entry of its nearest voxel's label; an
+        (out_rows, out_width, 4) uint8 array.  The context's clip, lighting and shadow apply; params.sampling must be one of the TRILINEAR modes."""
+        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_labelled(self._ctx, C.byref(params), out.ctypes.data), "render_labelled")
+        return out
+
+    def render_labelled_device(self, params, dev_ptr, stream=None):
+        """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
+        self._resolve_shadow(params.ray_step)
+        self._check(self._L.vr_hip_render_labelled_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream) if stream else None),
+                    "render_labelled_device")
+
+    def labelled_frames(self):
+        """vr_hip_labelled_frames: the labelled frames this context launched"""
+        n = C.c_uint64(0)
+        self._check(self._L.vr_hip_labelled_frames(self._ctx, C.byref(n)), "labelled_frames")
         return int(n.value)
 
     # -- timing (Profiler.cpp:46-67)
