@@ -762,7 +762,35 @@ uint32_t vr_hip_multi_default_band_rows(uint32_t height, uint32_t n);
 #define VR_COPY_COLV_Z   (1u << 12)
 #define VR_COPY_ALL      0x1fffu
 #define VR_COPY_KINDS    13
+/* Aligned run bricks along z / y (1-byte voxels, edges <= 1024): runs of 8 elements = 32 bytes that cover SEVEN cells, bricks of 2048 bytes —
+ * no run straddles a 128-byte line, every line is one 2x2 block of cell columns (volume-rendering_amd/csrc/vr_device.h).  32/7 bytes per
+ * voxel each.  Behind the VR_COPY_KINDS kinds and NOT part of VR_COPY_ALL, of vr_volume_info::copies_in_policy or ::build_ms:
+ * built by the first full-march frame that reads them (vr_hip_set_run_flavour) or by vr_hip_prepare when their bit is named; resident or
+ * refused they show under these bits in vr_volume_info::copies / ::copies_refused and count in ::bricked_bytes, their build times are in
+ * vr_hip_run_aligned_info.
+ * vr_hip_download_copy takes their bit indices 13 / 14. */
+#define VR_COPY_RUN7_Z   (1u << 13)
+#define VR_COPY_RUN7_Y   (1u << 14)
 int vr_hip_prepare(vr_ctx *ctx, uint32_t copies);
+/* Which flavour of the run bricks a frame reads that reads run bricks at all (vr_launch_info::layout 2, 3 or 6).
+ *   0  automatic (the default): a FULL-MARCH frame (esl off, ray_threshold >= 1) reads the aligned kind (VR_COPY_RUN7_*) where it is
+ *      resident or can be built, else the nine-element kind; every other frame — leaping, early termination — reads the nine-element kind;
+ *   1  nine-element runs (VR_COPY_RUN_*) for every frame;
+ *   2  seven-cell aligned runs for every full-march frame, as 0 (the switch exists for A/B runs and tests: 0 may stop choosing them).
+ * The image is the same bit for bit whichever is read; which copy a tile reads, lane maps and wave shapes do not depend on it.  Anything
+ * else is VR_ERR_INVALID.  Forgets nothing: the cached tile mappings do not depend on the flavour. */
+int vr_hip_set_run_flavour(vr_ctx *ctx, uint32_t flavour);
+/* The aligned run bricks of the resident volume and what the last composite frame read.  These facts live here and not in vr_volume_info /
+ * vr_launch_info, whose sizes and members are pinned. */
+typedef struct vr_run_aligned_info {
+	uint32_t flavour;         /* vr_hip_set_run_flavour: 0, 1 or 2 */
+	uint32_t last_flavour;    /* the last vr_hip_render* frame: 0 = it read no run bricks, 1 = nine-element runs, 2 = seven-cell aligned runs */
+	uint32_t copies;          /* VR_COPY_RUN7_* bits resident now */
+	uint32_t copies_refused;  /* VR_COPY_RUN7_* bits whose build was refused (HBM guard / allocation) */
+	uint64_t bytes;           /* what the resident aligned copies occupy */
+	float    build_ms[2];     /* hipEvent time of the kernel that built the copy along z / y (0 if never built) */
+} vr_run_aligned_info;        /* 32 bytes */
+int vr_hip_run_aligned_info(vr_ctx *ctx, vr_run_aligned_info *out);
 /* Testing aid: the raw bytes of one resident brick copy (kind = bit index of its VR_COPY_* flag), so that a test can hold every copy
  * builder against a host-side construction of the layout, byte for byte.  *bytes_out (optional) = size of the copy; host_out may be
  * NULL for a size query.  VR_ERR_NOT_READY if the copy is not resident, VR_ERR_INVALID if capacity is too small. */

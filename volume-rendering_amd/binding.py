@@ -10,6 +10,9 @@ LAYOUT_BRICKED = 1
 # VR_COPY_* bits (vr_hip_prepare / vr_volume_info.copies): quad bricks per chunk plane, run bricks along z / y, voxel bricks
 COPY_QUAD_XY, COPY_QUAD_XZ, COPY_QUAD_YZ, COPY_RUN_Z, COPY_RUN_Y, COPY_VOXEL, COPY_OCT, COPY_COL_X, COPY_COL_Y, COPY_COL_Z, COPY_ALL = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 8191
 COPY_COLV_X, COPY_COLV_Y, COPY_COLV_Z = 1024, 2048, 4096
+# aligned run bricks along z / y (32-byte runs of seven cells): behind the COPY_KINDS kinds, not part of COPY_ALL; download_copy kinds 13 / 14
+COPY_RUN7_Z, COPY_RUN7_Y = 1 << 13, 1 << 14
+RUN_FLAVOUR_AUTO, RUN_FLAVOUR_NINE, RUN_FLAVOUR_SEVEN = 0, 1, 2      # vr_hip_set_run_flavour
 COPY_NAMES = ("quad_xy", "quad_xz", "quad_yz", "run_z", "run_y", "voxel", "oct", "col_x", "col_y", "col_z", "colv_x", "colv_y", "colv_z")
 COPY_KINDS = 13
 TF_SIZE = 128
@@ -175,6 +178,11 @@ class VrVolumeInfo(C.Structure):
                 ("build_ms", C.c_float * 13), ("upload_ms", C.c_float)]
 
 
+class VrRunAlignedInfo(C.Structure):
+    _fields_ = [("flavour", C.c_uint32), ("last_flavour", C.c_uint32), ("copies", C.c_uint32), ("copies_refused", C.c_uint32),
+                ("bytes", C.c_uint64), ("build_ms", C.c_float * 2)]
+
+
 class VrTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_float), ("total_ms", C.c_float), ("launches", C.c_uint64), ("kernel_ms_sum", C.c_double),
                 ("kernel_ms_max", C.c_float), ("total_ms_max", C.c_float)]
@@ -224,6 +232,8 @@ def lib():
         "vr_hip_set_tile_mapping": (C.c_int, [vp, C.c_int32, u32, u32]),
         "vr_hip_set_brick_plane": (C.c_int, [vp, C.c_int32]),
         "vr_hip_set_column_copy": (C.c_int, [vp, u32]),
+        "vr_hip_set_run_flavour": (C.c_int, [vp, u32]),
+        "vr_hip_run_aligned_info": (C.c_int, [vp, P(VrRunAlignedInfo)]),
         "vr_hip_set_tile_scheduling": (C.c_int, [vp, u32]),
         "vr_hip_set_clip": (C.c_int, [vp, P(VrClip)]),
         "vr_hip_set_shadow": (C.c_int, [vp, P(VrShadow)]),

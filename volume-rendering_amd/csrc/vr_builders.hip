@@ -27,13 +27,19 @@ template <int BPV, int KIND> struct StripCfg {
 
 template <int BPV, int KIND, int PLANE>
 __global__ __launch_bounds__(kStripThreads)
-void brick_strip_kernel(const void *__restrict__ lin, uint4 *__restrict__ out, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t nbx) {
+void brick_strip_kernel(const void *__restrict__ lin, uint4 *__restrict__ out, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t nbx, uint32_t run_cells) {
 	typedef StripCfg<BPV, KIND> S;
+	// run bricks: run_cells = cells a brick covers along the run axis — 8 (runs of 9 elements, 2304-byte bricks) or kRun7Cells (the aligned
+	// flavour: runs of 8 elements, 2048-byte bricks; vr_device.h).  A run holds run_cells + 1 elements, the last one the next brick's first,
+	// so the 9 staged slices / rows serve both.  The other kinds ignore it (8 cells per brick edge).
+	constexpr bool kRun = KIND == kBuildRunZ || KIND == kBuildRunY;
+	const uint32_t cells_r = kRun ? run_cells : 8u, run_len = cells_r + 1u;
+	const uint32_t chunks_per_brick = kRun ? run_len * (64u * 4u / 16u) : S::chunks_per_brick;
 	typedef typename VoxelT<BPV>::type V;
 	__shared__ uint32_t rows[S::ny * S::nz * S::pitch_words];
 	// brick order: x fastest, then the "other" axis, then the outer axis (quad / voxel / oct / runs along z: y then z; runs along y: z then y)
 	const uint32_t bx0 = blockIdx.x * kStripBricks, mid = blockIdx.y, outer = blockIdx.z;
-	const uint32_t y0 = (KIND == kBuildRunY ? outer : mid) * 8u, z0 = (KIND == kBuildRunY ? mid : outer) * 8u, x0 = bx0 * 8u;
+	const uint32_t y0 = KIND == kBuildRunY ? outer * cells_r : mid * 8u, z0 = KIND == kBuildRunY ? mid * 8u : outer * cells_r, x0 = bx0 * 8u;
 	const uint32_t t = threadIdx.x;
 	// -- stage: row (dy, dz) = voxels x0 .. x0 + 128 of line (min(y0 + dy, Y-1), min(z0 + dz, Z-1)), x clamped to X-1
 	{
@@ -71,9 +77,9 @@ void brick_strip_kernel(const void *__restrict__ lin, uint4 *__restrict__ out, u
 	};
 	const uint32_t bricks_here = nbx - bx0 < kStripBricks ? nbx - bx0 : kStripBricks;
 	const uint64_t first_brick = ((uint64_t) outer * gridDim.y + mid) * nbx + bx0;
-	uint4 *dst = out + first_brick * S::chunks_per_brick;
-	for (uint32_t c = t; c < bricks_here * S::chunks_per_brick; c += kStripThreads) {
-		const uint32_t b = c / S::chunks_per_brick, in = c - b * S::chunks_per_brick, xb = b * 8u;      // brick of the strip, chunk inside it
+	uint4 *dst = out + first_brick * chunks_per_brick;
+	for (uint32_t c = t; c < bricks_here * chunks_per_brick; c += kStripThreads) {
+		const uint32_t b = c / chunks_per_brick, in = c - b * chunks_per_brick, xb = b * 8u;      // brick of the strip, chunk inside it
 		uint32_t w[4];
 		#pragma unroll
 		for (uint32_t i = 0; i < 4u; i++) {
@@ -94,8 +100,8 @@ void brick_strip_kernel(const void *__restrict__ lin, uint4 *__restrict__ out, u
 					if (x0 + xb + lx < dim_x && y0 + ly < dim_y && z0 + lz < dim_z) word |= vox(xb + lx, ly, lz) << (8u * BPV * j);
 				}
 			} else {
-				// run bricks: 64 cell columns (2-D Morton over x and the other axis) x 9 elements along the run axis; element 8 = the next brick's first
-				const uint32_t e = in * 4u + i, cell = e / kRunLen, k = e - cell * kRunLen;
+				// run bricks: 64 cell columns (2-D Morton over x and the other axis) x 9 (8: aligned) elements along the run axis; the last = the next brick's first
+				const uint32_t e = in * 4u + i, cell = run_len == kRun7Len ? e / kRun7Len : e / kRunLen, k = e - cell * run_len;
 				const uint32_t lx = (cell & 1u) | ((cell >> 1) & 2u) | ((cell >> 2) & 4u), lo = ((cell >> 1) & 1u) | ((cell >> 2) & 2u) | ((cell >> 3) & 4u);
 				if (KIND == kBuildRunZ) {
 					if (x0 + xb + lx < dim_x && y0 + lo < dim_y) word = quad_word(xb + lx, lo, k, 0u);
@@ -110,10 +116,12 @@ void brick_strip_kernel(const void *__restrict__ lin, uint4 *__restrict__ out, u
 }
 
 template <int BPV, int KIND, int PLANE>
-static hipError_t launch_strip(const void *linear, void *copy, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
+static hipError_t launch_strip(const void *linear, void *copy, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream, bool aligned_runs = false) {
 	const uint32_t nbx = (dim_x + 7u) / 8u, nby = (dim_y + 7u) / 8u, nbz = (dim_z + 7u) / 8u;
-	const dim3 grid((nbx + kStripBricks - 1u) / kStripBricks, KIND == kBuildRunY ? nbz : nby, KIND == kBuildRunY ? nby : nbz);
-	hipLaunchKernelGGL((brick_strip_kernel<BPV, KIND, PLANE>), grid, dim3(kStripThreads), 0, stream, linear, (uint4 *) copy, dim_x, dim_y, dim_z, nbx);
+	// (the aligned run bricks: ceil(n / 7) bricks along the run axis, the outer axis of the grid)
+	const uint32_t run_cells = aligned_runs ? kRun7Cells : 8u, nbr = aligned_runs ? run7_bricks(KIND == kBuildRunY ? dim_y : dim_z) : (KIND == kBuildRunY ? nby : nbz);
+	const dim3 grid((nbx + kStripBricks - 1u) / kStripBricks, KIND == kBuildRunY ? nbz : nby, nbr);
+	hipLaunchKernelGGL((brick_strip_kernel<BPV, KIND, PLANE>), grid, dim3(kStripThreads), 0, stream, linear, (uint4 *) copy, dim_x, dim_y, dim_z, nbx, run_cells);
 	return hipGetLastError();
 }
 
@@ -139,9 +147,10 @@ hipError_t launch_brickify_voxel(const void *linear, void *voxel_bricks, uint32_
 // linear -> run bricks (1-byte voxels): element k = 8 of a run is the first element of the next brick along the run axis (index clamped at
 // the upper face, where the interpolation weight is exactly 0).  Runs along z: element = (x,y) neighbourhood of slice z; runs along y:
 // element = (x,z) neighbourhood of row y.
-hipError_t launch_brickify_run(const void *linear, void *run_copy, uint32_t run_layout, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
-	if (run_layout == kLayoutRunY) return launch_strip<1, kBuildRunY, kPlaneXY>(linear, run_copy, dim_x, dim_y, dim_z, stream);
-	return launch_strip<1, kBuildRunZ, kPlaneXY>(linear, run_copy, dim_x, dim_y, dim_z, stream);
+// `aligned`: the 32-byte runs of seven cells (vr_device.h kRun7*): the same kernel with 7 cells per brick along the run axis.
+hipError_t launch_brickify_run(const void *linear, void *run_copy, uint32_t run_layout, bool aligned, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
+	if (run_layout == kLayoutRunY) return launch_strip<1, kBuildRunY, kPlaneXY>(linear, run_copy, dim_x, dim_y, dim_z, stream, aligned);
+	return launch_strip<1, kBuildRunZ, kPlaneXY>(linear, run_copy, dim_x, dim_y, dim_z, stream, aligned);
 }
 
 // ---- linear -> column windows (kLayoutColumn): LDS-tiled like the brick strips --------------------------------------------------------

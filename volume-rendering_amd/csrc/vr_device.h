@@ -130,6 +130,10 @@ struct RayKernelArgs {
 	// the clip words: the depth in front of the march, the colour (and the depth again) behind it.  Addresses, not pointers: the output buffer
 	// may be the colour layer.  backdrop_on is for the host (launch_raymarch hands such a frame to the new units).
 	uint32_t backdrop_on;
+	// The flavour of the run bricks a run-layout frame reads: 1 = `vol` / alt_copy are the ALIGNED run bricks (kCopyRun7Z / Y: 32-byte runs
+	// of seven cells), 0 = the 36-byte runs.  Wave-uniform; read by the table staging of the run layouts only.  HERE because these four bytes
+	// were alignment padding: no other member moves and the argument keeps its size, so no other kernel's loads change.
+	uint32_t run_aligned;
 	uint64_t backdrop_rgba, backdrop_depth;
 };
 // Tiles are numbered in VR_TILE_ORDER x VR_TILE_ORDER blocks (blocks row-major, tiles column by column inside a block — VR_XCD_MODE
@@ -225,11 +229,22 @@ constexpr uint32_t kTileAltBit = 0x80000000u;       // kLayoutRunDual: set in a 
 __host__ __device__ constexpr bool is_brick_table_layout(int layout) { return layout == (int) kLayoutBricked || layout == (int) kLayoutVoxel; }
 constexpr uint32_t kRunLen = 9, kRunBytes = kRunLen * 4, kRunBrickBytes = 64 * kRunBytes;       // 8x8 cell columns per brick
 // byte offset of cell column (x & 7, y & 7) inside a run brick: 2-D Morton order, 36-byte runs
-__host__ __device__ inline uint32_t run_cell_spread(uint32_t axis, uint32_t v) {
-	return (((v & 1u) << axis) | (((v >> 1) & 1u) << (2 + axis)) | (((v >> 2) & 1u) << (4 + axis))) * kRunBytes;
+__host__ __device__ inline uint32_t run_cell_order(uint32_t axis, uint32_t v) {       // ... the column's place in that order (both flavours)
+	return ((v & 1u) << axis) | (((v >> 1) & 1u) << (2 + axis)) | (((v >> 2) & 1u) << (4 + axis));
 }
+__host__ __device__ inline uint32_t run_cell_spread(uint32_t axis, uint32_t v) { return run_cell_order(axis, v) * kRunBytes; }
 inline uint64_t run_copy_bytes(uint32_t dim_x, uint32_t dim_y, uint32_t dim_z) {
 	return (uint64_t) ((dim_x + 7) / 8) * ((dim_y + 7) / 8) * ((dim_z + 7) / 8) * kRunBrickBytes + 16;
+}
+// The second flavour of the run bricks, "aligned runs" (kCopyRun7Z / kCopyRun7Y): a run is 8 elements = 32 bytes and covers SEVEN cells
+// along the run axis — element 7 duplicates the next brick's first, as element 8 does above — so a brick of 8x8 cell columns is 2048
+// bytes, the run axis has ceil(n / 7) bricks, no run straddles a 128-byte line and every line is one 2x2 block of cell columns (the same
+// 2-D Morton order) x 7 cells; a slice pair straddles a 16-byte chunk in 1 of 7 positions instead of 1 of 4.  32/7 bytes per voxel.
+// The march reads both flavours with the same instructions: only the address tables (vr_raymarch_body.inc) and the builder differ.
+constexpr uint32_t kRun7Cells = 7, kRun7Len = 8, kRun7Bytes = kRun7Len * 4, kRun7BrickBytes = 64 * kRun7Bytes;
+__host__ __device__ constexpr uint32_t run7_bricks(uint32_t n) { return (n + kRun7Cells - 1u) / kRun7Cells; }
+inline uint64_t run7_copy_bytes(uint32_t dim_x, uint32_t dim_other, uint32_t dim_run) {       // the same 16 bytes of tail slack
+	return (uint64_t) ((dim_x + 7) / 8) * ((dim_other + 7) / 8) * run7_bricks(dim_run) * kRun7BrickBytes + 16;
 }
 enum : uint32_t { kLaneRows = 0, kLaneColumns = 1, kLaneBlocks = 2 };
 constexpr uint32_t kBrickEdge = 8, kBrickPitch = 512;
@@ -250,6 +265,11 @@ enum : uint32_t { kCopyQuadXY = 0, kCopyQuadXZ = 1, kCopyQuadYZ = 2, kCopyRunZ =
                   kCopyColVoxX = 10, kCopyColVoxY = 11, kCopyColVoxZ = 12,      // ... of plain voxels: NEAREST
                   kCopyKinds = 13 };
 static_assert(kCopyKinds == VR_COPY_KINDS, "include/vr_hip.h VR_COPY_KINDS");
+// ... and behind the kinds vr_volume_info counts (its build_ms array keeps VR_COPY_KINDS slots): the aligned run bricks along z / y
+// (above).  Not in VR_COPY_ALL nor in the policy's default set: built on first use by a full-march frame that reads run bricks, or by
+// vr_hip_prepare when their bit is named; reported by vr_hip_run_aligned_info.
+enum : uint32_t { kCopyRun7Z = kCopyKinds, kCopyRun7Y = kCopyKinds + 1, kCopySlots = kCopyKinds + 2 };
+static_assert((1u << kCopyRun7Z) == VR_COPY_RUN7_Z && (1u << kCopyRun7Y) == VR_COPY_RUN7_Y, "include/vr_hip.h VR_COPY_RUN7_*");
 // column windows (kLayoutColumn): lateral axes (u, v) of march axis m are the two other axes in increasing order
 // A lateral block is kColEdge x kColEdge cell columns: its windows are kColBlockBytes each and follow each other along m.  4 x 4 columns
 // = what one wave's 8 x 8 pixels cover at the reference's zoom, 256 bytes per window.  Measured against 8 x 8 columns (1 KiB per window
@@ -319,8 +339,8 @@ hipError_t launch_brickify_voxel(const void *linear, void *voxel_bricks, uint32_
 // linear -> oct bricks (2-byte voxels): element = the 2x2x2 neighbourhood, 16 bytes
 hipError_t launch_brickify_oct(const void *linear, void *oct_bricks, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
 // linear -> run bricks (1-byte voxels)
-hipError_t launch_brickify_run(const void *linear, void *run_copy, uint32_t run_layout /* kLayoutRun | kLayoutRunY */, uint32_t dim_x, uint32_t dim_y,
-                               uint32_t dim_z, hipStream_t stream);
+hipError_t launch_brickify_run(const void *linear, void *run_copy, uint32_t run_layout /* kLayoutRun | kLayoutRunY */, bool aligned /* 32-byte runs of seven cells */,
+                               uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
 // linear -> column windows along axis m (1-byte voxels)
 hipError_t launch_build_column(const void *linear, void *col_copy, uint32_t axis, bool voxels /* NEAREST windows */, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
 // number of quad elements (each 4 * bytes_per_voxel bytes)

@@ -49,9 +49,11 @@ struct vr_ctx {
 	// builds the (x,z) / (y,z) planes.  copy[kCopyQuadXY..YZ] = quad bricks per chunk plane, kCopyRunZ / kCopyRunY = run bricks,
 	// kCopyVoxel = voxel bricks (what NEAREST reads), kCopyOct = oct bricks (what TRILINEAR reads for 2-byte voxels).  copy_failed: a build was refused (HBM guard / allocation) — not retried
 	// until the next set_volume, so a frame never stalls twice on the same refusal.
-	void *copy[kCopyKinds] = {};            // kCopyColX..Z = column windows along x / y / z (orthogonal full-march frames along that axis)
-	float copy_build_ms[kCopyKinds] = {};
-	bool copy_failed[kCopyKinds] = {};
+	void *copy[kCopySlots] = {};            // kCopyColX..Z = column windows along x / y / z (orthogonal full-march frames along that axis)
+	float copy_build_ms[kCopySlots] = {};   // kCopyRun7Z / Y (behind the kCopyKinds kinds vr_volume_info counts) = the aligned run bricks: full-march frames that read run bricks
+	bool copy_failed[kCopySlots] = {};
+	uint32_t run_flavour = 0;               // vr_hip_set_run_flavour: 0 = automatic, 1 = nine-element runs, 2 = seven-cell aligned runs (full-march frames)
+	uint32_t last_run_flavour = 0;          // vr_hip_run_aligned_info: what the last composite frame read (0 no run bricks, 1 nine-element, 2 aligned)
 	int32_t column_force = 0;               // vr_hip_set_brick_plane: 0 = per view (views along a volume axis), 1 (plane 8) = every orthogonal full-march frame, -1 (plane 9) = never
 	uint32_t column_copy = 0;               // vr_hip_set_column_copy: 0 = TRILINEAR column frames read the voxel windows where a wave's columns fit (lit frames shade from the
 	                                        // quad-element windows), 1 = the quad-element windows, 2 = as 0, shading by byte loads from the voxel windows (no second copy)
@@ -439,10 +441,15 @@ void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
 	else { a.esl_div_magic = (uint32_t) ((1ull << 32) / bd + 1); a.esl_div_shift = 0; }
 }
 
+// What vr_hip_set_run_flavour(0), the automatic choice, gives a full-march frame that reads run bricks: the aligned flavour (true) or the
+// nine-element runs (false).  Measured (profiles/run7_ab.txt): the eight-view cycle 1.821 -> 1.747 ms per frame, the five run-brick views -2 .. -10 %.
+constexpr bool kRunAutoAligned = true;
+
 // ---- what launch_frame and launch_full_march_frame (further down) decide the same way ----------------------------------------------------
 
 // the copy a frame of this layout reads (not asked for kLayoutLinear)
 uint32_t copy_kind_of(const RayKernelArgs &a, uint32_t sampling) {
+	if (is_run_layout((int) a.layout) && a.run_aligned) return a.layout == kLayoutRunY ? kCopyRun7Y : kCopyRun7Z;
 	return a.layout == kLayoutRun || a.layout == kLayoutRunDual ? kCopyRunZ : a.layout == kLayoutRunY ? kCopyRunY : a.layout == kLayoutVoxel ? kCopyVoxel :
 	       a.layout == kLayoutOct ? kCopyOct : a.layout == kLayoutColumn ? (sampling == VR_SAMPLE_NEAREST ? kCopyColVoxX : kCopyColX) + a.col_axis :
 	       a.layout == kLayoutVoxCol ? kCopyColVoxX + a.col_axis : kCopyQuadXY + a.brick_plane;
@@ -549,7 +556,7 @@ hipError_t bounds_check_arm(vr_ctx *c, RayKernelArgs &a, const vr_params *p, con
 	a.bc_bytes = plan.reads_linear ? (c->vol_elems + volume_tail_slack(c->dim[0], c->dim[1])) * c->bpv :
 	             copy_bytes(c, copy_kind_of(a, p->sampling));
 	if (column) a.bc_bytes += 2ull * kColPadBytes;
-	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, a.layout == kLayoutVoxCol ? kCopyColX + a.col_axis : (uint32_t) kCopyRunY) : 0;      // (the pair fetch never reads the padding)
+	a.bc_alt_bytes = a.alt_copy ? copy_bytes(c, a.layout == kLayoutVoxCol ? kCopyColX + a.col_axis : (uint32_t) (a.run_aligned ? kCopyRun7Y : kCopyRunY)) : 0;      // (the pair fetch never reads the padding)
 	a.bc_fault = c->bc_fault; a.bc_ntiles = ntiles;
 	// self-test of the net itself: VR_BC_SELFTEST=1 halves the size the checks hold the gathers against — a full-march frame must then fail
 	if (const char *e = getenv("VR_BC_SELFTEST")) if (atoi(e) == 1) a.bc_bytes /= 2;
@@ -805,7 +812,22 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// The copy this frame reads, built now if this is its first use.  A build that is refused (HBM guard, allocation, linear array
 	// released) degrades to the next best resident copy; the image is the same.
 	const void *brick_copy = nullptr;
-	if (a.layout == kLayoutRunDual) {
+	// Run bricks, full march (the condition of kLayoutRunDual: with leaping or early termination the rays are short, and those frames keep
+	// the copies they have): the ALIGNED flavour (vr_device.h kRun7*: no run straddles a cache line) where the copies the frame would read
+	// are resident or can be built — same tiles, same copy per tile, same lane maps and wave shapes, same image; vr_hip_set_run_flavour.
+	// A build that is refused leaves the frame on the nine-element runs.
+	if (is_run_layout((int) a.layout) && !p->esl && p->ray_threshold >= 1.0f && c->bpv == 1 && (c->run_flavour == 2u || (c->run_flavour == 0u && kRunAutoAligned))) {
+		const bool want_z = a.layout != kLayoutRunY, want_y = a.layout != kLayoutRun;
+		if ((!want_z || copy_possible(c, kCopyRun7Z)) && (!want_y || copy_possible(c, kCopyRun7Y))) {
+			const void *cz = want_z ? copy_for(c, kCopyRun7Z) : nullptr, *cy = want_y ? copy_for(c, kCopyRun7Y) : nullptr;
+			if ((!want_z || cz != nullptr) && (!want_y || cy != nullptr)) {
+				a.run_aligned = 1u;
+				brick_copy = want_z ? cz : cy;
+				if (a.layout == kLayoutRunDual) a.alt_copy = (uint64_t) (uintptr_t) cy;
+			}
+		}
+	}
+	if (a.layout == kLayoutRunDual && brick_copy == nullptr) {
 		brick_copy = copy_for(c, kCopyRunZ);
 		a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyRunY);
 		if (brick_copy == nullptr || a.alt_copy == 0) { a.layout = run_layout; dual_stage = -1; dual_analytic = false; brick_copy = nullptr; }
@@ -985,6 +1007,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
 	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : uncached_straddle,
 	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u, shadow ? 1u : 0u };
+	c->last_run_flavour = is_run_layout((int) a.layout) && brick_copy != nullptr ? (a.run_aligned ? 2u : 1u) : 0u;
 
 	uint64_t frame_seq = 0;
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
@@ -1010,7 +1033,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 
 int ready(vr_ctx *c) {
 	bool any = c->vol != nullptr;
-	for (uint32_t k = 0; k < kCopyKinds; k++) any = any || c->copy[k] != nullptr;
+	for (uint32_t k = 0; k < kCopySlots; k++) any = any || c->copy[k] != nullptr;
 	if (!any) return fail(c, VR_ERR_NOT_READY, "render before set_volume");
 	if (!c->tf_set) return fail(c, VR_ERR_NOT_READY, "render before set_transfer_fn");
 	return VR_OK;
@@ -1025,7 +1048,7 @@ hipError_t drain(vr_ctx *c) {
 }
 
 void free_bricks(vr_ctx *c) {
-	for (uint32_t k = 0; k < kCopyKinds; k++) {
+	for (uint32_t k = 0; k < kCopySlots; k++) {
 		if (c->copy[k]) { (void) hipFree(k >= kCopyColX && k <= kCopyColVoxZ ? (uint8_t *) c->copy[k] - kColPadBytes : (uint8_t *) c->copy[k]); c->copy[k] = nullptr; }
 		c->copy_build_ms[k] = 0; c->copy_failed[k] = false;
 	}
@@ -1037,6 +1060,8 @@ uint64_t copy_bytes(const vr_ctx *c, uint32_t kind) {
 	if (kind == kCopyOct) return bricked_elems(c->dim[0], c->dim[1], c->dim[2]) * 8 * c->bpv;
 	if (kind >= kCopyColX && kind <= kCopyColZ) return col_copy_bytes(c->dim, kind - kCopyColX);
 	if (kind >= kCopyColVoxX && kind <= kCopyColVoxZ) return col_copy_bytes(c->dim, kind - kCopyColVoxX, true);
+	if (kind == kCopyRun7Z) return run7_copy_bytes(c->dim[0], c->dim[1], c->dim[2]);
+	if (kind == kCopyRun7Y) return run7_copy_bytes(c->dim[0], c->dim[2], c->dim[1]);
 	return run_copy_bytes(c->dim[0], c->dim[1], c->dim[2]);
 }
 
@@ -1086,7 +1111,7 @@ int build_copy(vr_ctx *c, uint32_t kind) {
 		else if (kind == kCopyOct) e = launch_brickify_oct(c->vol, dst, c->dim[0], c->dim[1], c->dim[2], c->stream);
 		else if (kind >= kCopyColX && kind <= kCopyColZ) e = launch_build_column(c->vol, dst, kind - kCopyColX, false, c->dim[0], c->dim[1], c->dim[2], c->stream);
 		else if (kind >= kCopyColVoxX && kind <= kCopyColVoxZ) e = launch_build_column(c->vol, dst, kind - kCopyColVoxX, true, c->dim[0], c->dim[1], c->dim[2], c->stream);
-		else e = launch_brickify_run(c->vol, dst, kind == kCopyRunY ? kLayoutRunY : kLayoutRun, c->dim[0], c->dim[1], c->dim[2], c->stream);
+		else e = launch_brickify_run(c->vol, dst, kind == kCopyRunY || kind == kCopyRun7Y ? kLayoutRunY : kLayoutRun, kind >= kCopyRun7Z, c->dim[0], c->dim[1], c->dim[2], c->stream);
 	}
 	if (e == hipSuccess) e = hipEventRecord(c->aux_stop, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1213,6 +1238,7 @@ int launch_full_march_frame(vr_ctx *c, const vr_params *p, hipStream_t stream, c
 		return fail(c, VR_ERR_NOT_READY, (std::string("this ") + what + " frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                  "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again").c_str());
 	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u, 0u };
+	c->last_run_flavour = 0u;                    // (these frames read no run bricks)
 	uint64_t frame_seq = 0;
 	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch(a, brick_copy, a.p.esl ? c->mip_bounds : nullptr); });
 }
@@ -1711,6 +1737,25 @@ int vr_hip_set_column_copy(vr_ctx *c, uint32_t mode) {
 	if (mode > 2u) return fail(c, VR_ERR_INVALID, "column copy must be 0 (voxel windows where a wave's columns fit, else quad-element windows; lit frames shade from the "
 	                                              "quad-element windows), 1 (quad-element windows) or 2 (as 0, shading from the voxel windows)");
 	c->column_copy = mode;
+	return VR_OK;
+}
+
+int vr_hip_set_run_flavour(vr_ctx *c, uint32_t flavour) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (flavour > 2u) return fail(c, VR_ERR_INVALID, "run flavour must be 0 (automatic), 1 (nine-element runs) or 2 (seven-cell aligned runs for full-march frames)");
+	c->run_flavour = flavour;
+	return VR_OK;
+}
+
+int vr_hip_run_aligned_info(vr_ctx *c, vr_run_aligned_info *out) {
+	if (c == nullptr || out == nullptr) return VR_ERR_INVALID;
+	memset(out, 0, sizeof *out);
+	out->flavour = c->run_flavour; out->last_flavour = c->last_run_flavour;
+	for (uint32_t k = kCopyRun7Z; k <= kCopyRun7Y; k++) {
+		out->build_ms[k - kCopyRun7Z] = c->copy_build_ms[k];
+		if (c->copy_failed[k]) out->copies_refused |= 1u << k;
+		if (c->copy[k]) { out->copies |= 1u << k; out->bytes += copy_bytes(c, k); }
+	}
 	return VR_OK;
 }
 
@@ -2312,6 +2357,11 @@ int vr_hip_volume_info(vr_ctx *c, vr_volume_info *out) {
 		out->bricked_bytes += copy_bytes(c, k);
 		if (k <= kCopyQuadYZ) { out->brick_planes |= 1u << k; out->brick_copies++; }
 	}
+	// the aligned run bricks: their own bits and their bytes (build times: vr_hip_run_aligned_info — this struct's size is pinned)
+	for (uint32_t k = kCopyRun7Z; k <= kCopyRun7Y; k++) {
+		if (c->copy[k]) { out->copies |= 1u << k; out->bricked_bytes += copy_bytes(c, k); }
+		if (c->copy_failed[k]) out->copies_refused |= 1u << k;
+	}
 	if (c->copy[kCopyRunZ]) out->run_copy |= 1u;
 	if (c->copy[kCopyRunY]) out->run_copy |= 2u;
 	if (c->copy[kCopyVoxel]) out->run_copy |= 4u;
@@ -2323,10 +2373,10 @@ int vr_hip_volume_info(vr_ctx *c, vr_volume_info *out) {
 int vr_hip_prepare(vr_ctx *c, uint32_t copies) {
 	if (c == nullptr) return VR_ERR_INVALID;
 	if (c->dim[0] == 0) return fail(c, VR_ERR_NOT_READY, "prepare before set_volume");
-	if (copies & ~((1u << kCopyKinds) - 1u)) return fail(c, VR_ERR_INVALID, "unknown copy bits");
+	if (copies & ~((1u << kCopySlots) - 1u)) return fail(c, VR_ERR_INVALID, "unknown copy bits");
 	VR_TRY(c, hipSetDevice(c->device));
 	int worst = VR_OK;
-	for (uint32_t k = 0; k < kCopyKinds; k++) {
+	for (uint32_t k = 0; k < kCopySlots; k++) {
 		if (!((copies >> k) & 1u) || c->copy[k] || !copy_in_policy(c, k)) continue;      // copies the policy does not have at this size are skipped
 		if (const int rc = need_linear(c, "set the volume again")) return rc;
 		c->copy_failed[k] = false;                   // an explicit request retries an earlier refusal
@@ -2339,10 +2389,10 @@ int vr_hip_prepare(vr_ctx *c, uint32_t copies) {
 
 int vr_hip_download_copy(vr_ctx *c, uint32_t kind, void *host_out, uint64_t capacity, uint64_t *bytes_out) {
 	if (c == nullptr) return VR_ERR_INVALID;
-	if (kind >= kCopyKinds) return fail(c, VR_ERR_INVALID, "unknown copy kind");
+	if (kind >= kCopySlots) return fail(c, VR_ERR_INVALID, "unknown copy kind");
 	if (c->copy[kind] == nullptr) return fail(c, VR_ERR_NOT_READY, "this brick copy is not resident (render a frame that reads it, or vr_hip_prepare)");
 	uint64_t bytes = copy_bytes(c, kind);
-	if (kind == kCopyRunZ || kind == kCopyRunY) bytes -= 16;     // the allocation's tail slack is not part of the copy
+	if (kind == kCopyRunZ || kind == kCopyRunY || kind == kCopyRun7Z || kind == kCopyRun7Y) bytes -= 16;     // the allocation's tail slack is not part of the copy
 	if (bytes_out) *bytes_out = bytes;
 	if (host_out == nullptr) return VR_OK;
 	if (capacity < bytes) return fail(c, VR_ERR_INVALID, "buffer too small for this copy");
@@ -2357,7 +2407,7 @@ int vr_hip_release_linear_copy(vr_ctx *c) {
 	if (c->dim[0] == 0) return fail(c, VR_ERR_NOT_READY, "release_linear_copy before set_volume");
 	if (c->vol == nullptr) return VR_OK;
 	bool any = false;
-	for (uint32_t k = 0; k < kCopyKinds; k++) any = any || c->copy[k] != nullptr;
+	for (uint32_t k = 0; k < kCopySlots; k++) any = any || c->copy[k] != nullptr;
 	if (!any || max_dim_of(c) > 2048u)
 		return fail(c, VR_ERR_INVALID, "the linear array is the only copy a render path can read (no brick copy resident: render a frame or call "
 		                               "vr_hip_prepare first; linear layout; or an edge above 2048)");

@@ -58,18 +58,23 @@
 			const bool along_y = LAYOUT == kLayoutRunY || alt_tile;
 			const uint32_t nx = a.dim_x, nr = along_y ? a.dim_y : a.dim_z, no = along_y ? a.dim_z : a.dim_y;
 			const uint32_t nbo = along_y ? a.nbz : a.nby;
-			const uint64_t slab = (uint64_t) a.nbx * nbo * kRunBrickBytes;
+			// the flavour of the copies (wave-uniform, vr_device.h): 36-byte runs of 8 cells, or aligned 32-byte runs of SEVEN cells — a
+			// cell's table entries say where it lies either way, and nothing below the barrier knows the difference
+			const bool aligned = a.run_aligned != 0u;
+			const uint32_t run_bytes = aligned ? kRun7Bytes : kRunBytes, brick_bytes = aligned ? kRun7BrickBytes : kRunBrickBytes;
+			const uint64_t slab = (uint64_t) a.nbx * nbo * brick_bytes;
 			const uint64_t copy_base = alt_tile ? a.alt_copy : (uint64_t) (uintptr_t) vol;
 #ifdef VR_BOUNDS_CHECK
 			if (t == 0) { bc_table_entries[0] = nx + 2 * kLutPad; bc_table_entries[1] = no + 2 * kLutPad; bc_table_entries[2] = nr + 2 * kLutPad; }
 #endif
 			for (uint32_t j = t; j < nr + 2 * kLutPad; j += kThreads) {
 				const uint32_t i = lut_cell_of(j, nr);
-				const uint64_t z0 = copy_base + (i >> 3) * slab + (i & 7u) * 4u;
+				const uint32_t brick = aligned ? i / kRun7Cells : i >> 3, in_run = aligned ? i - brick * kRun7Cells : i & 7u;
+				const uint64_t z0 = copy_base + brick * slab + in_run * 4u;
 				lut[2 * j] = (uint32_t) z0; lut[2 * j + 1] = (uint32_t) (z0 >> 32);
 			}
-			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, nx); lut[L::x_at + j] = (i >> 3) * kRunBrickBytes + run_cell_spread(0, i & 7u); }
-			for (uint32_t j = t; j < no + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, no); lut[L::y_at + j] = (i >> 3) * a.nbx * kRunBrickBytes + run_cell_spread(1, i & 7u); }
+			for (uint32_t j = t; j < nx + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, nx); lut[L::x_at + j] = (i >> 3) * brick_bytes + run_cell_order(0, i & 7u) * run_bytes; }
+			for (uint32_t j = t; j < no + 2 * kLutPad; j += kThreads) { const uint32_t i = lut_cell_of(j, no); lut[L::y_at + j] = (i >> 3) * a.nbx * brick_bytes + run_cell_order(1, i & 7u) * run_bytes; }
 		} else if constexpr (kUseLut) stage_brick_tables<BPV, ADDR, LAYOUT>(a, lut);      // (kUseLut: not the linear array, so L is LutCfg<ADDR>)
 		if (t <= VR_TF_SIZE) {
 			const f4 *tf4 = (const f4 *) tf_g;

@@ -85,6 +85,18 @@ class HipRenderer:
         1 quad-element windows, 2 voxel windows only (no second copy); speed and memory only."""
         self._check(self._L.vr_hip_set_column_copy(self._ctx, int(mode)), "set_column_copy")
 
+    def set_run_flavour(self, flavour=0):
+        """Run bricks of full-march frames: 0 automatic (default), 1 nine-element runs, 2 seven-cell aligned runs; speed and memory only."""
+        self._check(self._L.vr_hip_set_run_flavour(self._ctx, int(flavour)), "set_run_flavour")
+
+    def run_aligned_info(self):
+        """vr_run_aligned_info: dict(flavour, last_flavour (0 no run bricks, 1 nine-element, 2 aligned), copies, copies_refused, bytes, build_ms (z, y))."""
+        from .binding import VrRunAlignedInfo
+        info = VrRunAlignedInfo()
+        self._check(self._L.vr_hip_run_aligned_info(self._ctx, C.byref(info)), "run_aligned_info")
+        return {"flavour": int(info.flavour), "last_flavour": int(info.last_flavour), "copies": int(info.copies), "copies_refused": int(info.copies_refused),
+                "bytes": int(info.bytes), "build_ms": (float(info.build_ms[0]), float(info.build_ms[1]))}
+
     def set_tile_mapping(self, lane_map=-1, phase_x=0, phase_y=0):
         """Lane order inside a 4x4-pixel block (-1 automatic, 0 rows, 1 columns, 2 2x2 blocks) and tile-grid phase; speed only."""
         self._check(self._L.vr_hip_set_tile_mapping(self._ctx, int(lane_map), int(phase_x), int(phase_y)), "set_tile_mapping")
@@ -190,10 +202,12 @@ class HipRenderer:
 
     def last_launch(self):
         """What the last render launched: dict(layout, brick_plane, lane_map, phase_x, phase_y, clamp_fetch, tiles_x, tiles_y, ordered, straddle_permille,
-        column_voxels, column_shade_pairs, shadowed)."""
+        column_voxels, column_shade_pairs, shadowed) and, from vr_hip_run_aligned_info, run_flavour (0 no run bricks, 1 nine-element runs, 2 aligned runs)."""
         info = VrLaunchInfo()
         self._check(self._L.vr_hip_last_launch(self._ctx, C.byref(info)), "last_launch")
-        return {n: int(getattr(info, n)) for n, _ in VrLaunchInfo._fields_}
+        out = {n: int(getattr(info, n)) for n, _ in VrLaunchInfo._fields_}
+        out["run_flavour"] = self.run_aligned_info()["last_flavour"]
+        return out
 
     def tile_costs(self):
         """Cost map of the last frame rendered with set_tile_scheduling(2): [tiles_y, tiles_x] uint32, 64-cycle units per workgroup tile."""
