@@ -13,18 +13,11 @@ struct __attribute__((aligned(16))) DepthTables {
 	uint32_t esl[VR_ESL_VOLUME_SIZE];
 };
 
-// RaycasterBase.h:52-65 Raycaster::sample_data_esl on this unit's tables (vr_march.h block_empty reads the composite's)
-__device__ __forceinline__ bool depth_block_empty(const DepthTables &t, BlockIdx b) {
-	const uint32_t index = (b.z * VR_ESL_VOLUME_DIMS + b.y) & 0xffffu;
-	const uint32_t word = t.esl[index & (VR_ESL_VOLUME_SIZE - 1)];
-	return (word & (1u << (b.x & 31u))) != 0;
-}
-
 // the kernel-argument segment of depth_kernel as a struct: its arguments in order
 struct DepthKernelSegment { RayKernelArgs a; const void *vol; const float *tf; const uint32_t *esl; DepthArgs d; float *depth, *value, *alpha; };
 
 // Per pixel: the ray of raymarch_kernel (get_ray, intersect) under clip_segment (the identity clip when none is set), the composite's leaping
-// loop in its plain per-lane form, and on what is left the composite's sample sequence — k starts at the leapt kx, advances by repeated
+// loop in its plain per-lane form (vr_march.h leap_lane), and on what is left the composite's sample sequence — k starts at the leapt kx, advances by repeated
 // addition of ray_step, every position is fma(k, A, B) — in the section kernel's shape: kBatch samples are issued back to back before the
 // first is consumed behind a sched_barrier, in sample order.  Of the colour only the alpha channel is formed, with the composite's arithmetic:
 // the filtered lookup, or the slab's narrow / wide forms (d.slab, wave-uniform).  A lane that is finished — beyond ky, or terminated by
@@ -79,23 +72,7 @@ void depth_kernel(const RayKernelArgs a, const void *__restrict__ vol, const flo
 	const float step = a.p.ray_step;
 	bool alive = clip_segment(origin, dir, kx, ky) && ray.alive;
 
-	// -- empty space leaping (CPURenderer.cpp:18-25): the composite's loop, per lane
-	if (a.p.esl) {
-		f3 pt = march_point<SAMPLING>(origin, dir, kx);
-		bool probing = alive;
-		while (__builtin_amdgcn_ballot_w64(probing) != 0ull) {
-			if (probing) {
-				const BlockIdx blk = block_index(a, pt);
-				if (kx <= ky && depth_block_empty(lds, blk)) {
-					kx += leap_empty_space(a, blk, pt, dir);
-					kx += step;
-					pt = march_point<SAMPLING>(origin, dir, kx);
-				} else {
-					probing = false;
-				}
-			}
-		}
-	}
+	leap_lane<SAMPLING>(a, lds, origin, dir, kx, ky, alive);       // empty space leaping: the composite's loop, per lane (vr_march.h)
 	alive = alive && (kx <= ky);                    // a fully empty ray is a miss
 	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a sample: position 0, never live
 

@@ -445,7 +445,7 @@ void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
 // nine-element runs (false).  Measured (profiles/run7_ab.txt): the eight-view cycle 1.821 -> 1.747 ms per frame, the five run-brick views -2 .. -10 %.
 constexpr bool kRunAutoAligned = true;
 
-// ---- what launch_frame and launch_full_march_frame (further down) decide the same way ----------------------------------------------------
+// ---- what launch_frame and launch_full_march_frame (further down; its copy choice, full_march_copy, also serves build_shadow) decide the same way ----
 
 // the copy a frame of this layout reads (not asked for kLayoutLinear)
 uint32_t copy_kind_of(const RayKernelArgs &a, uint32_t sampling) {
@@ -599,6 +599,27 @@ int launch_timed(vr_ctx *c, RayKernelArgs &a, const vr_params *p, const Raymarch
 
 int build_shadow(vr_ctx *c);
 
+// the refusal of NEAREST by the five kinds of frame that are defined on the interpolated field, `what` in the message (launch_frame words its own)
+int need_interpolated(vr_ctx *c, const vr_params *p, const char *what) {
+	if (p->sampling == VR_SAMPLE_TRILINEAR || p->sampling == VR_SAMPLE_TRILINEAR_Q8) return VR_OK;
+	return fail(c, VR_ERR_INVALID, (std::string(what) + " is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8").c_str());
+}
+
+// the lighting and shadow words of the kernel argument, from what vr_hip_set_lighting and vr_hip_set_shadow left in the context (the light
+// grid is built by then: build_shadow)
+void lighting_shadow_args(const vr_ctx *c, RayKernelArgs &a) {
+	if (c->lighting_on) {
+		a.light_on = 1u; a.light_ka = c->lighting.ambient; a.light_kd = c->lighting.diffuse; a.light_ks = c->lighting.specular;
+		a.light_n = c->lighting.shininess_log2;
+	}
+	if (c->shadow_on) {
+		const uint32_t S = c->shadow.dims;
+		a.shadow_on = 1u; a.shadow_last = S - 2u; a.shadow_hs = 0.5f * (float) (S - 1u); a.shadow_max = (float) (S - 1u);
+		a.shadow_scale = c->shadow.strength * (1.0f / 255.0f); a.shadow_base = 1.0f - c->shadow.strength;
+		a.shadow_row = S; a.shadow_slab = S * S; a.shadow_q = (uint64_t) (uintptr_t) c->shadow_q;
+	}
+}
+
 // bd: the opaque layer of a backdrop frame (vr_hip_render_backdrop_device; device addresses), or NULL
 int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream, const vr_backdrop *bd = nullptr) {
 	// A shadowed frame (vr_hip_set_shadow): the light grid first, on the context's stream and synchronous like a brick copy's first use
@@ -626,16 +647,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	volume_args(c, p, a);
 	if (preint) a.slab_on = 1u;
 	if (bd != nullptr) { a.backdrop_on = 1u; a.backdrop_rgba = (uint64_t) (uintptr_t) bd->rgba; a.backdrop_depth = (uint64_t) (uintptr_t) bd->depth; }
-	if (lighting) {
-		a.light_on = 1u; a.light_ka = c->lighting.ambient; a.light_kd = c->lighting.diffuse; a.light_ks = c->lighting.specular;
-		a.light_n = c->lighting.shininess_log2;
-	}
-	if (shadow) {
-		const uint32_t S = c->shadow.dims;
-		a.shadow_on = 1u; a.shadow_last = S - 2u; a.shadow_hs = 0.5f * (float) (S - 1u); a.shadow_max = (float) (S - 1u);
-		a.shadow_scale = c->shadow.strength * (1.0f / 255.0f); a.shadow_base = 1.0f - c->shadow.strength;
-		a.shadow_row = S; a.shadow_slab = S * S; a.shadow_q = (uint64_t) (uintptr_t) c->shadow_q;
-	}
+	lighting_shadow_args(c, a);
 	const float half[3] = { a.half_x, a.half_y, a.half_z };
 	const ViewAxis va = view_axis(p, half);
 	transparent_corner_test(c, a);
@@ -1173,40 +1185,55 @@ int build_mip_bounds(vr_ctx *c) {
 	return VR_OK;
 }
 
-// One frame of a projection that marches every ray in full — MIP (vr_hip_render_mip) or isosurface (vr_hip_render_iso), `what` in
-// messages: the copy it reads — voxel bricks for NEAREST, quad bricks of the plane across the view (oct bricks for 2-byte voxels where a
-// DVR frame takes them) for TRILINEAR, the linear array under VR_LAYOUT_LINEAR —, the block maxima when esl is on, the tile mapping of a
-// DVR frame of the same view, one launch, one event pair.  launch(a, brick_copy, bounds or NULL) starts the kernel.
-template <class Launch>
-int launch_full_march_frame(vr_ctx *c, const vr_params *p, hipStream_t stream, const char *what, Launch &&launch) {
-	RayKernelArgs a;
-	volume_args(c, p, a);
-	a.force_wide = c->force_wide;
+// The copy a full-march frame of params p reads, and with it a.layout and a.brick_plane: voxel bricks for NEAREST, quad bricks for TRILINEAR
+// (oct bricks for 2-byte voxels where a DVR frame takes them), the linear array (NULL) under VR_LAYOUT_LINEAR; a copy that is refused falls
+// back to the first quad copy, then to whatever is resident.  plane_force is read as vr_ctx::brick_plane_force is: below 0 = the chunk plane
+// across a view along a volume axis, 0..2 = that plane (and no voxel bricks).  Also what build_shadow reads, for its own params and plane.
+const void *full_march_copy(vr_ctx *c, const vr_params *p, int32_t plane_force, RayKernelArgs &a) {
 	const float half[3] = { a.half_x, a.half_y, a.half_z };
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, nearest = p->sampling == VR_SAMPLE_NEAREST;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, nearest = p->sampling == VR_SAMPLE_NEAREST, forced = plane_force >= 0 && plane_force < (int32_t) kPlanes;
+	a.force_wide = c->force_wide;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	a.brick_plane = kPlaneXY;
-	if (bricked && nearest && copy_possible(c, kCopyVoxel) && c->force_wide != 1 && !(c->brick_plane_force >= 0 && c->brick_plane_force < (int32_t) kPlanes))
+	if (bricked && nearest && copy_possible(c, kCopyVoxel) && c->force_wide != 1 && !forced)
 		a.layout = kLayoutVoxel;
 	if (bricked && !nearest && !c->force_wide) {
 		uint32_t plane = kPlaneXY;
-		if (c->brick_plane_force >= 0 && c->brick_plane_force < (int32_t) kPlanes) plane = (uint32_t) c->brick_plane_force;
-		else if (c->brick_plane_force < 0) {             // along a volume axis: the chunk plane across it
+		if (forced) plane = (uint32_t) plane_force;
+		else if (plane_force < 0) {                      // along a volume axis: the chunk plane across it
 			const ViewAxis va = view_axis(p, half);
 			if (va.along) plane = plane_across(va.major);
 		}
 		if (copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
 	}
 	if (takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
-	const void *brick_copy = nullptr;
-	if (a.layout != kLayoutLinear) {
-		brick_copy = copy_for(c, copy_kind_of(a, p->sampling));
-		if (brick_copy == nullptr) {                     // refused or not buildable any more: the first quad copy, then whatever is resident
-			a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
-			brick_copy = copy_for(c, kCopyQuadXY);
-		}
-		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, false, a.layout);      // (a MIP frame never reads the run copies)
+	if (a.layout == kLayoutLinear) return nullptr;
+	const void *brick_copy = copy_for(c, copy_kind_of(a, p->sampling));
+	if (brick_copy == nullptr) {                         // refused or not buildable any more: the first quad copy, then whatever is resident
+		a.layout = kLayoutBricked; a.brick_plane = kPlaneXY;
+		brick_copy = copy_for(c, kCopyQuadXY);
 	}
+	if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, false, a.layout);      // (these frames never read the run copies)
+	return brick_copy;
+}
+
+// What a caller of launch_full_march_frame asks for: `what` names the frame in messages; block_maxima: params.esl skips fetches by the
+// volume's block maxima (MIP, isosurface) — without it the frame is planned and cached as the same frame with esl off; leaping: the kernel
+// argument carries the composite's leaping instead (params.esl, the divisor of params.esl_block_dims, the transparent-sample test: depth,
+// labelled); plane: a chunk plane that stands in for the context's forced plane, -1 = as the context says.
+struct FullMarch { const char *what; bool block_maxima, leaping; int32_t plane; };
+
+// One frame that marches every ray in full — MIP, isosurface, section, depth, labelled: the copy it reads (full_march_copy), the block maxima
+// where it skips by them, the tile mapping of a DVR frame of the same view, one launch, one event pair.  launch(a, brick_copy, bounds or
+// NULL) starts the kernel; it may add words of its own to a.
+template <class Launch>
+int launch_full_march_frame(vr_ctx *c, const vr_params *params, hipStream_t stream, const FullMarch &f, Launch &&launch) {
+	vr_params planned = *params;
+	if (!f.block_maxima) planned.esl = 0u;
+	const vr_params *p = &planned;
+	RayKernelArgs a;
+	volume_args(c, p, a);
+	const void *brick_copy = full_march_copy(c, p, f.plane >= 0 ? f.plane : c->brick_plane_force, a);
 	// Skipping and stopping by block maxima.  The grid is the volume's own (vr_hip_volume_minmax), whatever params.esl_block_* say.  Not
 	// for views so far away that fp32 sample coordinates are not exact to a small fraction of a cell (the condition under which DVR
 	// frames clamp every fetch, launch_frame): the TRILINEAR bound covers one voxel around the block of the sample's position.
@@ -1235,30 +1262,33 @@ int launch_full_march_frame(vr_ctx *c, const vr_params *p, hipStream_t stream, c
 	}
 	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
 	if (plan.reads_linear && c->vol == nullptr)
-		return fail(c, VR_ERR_NOT_READY, (std::string("this ") + what + " frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
+		return fail(c, VR_ERR_NOT_READY, (std::string("this ") + f.what + " frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                  "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again").c_str());
 	c->last_launch = vr_launch_info{ plan.reads_linear ? (uint32_t) kLayoutLinear : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, 0u, plan.tiles_x, plan.tiles_y, 0u, straddle, 0u, 0u, 0u };
 	c->last_run_flavour = 0u;                    // (these frames read no run bricks)
+	const uint8_t *bounds = a.p.esl ? c->mip_bounds : nullptr;
+	if (f.leaping) { a.p.esl = params->esl; esl_divisor(a, params->esl_block_dims); transparent_corner_test(c, a); }
 	uint64_t frame_seq = 0;
-	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch(a, brick_copy, a.p.esl ? c->mip_bounds : nullptr); });
+	return launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch(a, brick_copy, bounds); });
 }
 
 int launch_mip_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
-	return launch_full_march_frame(c, p, stream, "MIP", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
+	return launch_full_march_frame(c, p, stream, FullMarch{ "MIP", true, false, -1 }, [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
 		return launch_mip(a, c->vol, brick_copy, c->bpv, c->tf, bounds, dev_rgba, stream);
 	});
 }
 
 // One isosurface frame (include/vr_hip.h vr_hip_render_iso): what a MIP frame of the same view and sampling reads and maps, another kernel
 int launch_iso_frame(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, hipStream_t stream) {
-	return launch_full_march_frame(c, p, stream, "isosurface", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
+	return launch_full_march_frame(c, p, stream, FullMarch{ "isosurface", true, false, -1 }, [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *bounds) {
 		return launch_iso(a, c->vol, brick_copy, c->bpv, c->tf, bounds, iso->level, iso->refine, dev_rgba, dev_depth, stream);
 	});
 }
 
-// The light grid of a shadow (include/vr_hip.h vr_hip_set_shadow): S^3 bytes built by shadow_build_kernel from the copy a TRILINEAR MIP frame
-// along z reads — the quad bricks of plane (x,y), the oct bricks for 2-byte voxels, the linear array under VR_LAYOUT_LINEAR — on the context's
-// stream, synchronous like a brick copy's first use.  Waits for the context's frames first: one of them may still read the bytes it rewrites.
+// The light grid of a shadow (include/vr_hip.h vr_hip_set_shadow): S^3 bytes built by shadow_build_kernel from the copy full_march_copy gives
+// a TRILINEAR frame of zeroed params on plane (x,y) — its quad bricks, the oct bricks for 2-byte voxels (no perspective, no pixel pitch: at
+// most one cell per pixel), the linear array under VR_LAYOUT_LINEAR — on the context's stream, synchronous like a brick copy's first use.
+// Waits for the context's frames first: one of them may still read the bytes it rewrites.
 int build_shadow(vr_ctx *c) {
 	if (c->shadow_ready) return VR_OK;
 	const vr_shadow &sh = c->shadow;
@@ -1274,17 +1304,7 @@ int build_shadow(vr_ctx *c) {
 	p.sampling = VR_SAMPLE_TRILINEAR;            // (the selector's row; the builder takes Q8 as a flag)
 	RayKernelArgs a;
 	volume_args(c, &p, a);
-	a.force_wide = c->force_wide;
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED;
-	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
-	a.brick_plane = kPlaneXY;
-	if (bricked && c->bpv == 2 && copy_possible(c, kCopyOct) && c->brick_plane_force < 0 && c->force_wide != 1) a.layout = kLayoutOct;
-	const void *brick_copy = nullptr;
-	if (a.layout != kLayoutLinear) {
-		brick_copy = copy_for(c, copy_kind_of(a, p.sampling));
-		if (brick_copy == nullptr) { a.layout = kLayoutBricked; brick_copy = copy_for(c, kCopyQuadXY); }
-		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p.sampling, false, a.layout);
-	}
+	const void *brick_copy = full_march_copy(c, &p, (int32_t) kPlaneXY, a);      // (always plane (x,y), whatever plane is forced on the frames)
 	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
 	if (plan.reads_linear && c->vol == nullptr)
 		return fail(c, VR_ERR_NOT_READY, "the light grid of the shadow needs the linear array, which was released (vr_hip_release_linear_copy), and no resident brick copy serves it");
@@ -1314,8 +1334,7 @@ int build_shadow(vr_ctx *c) {
 // what the two isosurface entry points check beyond render_preamble
 int validate_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso) {
 	if (iso == nullptr) return fail(c, VR_ERR_INVALID, "iso is NULL");
-	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
-		return fail(c, VR_ERR_INVALID, "an isosurface is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (const int rc = need_interpolated(c, p, "an isosurface")) return rc;
 	if (!std::isfinite(iso->level)) return fail(c, VR_ERR_INVALID, "iso level must be finite");
 	if (iso->refine > 16u) return fail(c, VR_ERR_INVALID, "iso refine must be in 0..16");
 	return VR_OK;
@@ -1339,9 +1358,7 @@ int render_preamble(vr_ctx *c, const vr_params *p, const void *buffer, bool host
 int validate_backdrop(vr_ctx *c, const vr_params *p, const vr_backdrop *bd) {
 	if (bd == nullptr) return fail(c, VR_ERR_INVALID, "backdrop is NULL");
 	if (bd->rgba == nullptr || bd->depth == nullptr) return fail(c, VR_ERR_INVALID, "backdrop rgba / depth is NULL");
-	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
-		return fail(c, VR_ERR_INVALID, "a backdrop frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
-	return VR_OK;
+	return need_interpolated(c, p, "a backdrop frame");
 }
 
 // a context-owned device buffer of at least `bytes`: allocated on first use and grown (behind the context's frames, one of which may
@@ -1355,22 +1372,26 @@ int grow_buffer(vr_ctx *c, void **buffer, size_t &have, size_t bytes) {
 	return VR_OK;
 }
 
-// The hybrid (include/vr_hip.h): the isosurface frame into dev_rgba and the depth buffer, then the backdrop frame in place, on one stream
-int launch_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+// The two composed forms (include/vr_hip.h: the hybrid, the section in the volume): first(depth buffer) renders its frame into dev_rgba and
+// the depth buffer — the context's own when the caller gives none —, then the backdrop frame goes over it in place, on one stream
+template <class First>
+int launch_under_volume(vr_ctx *c, const vr_params *p, void *dev_rgba, void *dev_depth, hipStream_t stream, First &&first) {
 	if (dev_depth == nullptr) {
 		if (const int rc = grow_buffer(c, (void **) &c->hybrid_depth, c->hybrid_depth_bytes, (size_t) p->out_width * p->out_rows * sizeof(float))) return rc;
 		dev_depth = c->hybrid_depth;
 	}
-	if (const int rc = launch_iso_frame(c, p, iso, dev_rgba, dev_depth, stream)) return rc;
+	if (const int rc = first(dev_depth)) return rc;
 	const vr_backdrop layer = { dev_rgba, dev_depth };
 	return launch_frame(c, p, dev_rgba, stream, &layer);
+}
+int launch_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	return launch_under_volume(c, p, dev_rgba, dev_depth, stream, [&](void *depth) { return launch_iso_frame(c, p, iso, dev_rgba, depth, stream); });
 }
 
 // what the four section entry points check beyond render_preamble (include/vr_hip.h, step 10 of the section contract)
 int validate_section(vr_ctx *c, const vr_params *p, const vr_section *s) {
 	if (s == nullptr) return fail(c, VR_ERR_INVALID, "section is NULL");
-	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
-		return fail(c, VR_ERR_INVALID, "a section is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (const int rc = need_interpolated(c, p, "a section")) return rc;
 	for (int i = 0; i < 4; i++)
 		if (!std::isfinite(s->plane[i])) return fail(c, VR_ERR_INVALID, "section plane must be finite");
 	if (!std::isfinite(s->half_width) || !std::isfinite(s->window[0]) || !std::isfinite(s->window[1]))
@@ -1385,12 +1406,9 @@ int validate_section(vr_ctx *c, const vr_params *p, const vr_section *s) {
 	return VR_OK;
 }
 
-// One section frame (include/vr_hip.h vr_hip_render_section): what a clipped MIP frame of the same view and sampling reads and maps, with
-// esl off (every sample is fetched: no block maxima are built), another kernel.  volume_args has filled the clip words, the identity clip
-// when none is set.
+// One section frame (include/vr_hip.h vr_hip_render_section): what a clipped MIP frame of the same view and sampling reads and maps, without
+// its block maxima (every sample is fetched), another kernel.  volume_args has filled the clip words, the identity clip when none is set.
 int launch_section_frame(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, hipStream_t stream) {
-	vr_params q = *p;
-	q.esl = 0u;
 	SectionArgs sa;
 	memset(&sa, 0, sizeof sa);
 	for (int i = 0; i < 4; i++) sa.plane[i] = s->plane[i];
@@ -1399,50 +1417,36 @@ int launch_section_frame(vr_ctx *c, const vr_params *p, const vr_section *s, voi
 	sa.windowed = (s->window[0] == 0.0f && s->window[1] == 0.0f) ? 0u : 1u;
 	sa.window_lo = s->window[0];
 	sa.window_inv = sa.windowed ? 1.0f / (s->window[1] - s->window[0]) : 0.0f;
-	const int rc = launch_full_march_frame(c, &q, stream, "section", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+	const int rc = launch_full_march_frame(c, p, stream, FullMarch{ "section", false, false, -1 }, [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
 		return launch_section(a, sa, c->vol, brick_copy, c->bpv, c->tf, dev_rgba, dev_depth, stream);
 	});
 	if (rc == VR_OK) c->section_frames++;
 	return rc;
 }
 
-// The section in the volume (include/vr_hip.h): the section frame into dev_rgba and the depth buffer, then the backdrop frame in place, on one stream
-int launch_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, hipStream_t stream) {
-	if (dev_depth == nullptr) {
-		if (const int rc = grow_buffer(c, (void **) &c->hybrid_depth, c->hybrid_depth_bytes, (size_t) p->out_width * p->out_rows * sizeof(float))) return rc;
-		dev_depth = c->hybrid_depth;
-	}
-	if (const int rc = launch_section_frame(c, p, s, dev_rgba, dev_depth, stream)) return rc;
-	const vr_backdrop layer = { dev_rgba, dev_depth };
-	return launch_frame(c, p, dev_rgba, stream, &layer);
+int launch_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *sec, void *dev_rgba, void *dev_depth, hipStream_t stream) {
+	return launch_under_volume(c, p, dev_rgba, dev_depth, stream, [&](void *depth) { return launch_section_frame(c, p, sec, dev_rgba, depth, stream); });
 }
 
 // what the depth entry points check beyond render_preamble (include/vr_hip.h, step 10 of the depth contract)
 int validate_depth(vr_ctx *c, const vr_params *p, const vr_depth *d) {
 	if (d == nullptr) return fail(c, VR_ERR_INVALID, "depth is NULL");
-	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
-		return fail(c, VR_ERR_INVALID, "a depth frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (const int rc = need_interpolated(c, p, "a depth frame")) return rc;
 	if (d->mode > VR_DEPTH_MEAN) return fail(c, VR_ERR_INVALID, "depth mode must be in 0..2");
 	if (!std::isfinite(d->opacity) || d->opacity < 0.0f || d->opacity > 1.0f) return fail(c, VR_ERR_INVALID, "depth opacity must be finite and in [0, 1]");
 	if (d->mode == VR_DEPTH_FIRST && d->opacity == 0.0f) return fail(c, VR_ERR_INVALID, "a FIRST depth needs opacity > 0: a transparent sample would be a surface");
 	return VR_OK;
 }
 
-// One depth frame (include/vr_hip.h vr_hip_render_depth): what a clipped MIP frame of the same view and sampling reads and maps — the frame
-// goes through launch_full_march_frame with esl off, so no block maxima are built and the volume's own grid is not looked at —, then the
-// composite's leaping (params.esl, the ESL bits of vr_hip_set_transfer_fn, the block grid of the params) and its transparent-sample test are
-// put back into the kernel argument, and the classification is the context's.  volume_args has filled the clip words.
+// One depth frame (include/vr_hip.h vr_hip_render_depth): what a clipped MIP frame of the same view and sampling reads and maps — no block
+// maxima are built and the volume's own grid is not looked at —, with the composite's leaping (params.esl, the ESL bits of
+// vr_hip_set_transfer_fn, the block grid of the params) and its transparent-sample test in the kernel argument (FullMarch::leaping), and the
+// classification is the context's.  volume_args has filled the clip words.
 int launch_depth_frame(vr_ctx *c, const vr_params *p, const vr_depth *d, const vr_depth_out *out, hipStream_t stream) {
-	vr_params q = *p;
-	q.esl = 0u;
 	DepthArgs da;
 	da.opacity = d->opacity; da.mode = d->mode; da.slab = c->preint_on ? 1u : 0u; da.want_alpha = out->alpha != nullptr ? 1u : 0u;
-	const int rc = launch_full_march_frame(c, &q, stream, "depth", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
-		RayKernelArgs b = a;
-		b.p.esl = p->esl;
-		esl_divisor(b, p->esl_block_dims);
-		transparent_corner_test(c, b);
-		return launch_depth(b, da, c->vol, brick_copy, c->bpv, c->tf, c->esl, out->depth, out->value, out->alpha, stream);
+	const int rc = launch_full_march_frame(c, p, stream, FullMarch{ "depth", false, true, -1 }, [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		return launch_depth(a, da, c->vol, brick_copy, c->bpv, c->tf, c->esl, out->depth, out->value, out->alpha, stream);
 	});
 	if (rc == VR_OK) c->depth_frames++;
 	return rc;
@@ -1474,8 +1478,7 @@ const uint8_t *label_bricks_for(vr_ctx *c) {
 
 // what the two labelled entry points check beyond render_preamble (include/vr_hip.h, step 11 of the label contract)
 int validate_labelled(vr_ctx *c, const vr_params *p) {
-	if (p->sampling != VR_SAMPLE_TRILINEAR && p->sampling != VR_SAMPLE_TRILINEAR_Q8)
-		return fail(c, VR_ERR_INVALID, "a labelled frame is defined on the interpolated field: sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	if (const int rc = need_interpolated(c, p, "a labelled frame")) return rc;
 	if (c->preint_on)
 		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab between two samples with different labels has no single table entry "
 		                               "(vr_hip_set_preintegration(ctx, 0) switches it off)");
@@ -1483,36 +1486,19 @@ int validate_labelled(vr_ctx *c, const vr_params *p) {
 	return VR_OK;
 }
 
-// One labelled frame (include/vr_hip.h vr_hip_render_labelled): what a depth frame of the same view and sampling reads and maps — through
-// launch_full_march_frame with esl off —, then the composite's leaping, its transparent-sample test, the lighting and the shadow are put into
-// the kernel argument as launch_frame does.  1-byte voxels read the (x,y) quad copy whatever the view (unless a plane is forced): the label
-// bricks follow that order, and the kernel addresses them with the field's tables.  volume_args has filled the clip words.
+// One labelled frame (include/vr_hip.h vr_hip_render_labelled): what a depth frame of the same view and sampling reads and maps, with the
+// composite's leaping and its transparent-sample test in the kernel argument, and the lighting and the shadow as launch_frame puts them
+// there.  1-byte voxels read the (x,y) quad copy whatever the view (unless a plane is forced): the label bricks follow that order, and the
+// kernel addresses them with the field's tables.  volume_args has filled the clip words.
 int launch_labelled_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
 	if (c->shadow_on) { if (const int rc = build_shadow(c)) return rc; }
 	if (const int rc = ensure_label_table(c)) return rc;
-	vr_params q = *p;
-	q.esl = 0u;
-	const int32_t plane_force = c->brick_plane_force;
-	if (c->bpv == 1u && plane_force < 0) c->brick_plane_force = (int32_t) kPlaneXY;
-	const int rc = launch_full_march_frame(c, &q, stream, "labelled", [&](const RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
-		RayKernelArgs b = a;
-		b.p.esl = p->esl;
-		esl_divisor(b, p->esl_block_dims);
-		transparent_corner_test(c, b);
-		if (c->lighting_on) {
-			b.light_on = 1u; b.light_ka = c->lighting.ambient; b.light_kd = c->lighting.diffuse; b.light_ks = c->lighting.specular;
-			b.light_n = c->lighting.shininess_log2;
-		}
-		if (c->shadow_on) {
-			const uint32_t S = c->shadow.dims;
-			b.shadow_on = 1u; b.shadow_last = S - 2u; b.shadow_hs = 0.5f * (float) (S - 1u); b.shadow_max = (float) (S - 1u);
-			b.shadow_scale = c->shadow.strength * (1.0f / 255.0f); b.shadow_base = 1.0f - c->shadow.strength;
-			b.shadow_row = S; b.shadow_slab = S * S; b.shadow_q = (uint64_t) (uintptr_t) c->shadow_q;
-		}
-		const bool xy_quads = brick_copy != nullptr && c->bpv == 1u && b.layout == kLayoutBricked && b.brick_plane == kPlaneXY;
-		return launch_labelled(b, c->labels, xy_quads ? label_bricks_for(c) : nullptr, c->vol, brick_copy, c->bpv, c->tf, c->esl, c->label_table, dev_rgba, stream);
+	const FullMarch f = { "labelled", false, true, c->bpv == 1u && c->brick_plane_force < 0 ? (int32_t) kPlaneXY : -1 };
+	const int rc = launch_full_march_frame(c, p, stream, f, [&](RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		lighting_shadow_args(c, a);
+		const bool xy_quads = brick_copy != nullptr && c->bpv == 1u && a.layout == kLayoutBricked && a.brick_plane == kPlaneXY;
+		return launch_labelled(a, c->labels, xy_quads ? label_bricks_for(c) : nullptr, c->vol, brick_copy, c->bpv, c->tf, c->esl, c->label_table, dev_rgba, stream);
 	});
-	c->brick_plane_force = plane_force;
 	if (rc == VR_OK) c->labelled_frames++;
 	return rc;
 }
@@ -1538,6 +1524,42 @@ int frame_to_host(vr_ctx *c, uint8_t *host_rgba, size_t bytes, std::chrono::stea
 	VR_TRY(c, hipMemcpyAsync(host_rgba, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
 	VR_TRY(c, hipStreamSynchronize(c->stream));
 	take_total_time(c, t0);
+	return VR_OK;
+}
+
+// The two entry points of a feature frame (MIP, isosurface, hybrid, section, section in the volume, labelled), each written once: the
+// preamble, what the feature checks beyond it (validate()), then the launch.  The device one: launch(stream) on the caller's stream or the
+// context's.
+template <class Validate, class Launch>
+int render_to_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream, Validate &&validate, Launch &&launch) {
+	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
+	if (const int rc = validate()) return rc;
+	return launch(stream ? (hipStream_t) stream : c->stream);
+}
+// The host one: launch(depth buffer) into the window buffer on the context's stream, timed until the frame is in host memory.  depth: the
+// context's buffer the frame leaves its depth in, copied out where the caller gave host_depth — iso_depth, sized here before t0 and handed
+// to the launch only then, or hybrid_depth, which the composed forms grow and use by themselves (the launch gets NULL) —, NULL = no depth.
+template <class Validate, class Launch>
+int render_to_host(vr_ctx *c, const vr_params *p, uint8_t *host_rgba, float *host_depth, float *vr_ctx::*depth, Validate &&validate, Launch &&launch) {
+	int rc = render_preamble(c, p, host_rgba, true);
+	if (rc) return rc;
+	rc = validate();
+	if (rc) return rc;
+	const size_t pixels = (size_t) p->out_width * p->out_rows;
+	const bool sized_here = host_depth != nullptr && depth == &vr_ctx::iso_depth;
+	if (sized_here) { const int sized = size_host_depth(c); if (sized) return sized; }
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = launch(sized_here ? c->iso_depth : nullptr);
+	if (rc) return rc;
+	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->*depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	return frame_to_host(c, host_rgba, pixels * 4, t0);
+}
+const auto nothing_more = [] { return (int) VR_OK; };
+
+// the six vr_hip_*_frames getters
+int frames_counted(vr_ctx *c, uint64_t vr_ctx::*count, uint64_t *frames_out) {
+	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
+	*frames_out = c->*count;
 	return VR_OK;
 }
 
@@ -1832,11 +1854,7 @@ int vr_hip_set_lighting(vr_ctx *c, const vr_lighting *l) {
 	return VR_OK;
 }
 
-int vr_hip_lighting_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->lit_frames;
-	return VR_OK;
-}
+int vr_hip_lighting_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::lit_frames, frames_out); }
 
 int vr_hip_set_preintegration(vr_ctx *c, uint32_t on) {
 	if (c == nullptr) return VR_ERR_INVALID;
@@ -1848,11 +1866,7 @@ int vr_hip_set_preintegration(vr_ctx *c, uint32_t on) {
 	return VR_OK;
 }
 
-int vr_hip_preint_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->preint_frames;
-	return VR_OK;
-}
+int vr_hip_preint_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::preint_frames, frames_out); }
 
 int vr_hip_download_tf_integral(vr_ctx *c, float *host_out512) {
 	if (c == nullptr) return VR_ERR_INVALID;
@@ -1960,37 +1974,20 @@ int vr_hip_render(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 }
 
 int vr_hip_render_mip_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	return launch_mip_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, nothing_more, [&](hipStream_t on) { return launch_mip_frame(c, p, dev_rgba, on); });
 }
 
 int vr_hip_render_mip(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_mip_frame(c, p, c->fb, c->stream);
-	if (rc) return rc;
-	return frame_to_host(c, host_rgba, (size_t) p->out_width * p->out_rows * 4, t0);
+	return render_to_host(c, p, host_rgba, nullptr, nullptr, nothing_more, [&](void *) { return launch_mip_frame(c, p, c->fb, c->stream); });
 }
 
 int vr_hip_render_iso_device(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	if (const int rc = validate_iso(c, p, iso)) return rc;
-	return launch_iso_frame(c, p, iso, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_iso(c, p, iso); }, [&](hipStream_t on) { return launch_iso_frame(c, p, iso, dev_rgba, dev_depth, on); });
 }
 
 int vr_hip_render_iso(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t *host_rgba, float *host_depth) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	rc = validate_iso(c, p, iso);
-	if (rc) return rc;
-	const size_t pixels = (size_t) p->out_width * p->out_rows;
-	if (host_depth != nullptr) { const int sized = size_host_depth(c); if (sized) return sized; }
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_iso_frame(c, p, iso, c->fb, host_depth ? c->iso_depth : nullptr, c->stream);
-	if (rc) return rc;
-	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->iso_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-	return frame_to_host(c, host_rgba, pixels * 4, t0);
+	return render_to_host(c, p, host_rgba, host_depth, &vr_ctx::iso_depth, [&] { return validate_iso(c, p, iso); },
+	                      [&](void *depth) { return launch_iso_frame(c, p, iso, c->fb, depth, c->stream); });
 }
 
 // ---- backdrop and hybrid frames (include/vr_hip.h vr_backdrop) ----
@@ -2020,76 +2017,37 @@ int vr_hip_render_backdrop(vr_ctx *c, const vr_params *p, const vr_backdrop *hos
 }
 
 int vr_hip_render_hybrid_device(vr_ctx *c, const vr_params *p, const vr_iso *iso, void *dev_rgba, void *dev_depth, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	if (const int rc = validate_iso(c, p, iso)) return rc;
-	return launch_hybrid(c, p, iso, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_iso(c, p, iso); }, [&](hipStream_t on) { return launch_hybrid(c, p, iso, dev_rgba, dev_depth, on); });
 }
 
 int vr_hip_render_hybrid(vr_ctx *c, const vr_params *p, const vr_iso *iso, uint8_t *host_rgba, float *host_depth) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	rc = validate_iso(c, p, iso);
-	if (rc) return rc;
-	const size_t pixels = (size_t) p->out_width * p->out_rows;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_hybrid(c, p, iso, c->fb, nullptr, c->stream);       // (the context's own depth buffer)
-	if (rc) return rc;
-	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->hybrid_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-	return frame_to_host(c, host_rgba, pixels * 4, t0);
+	return render_to_host(c, p, host_rgba, host_depth, &vr_ctx::hybrid_depth, [&] { return validate_iso(c, p, iso); },
+	                      [&](void *depth) { return launch_hybrid(c, p, iso, c->fb, depth, c->stream); });
 }
 
-int vr_hip_backdrop_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->backdrop_frames;
-	return VR_OK;
-}
+int vr_hip_backdrop_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::backdrop_frames, frames_out); }
 
 // ---- section frames (include/vr_hip.h vr_section) ----
 
 int vr_hip_render_section_device(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	if (const int rc = validate_section(c, p, s)) return rc;
-	return launch_section_frame(c, p, s, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_section(c, p, s); }, [&](hipStream_t on) { return launch_section_frame(c, p, s, dev_rgba, dev_depth, on); });
 }
 
 int vr_hip_render_section(vr_ctx *c, const vr_params *p, const vr_section *s, uint8_t *host_rgba, float *host_depth) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	rc = validate_section(c, p, s);
-	if (rc) return rc;
-	const size_t pixels = (size_t) p->out_width * p->out_rows;
-	if (host_depth != nullptr) { const int sized = size_host_depth(c); if (sized) return sized; }
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_section_frame(c, p, s, c->fb, host_depth ? c->iso_depth : nullptr, c->stream);
-	if (rc) return rc;
-	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->iso_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-	return frame_to_host(c, host_rgba, pixels * 4, t0);
+	return render_to_host(c, p, host_rgba, host_depth, &vr_ctx::iso_depth, [&] { return validate_section(c, p, s); },
+	                      [&](void *depth) { return launch_section_frame(c, p, s, c->fb, depth, c->stream); });
 }
 
 int vr_hip_render_section_in_volume_device(vr_ctx *c, const vr_params *p, const vr_section *s, void *dev_rgba, void *dev_depth, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	if (const int rc = validate_section(c, p, s)) return rc;
-	return launch_section_in_volume(c, p, s, dev_rgba, dev_depth, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_section(c, p, s); }, [&](hipStream_t on) { return launch_section_in_volume(c, p, s, dev_rgba, dev_depth, on); });
 }
 
 int vr_hip_render_section_in_volume(vr_ctx *c, const vr_params *p, const vr_section *s, uint8_t *host_rgba, float *host_depth) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	rc = validate_section(c, p, s);
-	if (rc) return rc;
-	const size_t pixels = (size_t) p->out_width * p->out_rows;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_section_in_volume(c, p, s, c->fb, nullptr, c->stream);       // (the context's own depth buffer)
-	if (rc) return rc;
-	if (host_depth != nullptr) VR_TRY(c, hipMemcpyAsync(host_depth, c->hybrid_depth, pixels * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-	return frame_to_host(c, host_rgba, pixels * 4, t0);
+	return render_to_host(c, p, host_rgba, host_depth, &vr_ctx::hybrid_depth, [&] { return validate_section(c, p, s); },
+	                      [&](void *depth) { return launch_section_in_volume(c, p, s, c->fb, depth, c->stream); });
 }
 
-int vr_hip_section_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->section_frames;
-	return VR_OK;
-}
+int vr_hip_section_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::section_frames, frames_out); }
 
 // ---- depth frames of the composite and picking (include/vr_hip.h vr_depth) ----
 
@@ -2158,11 +2116,7 @@ int vr_hip_pick(vr_ctx *c, const vr_params *p, const vr_depth *d, uint32_t n, co
 	return VR_OK;
 }
 
-int vr_hip_depth_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->depth_frames;
-	return VR_OK;
-}
+int vr_hip_depth_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::depth_frames, frames_out); }
 
 // ---- label volumes (include/vr_hip.h vr_label_entry) ----
 
@@ -2221,27 +2175,14 @@ int vr_hip_set_label_table(vr_ctx *c, const vr_label_entry *entries, uint32_t co
 }
 
 int vr_hip_render_labelled_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
-	if (const int rc = render_preamble(c, p, dev_rgba, false)) return rc;
-	if (const int rc = validate_labelled(c, p)) return rc;
-	return launch_labelled_frame(c, p, dev_rgba, stream ? (hipStream_t) stream : c->stream);
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_labelled(c, p); }, [&](hipStream_t on) { return launch_labelled_frame(c, p, dev_rgba, on); });
 }
 
 int vr_hip_render_labelled(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
-	int rc = render_preamble(c, p, host_rgba, true);
-	if (rc) return rc;
-	rc = validate_labelled(c, p);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = launch_labelled_frame(c, p, c->fb, c->stream);
-	if (rc) return rc;
-	return frame_to_host(c, host_rgba, (size_t) p->out_width * p->out_rows * 4, t0);
+	return render_to_host(c, p, host_rgba, nullptr, nullptr, [&] { return validate_labelled(c, p); }, [&](void *) { return launch_labelled_frame(c, p, c->fb, c->stream); });
 }
 
-int vr_hip_labelled_frames(vr_ctx *c, uint64_t *frames_out) {
-	if (c == nullptr || frames_out == nullptr) return VR_ERR_INVALID;
-	*frames_out = c->labelled_frames;
-	return VR_OK;
-}
+int vr_hip_labelled_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::labelled_frames, frames_out); }
 
 #ifdef VR_MIP_STATS
 // probe build only (scripts/mip_probe.py): { samples, fetches issued } of the MIP frames that skipped since the last call

@@ -15,12 +15,6 @@ struct __attribute__((aligned(16))) LabelTables {
 	uint32_t esl[VR_ESL_VOLUME_SIZE];
 };
 
-__device__ __forceinline__ bool label_block_empty(const LabelTables &t, BlockIdx b) {       // (depth_block_empty on this unit's tables)
-	const uint32_t index = (b.z * VR_ESL_VOLUME_DIMS + b.y) & 0xffffu;
-	const uint32_t word = t.esl[index & (VR_ESL_VOLUME_SIZE - 1)];
-	return (word & (1u << (b.x & 31u))) != 0;
-}
-
 // the kernel-argument segment of label_kernel as a struct: its arguments in order
 struct LabelKernelSegment { RayKernelArgs a; const void *vol; const float *tf; const uint32_t *esl; LabelArgs d; const float *table; uint32_t *out; };
 
@@ -87,7 +81,7 @@ __device__ __forceinline__ float label_cue(const void *vol, const RayKernelArgs 
 }
 
 // Per pixel: the ray of raymarch_kernel (get_ray, intersect) under clip_segment (the identity clip when none is set), the composite's leaping
-// loop in its plain per-lane form, and on what is left the composite's sample sequence — k starts at the leapt kx, advances by repeated
+// loop in its plain per-lane form (vr_march.h leap_lane), and on what is left the composite's sample sequence — k starts at the leapt kx, advances by repeated
 // addition of ray_step, every position is fma(k, A, B) — in the depth kernel's shape: kBatch samples are issued back to back before the first
 // is consumed behind a sched_barrier, in sample order.  A lane that is finished — beyond ky, or terminated by acc.w > ray_threshold inside a
 // batch already issued — stays ON its last sample and fetches it again (every fetch clamps its cell: in bounds whatever k is); it is composited
@@ -156,23 +150,7 @@ void label_kernel(const RayKernelArgs a, const void *__restrict__ vol, const flo
 	const float step = a.p.ray_step;
 	bool alive = clip_segment(origin, dir, kx, ky) && ray.alive;
 
-	// -- empty space leaping (CPURenderer.cpp:18-25): the composite's loop, per lane
-	if (a.p.esl) {
-		f3 pt = march_point<SAMPLING>(origin, dir, kx);
-		bool probing = alive;
-		while (__builtin_amdgcn_ballot_w64(probing) != 0ull) {
-			if (probing) {
-				const BlockIdx blk = block_index(a, pt);
-				if (kx <= ky && label_block_empty(lds, blk)) {
-					kx += leap_empty_space(a, blk, pt, dir);
-					kx += step;
-					pt = march_point<SAMPLING>(origin, dir, kx);
-				} else {
-					probing = false;
-				}
-			}
-		}
-	}
+	leap_lane<SAMPLING>(a, lds, origin, dir, kx, ky, alive);       // empty space leaping: the composite's loop, per lane (vr_march.h)
 	alive = alive && (kx <= ky);                    // a fully empty ray is a miss
 	if (!alive) { kx = 0.0f; ky = 0.0f; origin = mk3(0.0f, 0.0f, 0.0f); dir = origin; }      // lanes without a sample: position 0, never live
 

@@ -466,8 +466,9 @@ __device__ __forceinline__ BlockIdx block_index(const RayKernelArgs &a, f3 pos) 
 	return b;
 }
 
-// RaycasterBase.h:52-65 Raycaster::sample_data_esl — bit set = block is empty; table read from LDS
-__device__ __forceinline__ bool block_empty(const LdsTables &t, BlockIdx b) {
+// RaycasterBase.h:52-65 Raycaster::sample_data_esl — bit set = block is empty; table read from LDS (Tables: a unit's struct with the ESL words)
+template <class Tables>
+__device__ __forceinline__ bool block_empty(const Tables &t, BlockIdx b) {
 	const uint32_t index = (b.z * VR_ESL_VOLUME_DIMS + b.y) & 0xffffu;          // `unsigned short index` in the reference
 	const uint32_t word = t.esl[index & (VR_ESL_VOLUME_SIZE - 1)];
 	return (word & (1u << (b.x & 31u))) != 0;
@@ -689,6 +690,29 @@ __device__ __forceinline__ bool clip_segment(f3 origin, f3 dir, float &kx, float
 	else if (dn < 0) ky = flmin(ky, -on / dn);
 	else kept = on >= 0;                            // the ray runs inside the plane's direction (no plane: 0 >= 0)
 	return kept && (kx < ky) && (ky > 0);
+}
+
+// -- empty space leaping (CPURenderer.cpp:18-25): the composite's loop in its plain per-lane form, on the ESL words of the unit's tables
+//    (depth_kernel, label_kernel).  What else these kernels and section_kernel repeat — the pixel prologue, the reset of lanes without a sample
+//    with A / B, the batch issue — stays written out in them: as functions each changed the machine code of some row (scripts/kernel_diff.py).
+template <int SAMPLING, class Tables>
+__device__ __forceinline__ void leap_lane(const RayKernelArgs &a, const Tables &t, f3 origin, f3 dir, float &kx, float ky, bool alive) {
+	if (!a.p.esl) return;
+	const float step = a.p.ray_step;
+	f3 pt = march_point<SAMPLING>(origin, dir, kx);
+	bool probing = alive;
+	while (__builtin_amdgcn_ballot_w64(probing) != 0ull) {
+		if (probing) {
+			const BlockIdx blk = block_index(a, pt);
+			if (kx <= ky && block_empty(t, blk)) {
+				kx += leap_empty_space(a, blk, pt, dir);
+				kx += step;
+				pt = march_point<SAMPLING>(origin, dir, kx);
+			} else {
+				probing = false;
+			}
+		}
+	}
 }
 
 // -- the factor of a shadowed composite frame (include/vr_hip.h vr_hip_set_shadow) for the sample at model-space point
