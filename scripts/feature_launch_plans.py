@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""feature_launch_plans.py [--check] — prints the JSON of tests/golden/feature_launch_plans.json: what vr_hip_last_launch reports for every frame
-tests/test_gpu_feature_plans.py enumerates (record() there), on the library of this tree.  The fixture pins what the host decided BEFORE a
-change of the launchers: run it in a checkout of the commit before the change (with that test module copied in), not on the code under
-test.  --check runs the enumeration twice in two fresh contexts and exits 1 if the two differ in any field (the plan is host arithmetic)."""
+"""feature_launch_plans.py [--check] [test module] — prints the JSON of a launch-plan fixture under tests/golden/: what record() of the
+test module enumerates, on the library of this tree.  test_gpu_feature_plans (the default) prints feature_launch_plans.json,
+test_gpu_composite_plans prints composite_launch_plans.json.  A fixture pins what the host decided BEFORE a change of the launchers: run
+this in a checkout of the commit before the change (with the test module and tests/plan_helpers.py copied in), not on the code under test.
+--check runs the enumeration twice in two fresh contexts and exits 1 if the two differ in any field (the plan is host arithmetic)."""
 import importlib
-import json
 import os
 import sys
 
@@ -12,26 +12,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 
-def once(vr, plans):
-    gpu = vr.HipRenderer(0)
-    try:
-        return plans.record(vr, gpu)
-    finally:
-        gpu.close()
-
-
 def main():
     import torch  # noqa: F401  (loads the process's HIP runtime first)
-    vr = importlib.import_module("volume-rendering_amd")
-    plans = importlib.import_module("test_gpu_feature_plans")
-    first = once(vr, plans)
-    if "--check" in sys.argv[1:]:
-        second = once(vr, plans)
-        differing = [k for k in first["plans"] if first["plans"][k] != second["plans"].get(k)]
-        if differing or len(first["plans"]) != len(second["plans"]):
-            sys.exit(f"two runs differ in {len(differing)} plans: {differing[:8]}")
-    rows = ",\n".join(f"  {json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" for k, v in first["plans"].items())      # one plan per line
-    sys.stdout.write(f'{{"fields": {json.dumps(first["fields"])},\n "plans": {{\n{rows}\n }}}}\n')
+    from plan_helpers import print_plans
+    modules = [a for a in sys.argv[1:] if not a.startswith("--")]
+    print_plans(importlib.import_module("volume-rendering_amd"), modules[0] if modules else "test_gpu_feature_plans", "--check" in sys.argv[1:])
 
 
 if __name__ == "__main__":

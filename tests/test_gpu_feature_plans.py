@@ -14,50 +14,21 @@ import pytest
 from gpu_feature import load, reset_context
 from helpers import GOLDEN_DIR
 from mip_helpers import ramp_tf
+from plan_helpers import FIELDS, LIGHT, VOXELS, assert_same, axis_view, frame_params, launched, volume
 
 pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(GOLDEN_DIR, "feature_launch_plans.json")
-FIELDS = ("layout", "brick_plane", "lane_map", "phase_x", "phase_y", "clamp_fetch", "tiles_x", "tiles_y", "ordered", "straddle_permille", "column_voxels",
-          "column_shade_pairs", "shadowed", "run_flavour")
 WINDOW = (48, 32)
-SHAPE = (16, 20, 24)                             # z, y, x: ragged, no edge a multiple of the brick edge but z
-VOXELS = ("u8", "u16")
 KINDS = {"mip": (0, 1, 2), "iso": (1, 2), "section": (1, 2), "depth": (1, 2), "labelled": (1, 2)}      # kind -> its legal sampling modes
 CLIP = dict(box_min=(-0.75, -1.0, -0.5), box_max=(0.5, 0.75, 1.0), plane=(0.6, 0.0, 0.8, 0.1))
-LIGHT = (0.5, -1.0, 3.0)
-
-
-def volume(voxels):
-    rng = np.random.default_rng(11)
-    raw = rng.integers(0, 256, SHAPE)
-    return raw.astype(np.uint8) if voxels == "u8" else (raw * 257).astype(np.uint16)
 
 
 def views(vr):
     """orthogonal along x, y and z (built by hand: exact zeros), one oblique orthogonal pose, one perspective view along z"""
-    out = {}
-    for name, axis, perspective in (("x", 0, 0), ("y", 1, 0), ("z", 2, 0), ("persp_z", 2, 1)):
-        v = vr.VrView()
-        v.width, v.height, v.perspective = WINDOW[0], WINDOW[1], perspective
-        for j in range(3):
-            v.origin[j] = v.direction[j] = v.right_plane[j] = v.up_plane[j] = 0.0
-            v.light_pos[j] = LIGHT[j]
-        v.direction[axis], v.origin[axis] = 1.0, -3.0 if perspective else -2.0
-        v.right_plane[(axis + 1) % 3] = v.up_plane[(axis + 2) % 3] = 0.0125 if perspective else 0.045
-        out[name] = v
+    out = {name: axis_view(vr, WINDOW, axis, perspective) for name, axis, perspective in (("x", 0, 0), ("y", 1, 0), ("z", 2, 0), ("persp_z", 2, 1))}
     out["oblique"] = vr.custom_view(WINDOW[0], WINDOW[1], 0, (-45.0, -45.0, 0.0), 2.0)
     return out
-
-
-def frame_params(vr, view, sampling, esl):
-    p = vr.VrParams()
-    p.view = view
-    p.ray_step, p.ray_threshold, p.light_kd = 0.05, 0.95, 0.7
-    p.esl, p.esl_block_dims, p.sampling = esl, 3, sampling
-    for j in range(3):
-        p.esl_block_size[j] = (0.25, 0.3, 0.375)[j]
-    return vr.whole_frame(p)
 
 
 def plan(vr, gpu, kind, p, top):
@@ -75,8 +46,7 @@ def plan(vr, gpu, kind, p, top):
             gpu.render_labelled(p)
     except vr.VrError as e:
         return ["refused", e.code]
-    launched = gpu.last_launch()
-    return [launched[f] for f in FIELDS]
+    return launched(gpu)
 
 
 def load_volume(gpu, voxels):
@@ -160,13 +130,6 @@ def fixture():
 def state_off_afterwards(vr, gpu):
     yield
     reset_context(vr, gpu)
-
-
-def assert_same(got, fixture, prefix):
-    want = {k: v for k, v in fixture.items() if k.startswith(prefix)}
-    assert set(got) == set(want), sorted(set(got) ^ set(want))[:8]
-    wrong = [(k, got[k], want[k]) for k in sorted(got) if got[k] != want[k]]
-    assert not wrong, (len(wrong), wrong[:8])
 
 
 @pytest.mark.parametrize("voxels", VOXELS)

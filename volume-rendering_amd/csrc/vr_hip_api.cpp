@@ -92,7 +92,7 @@ struct vr_ctx {
 	uint32_t tile_scheduling = 1;           // vr_hip_set_tile_scheduling: 0 = tile = workgroup id, 1 = measured-cost order, 2 = cost map
 	vr_launch_info last_launch = {};        // vr_hip_last_launch
 	uint32_t *cost_map = nullptr;           // mode 2: what every tile of the LAST frame cost (vr_hip_read_tile_costs)
-	uint32_t cost_map_capacity = 0, cost_map_tiles_x = 0, cost_map_tiles_y = 0;
+	size_t cost_map_bytes = 0; uint32_t cost_map_tiles_x = 0, cost_map_tiles_y = 0;
 	bool oct_always = false;                // vr_hip_set_brick_plane(5): 2-byte voxels read the oct bricks for every view (testing)
 	// feeders scratch
 	uint8_t *minmax = nullptr; unsigned long long *hist = nullptr;
@@ -172,6 +172,7 @@ bool copy_possible(const vr_ctx *c, uint32_t kind);
 uint64_t copy_bytes(const vr_ctx *c, uint32_t kind);
 hipError_t drain(vr_ctx *c);
 const void *copy_for(vr_ctx *c, uint32_t kind);
+int grow_buffer(vr_ctx *c, void **buffer, size_t &have, size_t bytes);
 
 uint32_t max_dim_of(const vr_ctx *c) { return std::max(c->dim[0], std::max(c->dim[1], c->dim[2])); }
 
@@ -620,69 +621,19 @@ void lighting_shadow_args(const vr_ctx *c, RayKernelArgs &a) {
 	}
 }
 
-// bd: the opaque layer of a backdrop frame (vr_hip_render_backdrop_device; device addresses), or NULL
-int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream, const vr_backdrop *bd = nullptr) {
-	// A shadowed frame (vr_hip_set_shadow): the light grid first, on the context's stream and synchronous like a brick copy's first use
-	const bool shadow = c->shadow_on;
-	if (shadow) {
-		if (p->sampling == VR_SAMPLE_NEAREST)
-			return fail(c, VR_ERR_INVALID, "a shadow is set: the light grid and its factor are defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
-			                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_shadow(ctx, NULL) switches the shadow off)");
-		if (const int rc = build_shadow(c)) return rc;
-	}
-	// A gradient-lit frame (vr_hip_set_lighting) reads what a clipped frame reads too, and its kernels take the shadow as an argument
-	const bool lighting = c->lighting_on;
-	if (lighting && p->sampling == VR_SAMPLE_NEAREST)
-		return fail(c, VR_ERR_INVALID, "a lighting is set: the gradient is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
-		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_lighting(ctx, NULL) switches the lighting off)");
-	// A pre-integrated frame (vr_hip_set_preintegration) reads what a clipped frame reads as well; clip, shadow and lighting compose with it
-	const bool preint = c->preint_on;
-	if (preint && p->sampling == VR_SAMPLE_NEAREST)
-		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab lies between two samples of the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
-		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_preintegration(ctx, 0) switches it off)");
-	// A backdrop frame (vr_hip_render_backdrop) reads what a clipped frame reads as well; clip, shadow, lighting and pre-integration compose with it
-	if (bd != nullptr && p->sampling == VR_SAMPLE_NEAREST)
-		return fail(c, VR_ERR_INVALID, "a backdrop frame is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
-	RayKernelArgs a;
-	volume_args(c, p, a);
-	if (preint) a.slab_on = 1u;
-	if (bd != nullptr) { a.backdrop_on = 1u; a.backdrop_rgba = (uint64_t) (uintptr_t) bd->rgba; a.backdrop_depth = (uint64_t) (uintptr_t) bd->depth; }
-	lighting_shadow_args(c, a);
-	const float half[3] = { a.half_x, a.half_y, a.half_z };
-	const ViewAxis va = view_axis(p, half);
-	transparent_corner_test(c, a);
-	{   // fp32 sample coordinates that are not exact to a fraction of a cell: clamp every sample
-		const float omax = max_abs_origin(p), nmax = (float) max_dim_of(c);
-		a.clamp_fetch = fetch_coordinates_exact(c, p) ? 0u : 1u;
-		// intersect() replaces a direction component that is exactly 0 by 1e-5 (RaycasterBase.h:33-35): a ray whose origin lies
-		// up to ky * 1e-5 outside a face of the cube is then still reported as a hit and marches at that constant out-of-cube
-		// coordinate, ky * 1e-5 * N/2 texels beyond the face.  ky <= sqrt(3) * (omax + 1) for |direction| >= 1 (orthogonal: unit
-		// direction; perspective: a unit vector plus in-plane offsets).  Keep that below 1/8 texel, else clamp every sample.
-		if (1.7321f * (omax + 1.0f) * 1e-5f * nmax * 0.5f >= 0.125f) a.clamp_fetch = 1u;
-		// The unclamped march fetches up to kDepth steps past a ray's exit point (software pipeline): that must stay inside the
-		// kLutPad repeated edge entries of the address tables.  The reference's longest step is 1.666 cells (RaycasterBase.cpp:90).
-		// A step moves a ray by ray_step * |direction component| * N/2 cells along an axis; perspective directions are not
-		// normalised (direction + right * fx + up * fy, ViewBase.h:29-31), so the bound is taken over the whole frame.
-		{
-			float advance = 0.0f;
-			for (int i = 0; i < 3; i++) {
-				float d = std::fabs(p->view.direction[i]);
-				if (p->view.perspective)
-					d += std::fabs(p->view.right_plane[i]) * (0.5f * (float) p->view.width + 1.0f) + std::fabs(p->view.up_plane[i]) * (0.5f * (float) p->view.height + 1.0f);
-				advance = std::fmax(advance, d * half[i]);
-			}
-			if (!((float) kOverrunSteps * p->ray_step * advance + 1.5f <= (float) kLutPad)) a.clamp_fetch = 1u;
-		}
-		if (c->force_clamp_fetch & 1u) a.clamp_fetch = 1u;
-		auto pow2 = [](uint32_t n) { return n != 0 && (n & (n - 1)) == 0; };
-		a.near_scaled = (pow2(c->dim[0]) && pow2(c->dim[1]) && pow2(c->dim[2]) && !(c->force_clamp_fetch & 2u)) ? 1u : 0u;
-	}
-	a.force_wide = c->force_wide;
-	// (a shadowed frame reads what a clipped frame reads: its kernels are the clipped ones with one more fetch per dense sample)
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = c->clip_on || shadow || lighting || preint || bd != nullptr;
+// What the copy steps of launch_frame hand on.  run_layout: which run copy a run-brick frame reads — runs along z unless the view marches along z;
+// hit, straddle: the cached tile mapping (none under a forced mapping and for a backdrop frame) and the straddle figure; dual_stage, measured /
+// alternating choice only: -1 no; 0..3: the four frames before; 4: per-tile choice in use
+struct CopyChoice { uint32_t run_layout = kLayoutRun, straddle = 1000u; vr_ctx::MapEntry *hit = nullptr; bool dual_analytic = false, shade_pairs = false; int dual_stage = -1; };
+// (a shadowed, lit, pre-integrated or backdrop frame reads what a clipped frame reads: its kernels are the clipped ones with more per dense sample)
+bool clipped_frame(const vr_ctx *c, const RayKernelArgs &a) { return c->clip_on || c->shadow_on || c->lighting_on || c->preint_on || a.backdrop_on; }
+
+// a.layout and a.brick_plane by view, sampling mode and the forced planes, then the tile mapping, which may still move the frame to another copy
+int choose_composite_copy(vr_ctx *c, const vr_params *p, const ViewAxis &va, RayKernelArgs &a, CopyChoice &choice) {
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED, clip = clipped_frame(c, a);
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	bool run_candidate = false, run_if_unaligned = false, dual_candidate = false;
-	uint32_t run_layout = kLayoutRun;        // which run copy a run-brick frame reads: runs along z unless the view marches along z
+	vr_ctx::MapEntry *&hit = choice.hit;
 	// Which brick copy: the one whose 16-byte chunks lie in the plane perpendicular to the view's dominant axis, so that the
 	// pixels of a lane quad — neighbours on the screen — are neighbours inside a chunk (TRILINEAR; NEAREST keeps (x,y)).
 	// Copies are built on first use (copy_for, further down); copy_possible asks without building.
@@ -693,14 +644,14 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		else {
 			// only for views (or, in perspective, central directions) along a volume axis: measured on the oblique benchmark pose the
 			// (x,y) copy is as good as any (4.1 ms against 4.1 - 5.1 ms), along an axis the perpendicular plane wins by 8 - 16 %
-			if (va.major == 2 && copy_possible(c, kCopyRunY)) run_layout = kLayoutRunY;     // runs across the march, never along it
+			if (va.major == 2 && copy_possible(c, kCopyRunY)) choice.run_layout = kLayoutRunY;     // runs across the march, never along it
 			if (va.along) {
 				plane = plane_across(va.major);
 				// Perspective along x or y: the pixel pitch grows from 0.4 to 1.1 cells along the march, most lane quads straddle
 				// chunks, and the run bricks — whose runs (along z) then lie across the march — are faster (measured 2.08 / 2.18 ms
 				// against 2.49 / 2.51 ms on the benchmark poses).  Along z the runs lie along the march and the quad copy wins
 				// (2.48 against 2.99 ms).  Orthogonal views along an axis are decided below, from how well their quads can be aligned.
-				if (p->view.perspective && (plane != kPlaneXY || run_layout == kLayoutRunY)) run_candidate = true;
+				if (p->view.perspective && (plane != kPlaneXY || choice.run_layout == kLayoutRunY)) run_candidate = true;
 				else if (!p->view.perspective) run_if_unaligned = true;
 			} else {
 				run_candidate = true;       // not along an axis: lane quads straddle chunks whatever the plane -> one 8-byte gather
@@ -716,18 +667,17 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		if (plane < kPlanes && copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
 		else if (plane == kPlanes && copy_possible(c, kCopyRunZ)) a.layout = kLayoutRun;               // forced: 3 = runs along z, 4 = runs along y
 		else if (plane == kPlanes + 1 && copy_possible(c, kCopyRunY)) a.layout = kLayoutRunY;
-		if (run_candidate && copy_possible(c, run_layout == kLayoutRunY ? kCopyRunY : kCopyRunZ)) a.layout = run_layout;
+		if (run_candidate && copy_possible(c, choice.run_layout == kLayoutRunY ? kCopyRunY : kCopyRunZ)) a.layout = choice.run_layout;
 	}
 	// NEAREST: the voxel bricks (one voxel per element) unless a quad copy is forced (testing) or a 64-bit path is
 	if (p->sampling == VR_SAMPLE_NEAREST && bricked && copy_possible(c, kCopyVoxel) && c->brick_plane_force < 0 && c->force_wide != 1)
 		a.layout = kLayoutVoxel;
+	const float half[3] = { a.half_x, a.half_y, a.half_z };
 	if (takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
 	esl_divisor(a, p->esl_block_dims);
 
-	vr_ctx::MapEntry *hit = nullptr;
-	uint32_t uncached_straddle = 1000u;
 	if (c->tile_lane_map >= 0) { a.lane_map = (uint32_t) c->tile_lane_map; a.phase_x = c->tile_phase_x; a.phase_y = c->tile_phase_y; }
-	else if (bd != nullptr) uncached_straddle = choose_tile_mapping(a);      // a backdrop frame leaves the cached mappings alone: they are keyed by vr_params, and it reads other copies
+	else if (a.backdrop_on) choice.straddle = choose_tile_mapping(a);      // a backdrop frame leaves the cached mappings alone: they are keyed by vr_params, and it reads other copies
 	else {
 		for (uint32_t i = 0; i < c->map_cached && hit == nullptr; i++)
 			if (memcmp(&c->map_cache[i].p, p, sizeof *p) == 0 && memcmp(c->map_cache[i].dim, c->dim, sizeof c->dim) == 0) hit = &c->map_cache[i];
@@ -746,10 +696,11 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			hit->lane_map = a.lane_map; hit->phase_x = a.phase_x; hit->phase_y = a.phase_y;
 		}
 		a.lane_map = hit->lane_map; a.phase_x = hit->phase_x; a.phase_y = hit->phase_y;
+		choice.straddle = hit->straddle_permille;
 		// An orthogonal view along an axis whose pixels sit exactly on cell boundaries can carry rounding noise in its direction
 		// (pose (180,90,0): components of 4e-8) that moves boundary pixels to the other neighbour part-way along the ray and
 		// differently across the frame: no phase aligns it.  Measured on that pose: 3.18 ms with the run bricks against 3.71 ms.
-		if (run_if_unaligned && hit->straddle_permille > 150u && copy_possible(c, run_layout == kLayoutRunY ? kCopyRunY : kCopyRunZ)) a.layout = run_layout;
+		if (run_if_unaligned && hit->straddle_permille > 150u && copy_possible(c, choice.run_layout == kLayoutRunY ? kCopyRunY : kCopyRunZ)) a.layout = choice.run_layout;
 	}
 	// Per-tile choice between the two run copies (kLayoutRunDual, vr_device.h): full-march frames only (with leaping or early
 	// termination the rays are short and the tile order is what matters), never for the clamping instantiation (its clamp bounds are
@@ -758,71 +709,76 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// — the first frame of a new view already reads the right copies.  vr_hip_set_brick_plane(6) keeps the round-3 MEASURED choice
 	// (frames 0-3 of a parameter set on one copy each, the last two recording tile costs, choice kernel, per-block choice from frame 4 on)
 	// as the validator of that rule; 7 = alternating tiles (testing: the copies meet at tile boundaries all over the frame).
-	bool dual_analytic = false, shade_pairs = false;
-	int dual_stage = -1;                                 // measured / alternating choice only: -1 no; 0..3: the four frames before; 4: per-tile choice in use
 	const bool dual_test = c->brick_plane_force == (int) kPlanes + 4, dual_measured = c->brick_plane_force == (int) kPlanes + 3;
 	if (dual_candidate && is_run_layout(a.layout) && !p->esl && p->ray_threshold >= 1.0f && !a.clamp_fetch && c->bpv == 1 &&
 	    copy_possible(c, kCopyRunZ) && copy_possible(c, kCopyRunY)) {
 		if (dual_test || dual_measured) {
 			if (hit != nullptr && c->tile_scheduling == 1 && !VR_ORDER_ALWAYS) {
-				dual_stage = dual_test ? 4 : (int) hit->dual_state;
-				a.layout = dual_stage == 4 ? kLayoutRunDual : ((dual_stage & 1) ? kLayoutRunY : kLayoutRun);
+				choice.dual_stage = dual_test ? 4 : (int) hit->dual_state;
+				a.layout = choice.dual_stage == 4 ? kLayoutRunDual : ((choice.dual_stage & 1) ? kLayoutRunY : kLayoutRun);
 			}
 		} else {
-			dual_analytic = true;
+			choice.dual_analytic = true;
 			a.layout = kLayoutRunDual;
 		}
 	}
-	// Column windows (kLayoutColumn, vr_device.h): full-march TRILINEAR frames of ORTHOGONAL views along a volume axis — every ray stays in
-	// one cell column (at most one cell flip per lateral axis: the direction's other components are rounding noise), all rays share the k
-	// sequence, and colmarch_kernel marches on wave-uniform state: one 16-byte gather and one transparency test per ~3 samples.  What the
-	// host checks: the lateral drift over the longest possible segment stays below half a cell, a sample advances between 1/64 and 1 cell
-	// along the axis (the kernel re-checks both per wave and otherwise marches per lane), at most one cell per pixel (the 32-bit offsets
-	// of a wave's columns), no clamping instantiation.  Measured on the benchmark poses (full march, lit): 2.12 / 2.13 / 2.86 ms before.
-	// NEAREST takes the same march over windows of 16 plain voxels (colmarch_nearest_kernel, kCopyColVox*): one gather per sixteen samples.
-	// Early ray termination alone is fine (the kernels clear a terminated lane's live bit like the general one; the k sequence stays shared);
-	// such frames give up the measured-cost tile order, which the column kernels do not take.
+	return VR_OK;
+}
+
+// Column windows (kLayoutColumn, vr_device.h): full-march TRILINEAR frames of ORTHOGONAL views along a volume axis — every ray stays in
+// one cell column (at most one cell flip per lateral axis: the direction's other components are rounding noise), all rays share the k
+// sequence, and colmarch_kernel marches on wave-uniform state: one 16-byte gather and one transparency test per ~3 samples.  What the
+// host checks: the lateral drift over the longest possible segment stays below half a cell, a sample advances between 1/64 and 1 cell
+// along the axis (the kernel re-checks both per wave and otherwise marches per lane), at most one cell per pixel (the 32-bit offsets
+// of a wave's columns), no clamping instantiation.  Measured on the benchmark poses (full march, lit): 2.12 / 2.13 / 2.86 ms before.
+// NEAREST takes the same march over windows of 16 plain voxels (colmarch_nearest_kernel, kCopyColVox*): one gather per sixteen samples.
+// Early ray termination alone is fine (the kernels clear a terminated lane's live bit like the general one; the k sequence stays shared);
+// such frames give up the measured-cost tile order, which the column kernels do not take.
+void column_march(const vr_ctx *c, const vr_params *p, const ViewAxis &va, RayKernelArgs &a, CopyChoice &choice) {
 	static const bool col_ert = [] { const char *e = getenv("VR_COL_ERT"); return e == nullptr || atoi(e) != 0; }();      // VR_COL_ERT=0: A/B
 	// Not a clipped frame: the column kernels march the whole cube on state the rays of a wave share, and a clipped segment is per ray.
-	if (bricked && !clip && c->bpv == 1 && !c->force_wide && !p->view.perspective && !p->esl && (p->ray_threshold >= 1.0f || col_ert) &&
-	    !a.clamp_fetch && c->column_force >= 0 && (c->brick_plane_force < 0 || c->column_force > 0)) {
-		const float *d = va.d;
-		const int m = va.major;
-		const float advance = d[m] * p->ray_step;
-		bool take = advance >= 1.0f / 64.0f && advance <= 1.0f && one_cell_per_pixel(p, half);
-		if (c->column_force == 0)                                          // per view: along the axis — 4 > 2 sqrt(3), the longest segment in k
-			for (int i = 0; i < 3; i++) if (i != m && d[i] * 4.0f >= 0.45f) take = false;
-		// TRILINEAR reads the voxel windows (kLayoutVoxCol, voxcol_tri_kernel) where every wave's rectangle of cell columns fits in its 64
-		// lanes: along a lateral axis i the 8x8 pixels of a wave span 7 pixel steps, i.e. at most floor(7 * cells per step) + 2 cells, + 1
-		// for the +1 neighbours of a trilinear sample and + 1 for a column flip.  The quad-element windows (colmarch_kernel) otherwise.
-		const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
-		bool voxcol = false;
-		if (!nearest && c->column_copy != 1u && col_copy_bytes(c->dim, (uint32_t) m, true) < (1ull << 32)) {      // (the kernel's explicit fetches use 32-bit offsets)
-			auto span = [&](int i) { return (int) std::floor(7.0f * (std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i]) + 4; };
-			voxcol = span(m == 0 ? 1 : 0) * span(m == 2 ? 1 : 2) <= 64;
-		}
-		if (take && copy_possible(c, (nearest || voxcol ? kCopyColVoxX : kCopyColX) + (uint32_t) m)) {
-			a.layout = voxcol ? kLayoutVoxCol : kLayoutColumn; a.col_axis = (uint32_t) m; a.brick_plane = (uint32_t) m;
-			// the dense path's constants, grouped for one scalar load each (vr_device.h); the products are the device's own fp32 products
-			a.col_sample.ax = p->view.direction[0] * a.half_x; a.col_sample.ay = p->view.direction[1] * a.half_y; a.col_sample.az = p->view.direction[2] * a.half_z;
-			a.col_sample.tf_scale = a.tf_scale; a.col_sample.tf_zero_below = a.tf_zero_below;
-			a.col_sample.max_x = a.max_x; a.col_sample.max_y = a.max_y; a.col_sample.max_z = a.max_z;
-			a.col_sample.light_kd = p->light_kd; a.col_sample.ray_threshold = p->ray_threshold;
-			for (int i = 0; i < 3; i++) { a.col_shade.dir[i] = p->view.direction[i]; a.col_shade.light[i] = p->view.light_pos[i]; }
-			a.col_shade.lh[0] = a.lh_x; a.col_shade.lh[1] = a.lh_y; a.col_shade.lh[2] = a.lh_z;
-			a.col_shade.kd_scaled = a.kd_scaled;
-			for (int i = 0; i < 3; i++) a.col_shade.dim[i] = c->dim[i];
-			a.col_shade.nbu = col_blocks(c->dim[m == 0 ? 1 : 0]);
-			a.col_shade.nw = col_windows(c->dim[m], nearest || voxcol ? kColVoxCells : kColCells);
-			a.col_shade.nwq = col_windows(c->dim[m]);
-			// a lit voxel-window frame shades from the quad-element windows of the same axis (voxcol_pairs_kernel: one 8-byte load per shaded
-			// sample instead of eight byte loads) — a second copy of 16/3 bytes per voxel, which vr_hip_set_column_copy(2) declines
-			shade_pairs = voxcol && p->light_kd > 0.01f && c->column_copy == 0;
-			dual_analytic = false; dual_stage = -1;
-		}
+	if (!(c->layout == VR_LAYOUT_BRICKED && !clipped_frame(c, a) && c->bpv == 1 && !c->force_wide && !p->view.perspective && !p->esl && (p->ray_threshold >= 1.0f || col_ert) &&
+	      !a.clamp_fetch && c->column_force >= 0 && (c->brick_plane_force < 0 || c->column_force > 0)))
+		return;
+	const float half[3] = { a.half_x, a.half_y, a.half_z };
+	const float *d = va.d;
+	const int m = va.major;
+	const float advance = d[m] * p->ray_step;
+	bool take = advance >= 1.0f / 64.0f && advance <= 1.0f && one_cell_per_pixel(p, half);
+	if (c->column_force == 0)                                          // per view: along the axis — 4 > 2 sqrt(3), the longest segment in k
+		for (int i = 0; i < 3; i++) if (i != m && d[i] * 4.0f >= 0.45f) take = false;
+	// TRILINEAR reads the voxel windows (kLayoutVoxCol, voxcol_tri_kernel) where every wave's rectangle of cell columns fits in its 64
+	// lanes: along a lateral axis i the 8x8 pixels of a wave span 7 pixel steps, i.e. at most floor(7 * cells per step) + 2 cells, + 1
+	// for the +1 neighbours of a trilinear sample and + 1 for a column flip.  The quad-element windows (colmarch_kernel) otherwise.
+	const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
+	bool voxcol = false;
+	if (!nearest && c->column_copy != 1u && col_copy_bytes(c->dim, (uint32_t) m, true) < (1ull << 32)) {      // (the kernel's explicit fetches use 32-bit offsets)
+		auto span = [&](int i) { return (int) std::floor(7.0f * (std::fabs(p->view.right_plane[i]) + std::fabs(p->view.up_plane[i])) * half[i]) + 4; };
+		voxcol = span(m == 0 ? 1 : 0) * span(m == 2 ? 1 : 2) <= 64;
 	}
-	// The copy this frame reads, built now if this is its first use.  A build that is refused (HBM guard, allocation, linear array
-	// released) degrades to the next best resident copy; the image is the same.
+	if (!take || !copy_possible(c, (nearest || voxcol ? kCopyColVoxX : kCopyColX) + (uint32_t) m)) return;
+	a.layout = voxcol ? kLayoutVoxCol : kLayoutColumn; a.col_axis = (uint32_t) m; a.brick_plane = (uint32_t) m;
+	// the dense path's constants, grouped for one scalar load each (vr_device.h); the products are the device's own fp32 products
+	a.col_sample.ax = p->view.direction[0] * a.half_x; a.col_sample.ay = p->view.direction[1] * a.half_y; a.col_sample.az = p->view.direction[2] * a.half_z;
+	a.col_sample.tf_scale = a.tf_scale; a.col_sample.tf_zero_below = a.tf_zero_below;
+	a.col_sample.max_x = a.max_x; a.col_sample.max_y = a.max_y; a.col_sample.max_z = a.max_z;
+	a.col_sample.light_kd = p->light_kd; a.col_sample.ray_threshold = p->ray_threshold;
+	for (int i = 0; i < 3; i++) { a.col_shade.dir[i] = p->view.direction[i]; a.col_shade.light[i] = p->view.light_pos[i]; }
+	a.col_shade.lh[0] = a.lh_x; a.col_shade.lh[1] = a.lh_y; a.col_shade.lh[2] = a.lh_z;
+	a.col_shade.kd_scaled = a.kd_scaled;
+	for (int i = 0; i < 3; i++) a.col_shade.dim[i] = c->dim[i];
+	a.col_shade.nbu = col_blocks(c->dim[m == 0 ? 1 : 0]);
+	a.col_shade.nw = col_windows(c->dim[m], nearest || voxcol ? kColVoxCells : kColCells);
+	a.col_shade.nwq = col_windows(c->dim[m]);
+	// a lit voxel-window frame shades from the quad-element windows of the same axis (voxcol_pairs_kernel: one 8-byte load per shaded
+	// sample instead of eight byte loads) — a second copy of 16/3 bytes per voxel, which vr_hip_set_column_copy(2) declines
+	choice.shade_pairs = voxcol && p->light_kd > 0.01f && c->column_copy == 0;
+	choice.dual_analytic = false; choice.dual_stage = -1;
+}
+
+// The copy this frame reads, built now if this is its first use.  A build that is refused (HBM guard, allocation, linear array
+// released) degrades to the next best resident copy; the image is the same.
+const void *acquire_copies(vr_ctx *c, const vr_params *p, CopyChoice &choice, RayKernelArgs &a) {
 	const void *brick_copy = nullptr;
 	// Run bricks, full march (the condition of kLayoutRunDual: with leaping or early termination the rays are short, and those frames keep
 	// the copies they have): the ALIGNED flavour (vr_device.h kRun7*: no run straddles a cache line) where the copies the frame would read
@@ -842,7 +798,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	if (a.layout == kLayoutRunDual && brick_copy == nullptr) {
 		brick_copy = copy_for(c, kCopyRunZ);
 		a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyRunY);
-		if (brick_copy == nullptr || a.alt_copy == 0) { a.layout = run_layout; dual_stage = -1; dual_analytic = false; brick_copy = nullptr; }
+		if (brick_copy == nullptr || a.alt_copy == 0) { a.layout = choice.run_layout; choice.dual_stage = -1; choice.dual_analytic = false; brick_copy = nullptr; }
 	}
 	if (a.layout != kLayoutLinear && brick_copy == nullptr) {
 		const uint32_t want = copy_kind_of(a, p->sampling);
@@ -852,53 +808,110 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			forget_tile_mappings(c);                         // lane orders were chosen for the copy that could not be had
 			brick_copy = copy_for(c, kCopyQuadXY);
 		}
-		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, !clip, a.layout);      // no quad copy either
+		if (brick_copy == nullptr) brick_copy = resident_fallback(c, p->sampling, !clipped_frame(c, a), a.layout);      // no quad copy either
 	}
 	// ... and the copy its shading samples read.  Refused or impossible (as above): the frame shades by byte loads from the voxel windows
-	if (shade_pairs && a.layout == kLayoutVoxCol && brick_copy != nullptr) a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyColX + a.col_axis);
+	if (choice.shade_pairs && a.layout == kLayoutVoxCol && brick_copy != nullptr) a.alt_copy = (uint64_t) (uintptr_t) copy_for(c, kCopyColX + a.col_axis);
+	return brick_copy;
+}
+
+// no frame that may still run reads or records the slot, and its order kernel, if one was issued, has run: its buffers may be rewritten
+bool slot_idle(const vr_ctx *c, const vr_ctx::SchedSlot &sl) {
+	if (sl.last_seq > c->completed_seq) return false;
+	if (sl.ready != nullptr && sl.issue_seq != 0 && hipEventQuery(sl.ready) != hipSuccess) { (void) hipGetLastError(); return false; }
+	return true;
+}
+
+// bd: the opaque layer of a backdrop frame (vr_hip_render_backdrop_device; device addresses), or NULL
+int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream, const vr_backdrop *bd = nullptr) {
+	// A shadowed frame (vr_hip_set_shadow): the light grid first, on the context's stream and synchronous like a brick copy's first use
+	const bool nearest = p->sampling == VR_SAMPLE_NEAREST;
+	if (c->shadow_on && nearest)
+		return fail(c, VR_ERR_INVALID, "a shadow is set: the light grid and its factor are defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_shadow(ctx, NULL) switches the shadow off)");
+	if (c->shadow_on) if (const int rc = build_shadow(c)) return rc;
+	// A gradient-lit, a pre-integrated and a backdrop frame read what a clipped frame reads too; clip, shadow, lighting and pre-integration compose
+	if (c->lighting_on && nearest)
+		return fail(c, VR_ERR_INVALID, "a lighting is set: the gradient is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_lighting(ctx, NULL) switches the lighting off)");
+	if (c->preint_on && nearest)
+		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab lies between two samples of the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or "
+		                               "VR_SAMPLE_TRILINEAR_Q8 (vr_hip_set_preintegration(ctx, 0) switches it off)");
+	if (bd != nullptr && nearest)
+		return fail(c, VR_ERR_INVALID, "a backdrop frame is defined on the interpolated field — sampling must be VR_SAMPLE_TRILINEAR or VR_SAMPLE_TRILINEAR_Q8");
+	RayKernelArgs a;
+	volume_args(c, p, a);
+	if (c->preint_on) a.slab_on = 1u;
+	if (bd != nullptr) { a.backdrop_on = 1u; a.backdrop_rgba = (uint64_t) (uintptr_t) bd->rgba; a.backdrop_depth = (uint64_t) (uintptr_t) bd->depth; }
+	lighting_shadow_args(c, a);
+	const float half[3] = { a.half_x, a.half_y, a.half_z };
+	const ViewAxis va = view_axis(p, half);
+	transparent_corner_test(c, a);
+	// fp32 sample coordinates that are not exact to a fraction of a cell: clamp every sample
+	const float omax = max_abs_origin(p), nmax = (float) max_dim_of(c);
+	a.clamp_fetch = fetch_coordinates_exact(c, p) ? 0u : 1u;
+	// intersect() replaces a direction component that is exactly 0 by 1e-5 (RaycasterBase.h:33-35): a ray whose origin lies
+	// up to ky * 1e-5 outside a face of the cube is then still reported as a hit and marches at that constant out-of-cube
+	// coordinate, ky * 1e-5 * N/2 texels beyond the face.  ky <= sqrt(3) * (omax + 1) for |direction| >= 1 (orthogonal: unit
+	// direction; perspective: a unit vector plus in-plane offsets).  Keep that below 1/8 texel, else clamp every sample.
+	if (1.7321f * (omax + 1.0f) * 1e-5f * nmax * 0.5f >= 0.125f) a.clamp_fetch = 1u;
+	// The unclamped march fetches up to kDepth steps past a ray's exit point (software pipeline): that must stay inside the
+	// kLutPad repeated edge entries of the address tables.  The reference's longest step is 1.666 cells (RaycasterBase.cpp:90).
+	// A step moves a ray by ray_step * |direction component| * N/2 cells along an axis; perspective directions are not
+	// normalised (direction + right * fx + up * fy, ViewBase.h:29-31), so the bound is taken over the whole frame.
+	float advance = 0.0f;
+	for (int i = 0; i < 3; i++) {
+		float d = std::fabs(p->view.direction[i]);
+		if (p->view.perspective)
+			d += std::fabs(p->view.right_plane[i]) * (0.5f * (float) p->view.width + 1.0f) + std::fabs(p->view.up_plane[i]) * (0.5f * (float) p->view.height + 1.0f);
+		advance = std::fmax(advance, d * half[i]);
+	}
+	if (!((float) kOverrunSteps * p->ray_step * advance + 1.5f <= (float) kLutPad)) a.clamp_fetch = 1u;
+	if (c->force_clamp_fetch & 1u) a.clamp_fetch = 1u;
+	auto pow2 = [](uint32_t n) { return n != 0 && (n & (n - 1)) == 0; };
+	a.near_scaled = (pow2(c->dim[0]) && pow2(c->dim[1]) && pow2(c->dim[2]) && !(c->force_clamp_fetch & 2u)) ? 1u : 0u;
+	a.force_wide = c->force_wide;
+	CopyChoice choice;
+	if (const int rc = choose_composite_copy(c, p, va, a, choice)) return rc;
+	column_march(c, p, va, a, choice);
+	const void *brick_copy = acquire_copies(c, p, choice, a);
 	// Shape of a wave's pixel tile (8x8, 16x4 or 4x16 inside the 32x16-pixel workgroup tile): a perspective view along a volume axis
 	// that reads run bricks gets its waves elongated along the screen direction the RUNS map to — the lanes of a wave then share the
 	// 36-byte runs (and their cache lines) instead of spreading over twice as many cell columns.  Measured on the benchmark's
 	// perspective poses: 2.07 -> 1.96 (along z, runs along y: tall), 2.04 -> 1.95 (along y, runs along z: tall), 2.05 -> 1.96 ms
 	// (along x, runs along z: wide); oblique views and orthogonal views lose 3-9 % with either elongated shape and keep 8x8.
-	if (c->tile_lane_map < 0 && is_run_layout(a.layout) && p->view.perspective && !p->esl) {       // (with leaping the rays are short: no difference measured)
-		if (va.along) {
-			const int run_axis = a.layout == kLayoutRunY ? 1 : 2;
-			const float across = std::fabs(p->view.right_plane[run_axis]), down = std::fabs(p->view.up_plane[run_axis]);
-			a.lane_map = (a.lane_map & 3u) | ((down > across ? 2u : 1u) << 2);
-		}
+	if (c->tile_lane_map < 0 && is_run_layout(a.layout) && p->view.perspective && !p->esl && va.along) {       // (with leaping the rays are short: no difference measured)
+		const int run_axis = a.layout == kLayoutRunY ? 1 : 2;
+		const float across = std::fabs(p->view.right_plane[run_axis]), down = std::fabs(p->view.up_plane[run_axis]);
+		a.lane_map = (a.lane_map & 3u) | ((down > across ? 2u : 1u) << 2);
 	}
 	// NEAREST on voxel bricks, perspective view along x or y: the four lanes of a quad are four pixels along the screen direction that
 	// maps to z — four different slices, i.e. four different lines — not a 2x2-pixel block: byte gathers whose lanes fall into the same
 	// dwords serialise (measured on the benchmark poses: 1.44 -> 1.38 ms along y, 1.46 -> 1.38 ms along x; along z the blocks stay: 1.23).
-	if (c->tile_lane_map < 0 && a.layout == kLayoutVoxel && p->view.perspective && (a.lane_map & 3u) == kLaneBlocks) {
-		if (va.major != 2) a.lane_map = std::fabs(p->view.up_plane[2]) > std::fabs(p->view.right_plane[2]) ? kLaneColumns : kLaneRows;
-	}
+	if (c->tile_lane_map < 0 && a.layout == kLayoutVoxel && p->view.perspective && (a.lane_map & 3u) == kLaneBlocks && va.major != 2)
+		a.lane_map = std::fabs(p->view.up_plane[2]) > std::fabs(p->view.right_plane[2]) ? kLaneColumns : kLaneRows;
 	const RaymarchPlan plan = plan_raymarch(a, brick_copy != nullptr, c->bpv);
 	if (plan.reads_linear && c->vol == nullptr)
 		return fail(c, VR_ERR_NOT_READY, "this frame needs the linear array, which was released (vr_hip_release_linear_copy): no resident brick copy "
 		                                 "serves this sampling mode / addressing path — prepare it before releasing, or set the volume again");
-
+	const uint32_t ntiles = plan.tiles_x * plan.tiles_y;
+	if (choice.dual_analytic && a.layout == kLayoutRunDual) dual_choice_bits(a, plan, choice.run_layout == kLayoutRunY);
 	// Measured-cost launch order: only where rays differ in length (empty-space leaping or early termination on) — the full
 	// march has no tail to remove and keeps its cache-friendly tile numbering.
-	const uint32_t ntiles = plan.tiles_x * plan.tiles_y;
-	if (dual_analytic && a.layout == kLayoutRunDual) dual_choice_bits(a, plan, run_layout == kLayoutRunY);
 	TileSchedule sched;
 	vr_ctx::SchedSlot *read_slot = nullptr, *record_slot = nullptr;
 	vr_ctx::OrderEntry *oe = nullptr;
 	// (not a backdrop frame: the layer changes per frame and the recorded orders are keyed by vr_params — its tiles start in grid order)
-	if (c->tile_scheduling == 1 && c->tile_lane_map < 0 && bd == nullptr && (VR_ORDER_ALWAYS || p->esl || p->ray_threshold < 1.0f) && ntiles >= 64 && ntiles <= (1u << 20)) {
+	if (c->tile_scheduling == 1 && c->tile_lane_map < 0 && !a.backdrop_on && (VR_ORDER_ALWAYS || p->esl || p->ray_threshold < 1.0f) && ntiles >= 64 && ntiles <= (1u << 20)) {
 		advance_completed(c);
 		vr_ctx::OrderKey key;
 		memset(&key, 0, sizeof key);
 		key.sampling = p->sampling; key.esl = p->esl ? 1u : 0u; key.ert = p->ray_threshold < 1.0f ? 1u : 0u; key.perspective = p->view.perspective ? 1u : 0u;
-		{
-			const int m = va.major;
-			key.major_axis = (uint32_t) m * 2u + (p->view.direction[m] < 0.0f ? 1u : 0u);
-			// ... and the direction itself in steps of 1/8 per component (views within a few degrees share their costs, different poses do not)
-			const float len = std::sqrt(p->view.direction[0] * p->view.direction[0] + p->view.direction[1] * p->view.direction[1] + p->view.direction[2] * p->view.direction[2]);
-			for (int i = 0; i < 3; i++) key.direction_q[i] = len > 0.0f ? (int32_t) std::lrint(p->view.direction[i] / len * 8.0f) : 0;
-		}
+		const int m = va.major;
+		key.major_axis = (uint32_t) m * 2u + (p->view.direction[m] < 0.0f ? 1u : 0u);
+		// ... and the direction itself in steps of 1/8 per component (views within a few degrees share their costs, different poses do not)
+		const float len = std::sqrt(p->view.direction[0] * p->view.direction[0] + p->view.direction[1] * p->view.direction[1] + p->view.direction[2] * p->view.direction[2]);
+		for (int i = 0; i < 3; i++) key.direction_q[i] = len > 0.0f ? (int32_t) std::lrint(p->view.direction[i] / len * 8.0f) : 0;
 		key.layout = a.layout; key.view_w = p->view.width; key.view_h = p->view.height; key.x0 = p->x0; key.out_width = p->out_width; key.out_rows = p->out_rows;
 		key.band_rows = p->band_rows; key.band_stride = p->band_stride; key.band_first = p->band_first;
 		memcpy(key.dim, c->dim, sizeof key.dim); key.tiles_x = plan.tiles_x; key.tiles_y = plan.tiles_y;
@@ -932,11 +945,8 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		static const bool estimate = [] { const char *e = getenv("VR_TILE_ESTIMATE"); return e == nullptr || atoi(e) != 0; }();      // VR_TILE_ESTIMATE=0: A/B
 		if (read_slot == nullptr && estimate && p->esl && a.layout != kLayoutColumn && a.layout != kLayoutVoxCol) {
 			vr_ctx::SchedSlot *est = nullptr;
-			for (auto &sl : oe->slot) {
-				if (sl.last_seq > c->completed_seq) continue;                                          // a frame that may still run reads or records it
-				if (sl.ready != nullptr && sl.issue_seq != 0) { const hipError_t q = hipEventQuery(sl.ready); if (q != hipSuccess) { (void) hipGetLastError(); continue; } }
-				est = &sl; break;
-			}
+			for (auto &sl : oe->slot)
+				if (slot_idle(c, sl)) { est = &sl; break; }
 			if (est != nullptr && !ensure_tile_buffers(est->cost, est->order, est->capacity, ntiles, 1u)) est = nullptr;
 			if (est != nullptr) {
 				if (est->ready == nullptr) VR_TRY(c, hipEventCreateWithFlags(&est->ready, hipEventDisableTiming));
@@ -956,8 +966,7 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 		if (!same) { oe->last = *p; oe->has_last = true; oe->repeats = 0; }
 		if (oe->repeats < 2u) {
 			for (auto &sl : oe->slot) {
-				if (&sl == read_slot || sl.last_seq > c->completed_seq) continue;                     // in use by this frame / by a frame that may still run
-				if (sl.ready != nullptr && sl.issue_seq != 0) { const hipError_t q = hipEventQuery(sl.ready); if (q != hipSuccess) { (void) hipGetLastError(); continue; } }   // its order kernel has not run yet
+				if (&sl == read_slot || !slot_idle(c, sl)) continue;                     // in use by this frame / by a frame that may still run / its order kernel has not run yet
 				if (record_slot == nullptr || (!sl.valid && record_slot->valid) || (sl.valid == record_slot->valid && sl.issue_seq < record_slot->issue_seq)) record_slot = &sl;
 			}
 			if (record_slot != nullptr && !ensure_tile_buffers(record_slot->cost, record_slot->order, record_slot->capacity, ntiles, 1u)) record_slot = nullptr;      // (free: nothing of it is in flight)
@@ -969,21 +978,21 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 			}
 		}
 	}
-
-	// kLayoutRunDual: frames 2 and 3 record, frame 3 is followed by the choice kernel, frame 4 onwards reads the choice.  Every step
-	// is ordered behind the one before through the entry's event when it runs on another stream.
-	bool dual_advance = false;
-	if (dual_stage >= 0) {
-		if (ntiles < 2u || ntiles > (1u << 20)) dual_stage = -1;      // (a frame that keeps kLayoutRunDual without a choice reads the copy along z)
+	// kLayoutRunDual by the measured / alternating choice: frames 2 and 3 record, frame 3 is followed by the choice kernel, frame 4 onwards reads
+	// the choice.  Every step is ordered behind the one before through the entry's event when it runs on another stream.
+	vr_ctx::MapEntry *hit = choice.hit;
+	const bool dual_test = c->brick_plane_force == (int) kPlanes + 4;
+	if (choice.dual_stage >= 0) {
+		if (ntiles < 2u || ntiles > (1u << 20)) choice.dual_stage = -1;      // (a frame that keeps kLayoutRunDual without a choice reads the copy along z)
 		else if (hit->capacity < ntiles) {
 			if (hit->cost) VR_TRY(c, drain(c));
-			if (!ensure_tile_buffers(hit->cost, hit->order, hit->capacity, ntiles, 2u)) dual_stage = -1;      // (order: the choice, and behind it the second recording)
-			if (!dual_test) { hit->dual_state = 0; if (dual_stage > 0) dual_stage = -1; }      // (cannot happen: the grid of a parameter set does not change)
+			if (!ensure_tile_buffers(hit->cost, hit->order, hit->capacity, ntiles, 2u)) choice.dual_stage = -1;      // (order: the choice, and behind it the second recording)
+			if (!dual_test) { hit->dual_state = 0; if (choice.dual_stage > 0) choice.dual_stage = -1; }      // (cannot happen: the grid of a parameter set does not change)
 		}
 	}
-	if (dual_stage >= 0) {
+	if (choice.dual_stage >= 0) {
 		if (hit->order_ready == nullptr) VR_TRY(c, hipEventCreateWithFlags(&hit->order_ready, hipEventDisableTiming));
-		if (dual_stage > 0 && !(dual_test && hit->order_tiles != ntiles) && hit->order_stream != nullptr && stream != hit->order_stream)
+		if (choice.dual_stage > 0 && !(dual_test && hit->order_tiles != ntiles) && hit->order_stream != nullptr && stream != hit->order_stream)
 			VR_TRY(c, hipStreamWaitEvent(stream, hit->order_ready, 0));
 		if (dual_test) {                                   // alternating tiles, built once per grid size
 			if (hit->order_tiles != ntiles) {
@@ -992,23 +1001,14 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 				hit->order_tiles = ntiles; hit->order_stream = stream;
 			}
 			sched.order = hit->order;
-		} else if (dual_stage == 2 || dual_stage == 3) {
-			uint32_t *into = dual_stage == 2 ? hit->cost : hit->order + hit->capacity;
+		} else if (choice.dual_stage == 2 || choice.dual_stage == 3) {
+			uint32_t *into = choice.dual_stage == 2 ? hit->cost : hit->order + hit->capacity;
 			VR_TRY(c, hipMemsetAsync(into, 0, (size_t) ntiles * 4, stream));
 			sched.cost = into;
-			dual_advance = true;
-		} else if (dual_stage == 4) sched.order = hit->order;
-		else dual_advance = true;
+		} else if (choice.dual_stage == 4) sched.order = hit->order;
 	}
-
 	if (c->tile_scheduling == 2 && ntiles <= (1u << 20)) {     // profiling: the cost of every tile of this frame, tile = workgroup id
-		if (c->cost_map_capacity < ntiles) {
-			VR_TRY(c, drain(c));
-			if (c->cost_map) (void) hipFree(c->cost_map);
-			c->cost_map = nullptr; c->cost_map_capacity = 0;
-			VR_TRY(c, hipMalloc((void **) &c->cost_map, (size_t) ntiles * 4));
-			c->cost_map_capacity = ntiles;
-		}
+		if (const int rc = grow_buffer(c, (void **) &c->cost_map, c->cost_map_bytes, (size_t) ntiles * 4)) return rc;
 		VR_TRY(c, hipMemsetAsync(c->cost_map, 0, (size_t) ntiles * 4, stream));
 		sched.cost = c->cost_map;
 		c->cost_map_tiles_x = plan.tiles_x; c->cost_map_tiles_y = plan.tiles_y;
@@ -1017,21 +1017,21 @@ int launch_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stre
 	// (the TRILINEAR column march over the voxel windows reports layout 7, the column march, and column_voxels = 1; column_shade_pairs = 1
 	// when it shades from the quad-element windows)
 	c->last_launch = vr_launch_info{ a.layout == kLayoutVoxCol ? (uint32_t) kLayoutColumn : a.layout, a.brick_plane, a.lane_map, a.phase_x, a.phase_y, a.clamp_fetch,
-	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, hit != nullptr ? hit->straddle_permille : uncached_straddle,
-	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u, shadow ? 1u : 0u };
+	                                 plan.tiles_x, plan.tiles_y, sched.order != nullptr ? 1u : 0u, choice.straddle,
+	                                 a.layout == kLayoutVoxCol ? 1u : 0u, a.layout == kLayoutVoxCol && a.alt_copy != 0 ? 1u : 0u, c->shadow_on ? 1u : 0u };
 	c->last_run_flavour = is_run_layout((int) a.layout) && brick_copy != nullptr ? (a.run_aligned ? 2u : 1u) : 0u;
 
 	uint64_t frame_seq = 0;
 	const int rc = launch_timed(c, a, p, plan, brick_copy, stream, frame_seq, [&] { return launch_raymarch(a, c->vol, brick_copy, c->bpv, c->tf, c->esl, dev_rgba, sched, stream); });
 	if (rc) return rc;
-	if (lighting) c->lit_frames++;
-	if (preint) c->preint_frames++;
+	if (c->lighting_on) c->lit_frames++;
+	if (c->preint_on) c->preint_frames++;
 	if (bd != nullptr) c->backdrop_frames++;
-	if (dual_advance) {                          // behind the frame, on its stream
-		if (dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
+	if (choice.dual_stage >= 0 && choice.dual_stage < 4) {      // behind the frame, on its stream: the entry moves to its next stage
+		if (choice.dual_stage == 3) VR_TRY(c, launch_tile_choice(hit->cost, hit->order + hit->capacity, hit->order, ntiles, stream));
 		VR_TRY(c, hipEventRecord(hit->order_ready, stream));
 		hit->order_stream = stream; hit->order_tiles = ntiles;
-		hit->dual_state = (uint32_t) dual_stage + 1u;
+		hit->dual_state = (uint32_t) choice.dual_stage + 1u;
 	}
 	if (read_slot != nullptr) read_slot->last_seq = frame_seq;
 	if (record_slot != nullptr) {                // behind the frame, on its stream: the order for the next frame under this policy key
