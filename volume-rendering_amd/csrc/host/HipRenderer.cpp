@@ -31,15 +31,29 @@ void HipRenderer::to_params(const Raycaster &r, vr_sampling sampling, vr_params 
 	p->band_first = 0;
 }
 
-HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, labelled_(false), mirror_error_(nullptr) {
+// The refusal of a device list, stated once; string literals, because mirror_error_ is a const char *.
+#define SINGLE_DEVICE(what, entry) what " a single device (" entry "): construct the renderer without a device list"
+
+// per Kind, in the enum's order: what render_volume() says to a device list (the composite is the one kind that renders on one)
+static const char *const kind_single_device[] = {
+	nullptr,
+	SINGLE_DEVICE("the maximum-intensity projection renders on", "vr_hip_render_mip"),
+	SINGLE_DEVICE("the isosurface renders on", "vr_hip_render_iso"),
+	SINGLE_DEVICE("the hybrid renders on", "vr_hip_render_hybrid"),
+	SINGLE_DEVICE("a section frame renders on", "vr_hip_render_section"),
+	SINGLE_DEVICE("a section frame renders on", "vr_hip_render_section"),
+	SINGLE_DEVICE("a labelled frame renders on", "vr_hip_render_labelled"),
+};
+
+static int status(int rc) { return rc == 0 ? 0 : 1; }
+
+HipRenderer::HipRenderer(Raycaster r, int device, vr_sampling sampling, bool device_buffer) : sampling_(sampling), device_buffer_(device_buffer) {
 	create_status_ = vr_hip_create(device, &ctx_);
 	if (create_status_ == 0)
 		prime(r);
 }
 
-HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer)
-	: ctx_(nullptr), multi_(nullptr), create_status_(0), sampling_(sampling), device_buffer_(device_buffer), mip_(false), iso_(false), hybrid_(false), iso_params_{ 0.0f, 0u }, section_(false), section_in_volume_(false), section_params_{}, labelled_(false), mirror_error_(nullptr) {
+HipRenderer::HipRenderer(Raycaster r, const int *devices, int n_devices, vr_sampling sampling, bool device_buffer) : sampling_(sampling), device_buffer_(device_buffer) {
 	create_status_ = vr_hip_multi_create(n_devices, devices, &multi_);
 	if (create_status_ == 0)
 		prime(r);
@@ -70,159 +84,113 @@ const char *HipRenderer::last_error() const {
 	return vr_hip_last_error(ctx_);
 }
 
-void HipRenderer::set_window_buffer(View view) {
+bool HipRenderer::open() {
 	if (!ok())
-		return;
-	if (multi_) vr_hip_multi_set_window(multi_, view.dims.x, view.dims.y);
-	else vr_hip_set_window(ctx_, view.dims.x, view.dims.y);
+		return false;
+	mirror_error_ = nullptr;
+	return true;
+}
+
+bool HipRenderer::single_device(const char *refusal) {
+	if (multi_ == nullptr)
+		return true;
+	mirror_error_ = refusal;
+	return false;
+}
+
+template <typename... Params, typename... Args>
+int HipRenderer::forward(int (*on_list)(vr_multi *, Params...), int (*on_context)(vr_ctx *, Params...), Args... args) {
+	return status(multi_ ? on_list(multi_, args...) : on_context(ctx_, args...));
+}
+
+// the three virtuals of the reference keep a standing refusal of this class; the setters of this class alone clear it (open())
+void HipRenderer::set_window_buffer(View view) {
+	if (ok())
+		forward(vr_hip_multi_set_window, vr_hip_set_window, view.dims.x, view.dims.y);
 }
 
 void HipRenderer::set_transfer_fn(Raycaster r) {
-	if (!ok())
-		return;
-	if (multi_) vr_hip_multi_set_transfer_fn(multi_, (const float *) r.transfer_fn, r.esl_volume);
-	else vr_hip_set_transfer_fn(ctx_, (const float *) r.transfer_fn, r.esl_volume);
+	if (ok())
+		forward(vr_hip_multi_set_transfer_fn, vr_hip_set_transfer_fn, (const float *) r.transfer_fn, r.esl_volume);
 }
 
 int HipRenderer::set_volume(Model volume) {
-	if (!ok())
-		return 1;
-	int rc = multi_ ? vr_hip_multi_set_volume(multi_, volume.data, volume.dims.x, volume.dims.y, volume.dims.z, 1)
-	                : vr_hip_set_volume(ctx_, volume.data, volume.dims.x, volume.dims.y, volume.dims.z, 1);
-	return rc == 0 ? 0 : 1;
+	return ok() ? forward(vr_hip_multi_set_volume, vr_hip_set_volume, volume.data, volume.dims.x, volume.dims.y, volume.dims.z, 1) : 1;
 }
 
-int HipRenderer::set_clip(const vr_clip *clip) {
-	if (!ok())
-		return 1;
-	mirror_error_ = nullptr;
-	const int rc = multi_ ? vr_hip_multi_set_clip(multi_, clip) : vr_hip_set_clip(ctx_, clip);
-	return rc == 0 ? 0 : 1;
-}
+int HipRenderer::set_clip(const vr_clip *clip) { return open() ? forward(vr_hip_multi_set_clip, vr_hip_set_clip, clip) : 1; }
 
-int HipRenderer::set_shadow(const vr_shadow *shadow) {
-	if (!ok())
-		return 1;
-	mirror_error_ = nullptr;
-	const int rc = multi_ ? vr_hip_multi_set_shadow(multi_, shadow) : vr_hip_set_shadow(ctx_, shadow);
-	return rc == 0 ? 0 : 1;
-}
+int HipRenderer::set_shadow(const vr_shadow *shadow) { return open() ? forward(vr_hip_multi_set_shadow, vr_hip_set_shadow, shadow) : 1; }
 
-int HipRenderer::set_lighting(const vr_lighting *lighting) {
-	if (!ok())
-		return 1;
-	mirror_error_ = nullptr;
-	const int rc = multi_ ? vr_hip_multi_set_lighting(multi_, lighting) : vr_hip_set_lighting(ctx_, lighting);
-	return rc == 0 ? 0 : 1;
-}
+int HipRenderer::set_lighting(const vr_lighting *lighting) { return open() ? forward(vr_hip_multi_set_lighting, vr_hip_set_lighting, lighting) : 1; }
 
-int HipRenderer::set_preintegration(bool on) {
-	if (!ok())
-		return 1;
-	mirror_error_ = nullptr;
-	const int rc = multi_ ? vr_hip_multi_set_preintegration(multi_, on ? 1u : 0u) : vr_hip_set_preintegration(ctx_, on ? 1u : 0u);
-	return rc == 0 ? 0 : 1;
-}
+int HipRenderer::set_preintegration(bool on) { return open() ? forward(vr_hip_multi_set_preintegration, vr_hip_set_preintegration, on ? 1u : 0u) : 1; }
 
 int HipRenderer::render_volume(uchar4 *buffer, Raycaster r) {
-	if (!ok() || buffer == nullptr)
+	if (buffer == nullptr || !open())
+		return 1;
+	if (kind_ != Kind::composite && !single_device(kind_single_device[(int) kind_]))
 		return 1;
 	vr_params p;
 	to_params(r, sampling_, &p);
-	int rc;
-	mirror_error_ = nullptr;
-	if (mip_ && multi_) {
-		mirror_error_ = "the maximum-intensity projection renders on a single device (vr_hip_render_mip): construct the renderer without a device list";
-		return 1;
-	}
-	if (iso_ && multi_) {
-		mirror_error_ = "the isosurface renders on a single device (vr_hip_render_iso): construct the renderer without a device list";
-		return 1;
-	}
-	if (hybrid_ && multi_) {
-		mirror_error_ = "the hybrid renders on a single device (vr_hip_render_hybrid): construct the renderer without a device list";
-		return 1;
-	}
-	if (section_ && multi_) {
-		mirror_error_ = "a section frame renders on a single device (vr_hip_render_section): construct the renderer without a device list";
-		return 1;
-	}
-	if (labelled_ && multi_) {
-		mirror_error_ = "a labelled frame renders on a single device (vr_hip_render_labelled): construct the renderer without a device list";
-		return 1;
-	}
-	if (labelled_) rc = device_buffer_ ? vr_hip_render_labelled_device(ctx_, &p, buffer, nullptr) : vr_hip_render_labelled(ctx_, &p, (uint8_t *) buffer);
-	else if (section_ && section_in_volume_) rc = device_buffer_ ? vr_hip_render_section_in_volume_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section_in_volume(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
-	else if (section_) rc = device_buffer_ ? vr_hip_render_section_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr) : vr_hip_render_section(ctx_, &p, &section_params_, (uint8_t *) buffer, nullptr);
-	else if (hybrid_) rc = device_buffer_ ? vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_hybrid(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
-	else if (iso_) rc = device_buffer_ ? vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr) : vr_hip_render_iso(ctx_, &p, &iso_params_, (uint8_t *) buffer, nullptr);
-	else if (mip_) rc = device_buffer_ ? vr_hip_render_mip_device(ctx_, &p, buffer, nullptr) : vr_hip_render_mip(ctx_, &p, (uint8_t *) buffer);
-	else if (multi_) rc = device_buffer_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_multi_render(multi_, &p, (uint8_t *) buffer);
-	else rc = device_buffer_ ? vr_hip_render_device(ctx_, &p, buffer, nullptr) : vr_hip_render(ctx_, &p, (uint8_t *) buffer);
-	return rc == 0 ? 0 : 1;
+	uint8_t *const host = (uint8_t *) buffer;
+	if (device_buffer_)
+		switch (kind_) {
+			case Kind::composite: return status(multi_ ? vr_hip_multi_render_device(multi_, &p, buffer) : vr_hip_render_device(ctx_, &p, buffer, nullptr));
+			case Kind::mip: return status(vr_hip_render_mip_device(ctx_, &p, buffer, nullptr));
+			case Kind::iso: return status(vr_hip_render_iso_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr));
+			case Kind::hybrid: return status(vr_hip_render_hybrid_device(ctx_, &p, &iso_params_, buffer, nullptr, nullptr));
+			case Kind::section: return status(vr_hip_render_section_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr));
+			case Kind::section_in_volume: return status(vr_hip_render_section_in_volume_device(ctx_, &p, &section_params_, buffer, nullptr, nullptr));
+			case Kind::labelled: return status(vr_hip_render_labelled_device(ctx_, &p, buffer, nullptr));
+		}
+	else
+		switch (kind_) {
+			case Kind::composite: return status(multi_ ? vr_hip_multi_render(multi_, &p, host) : vr_hip_render(ctx_, &p, host));
+			case Kind::mip: return status(vr_hip_render_mip(ctx_, &p, host));
+			case Kind::iso: return status(vr_hip_render_iso(ctx_, &p, &iso_params_, host, nullptr));
+			case Kind::hybrid: return status(vr_hip_render_hybrid(ctx_, &p, &iso_params_, host, nullptr));
+			case Kind::section: return status(vr_hip_render_section(ctx_, &p, &section_params_, host, nullptr));
+			case Kind::section_in_volume: return status(vr_hip_render_section_in_volume(ctx_, &p, &section_params_, host, nullptr));
+			case Kind::labelled: return status(vr_hip_render_labelled(ctx_, &p, host));
+		}
+	return 1;
 }
 
 int HipRenderer::render_backdrop(uchar4 *buffer, Raycaster r, const vr_backdrop *layer) {
-	if (!ok() || buffer == nullptr)
+	if (buffer == nullptr || !open() || !single_device(SINGLE_DEVICE("a backdrop frame renders on", "vr_hip_render_backdrop")))
 		return 1;
-	mirror_error_ = nullptr;
-	if (multi_) {
-		mirror_error_ = "a backdrop frame renders on a single device (vr_hip_render_backdrop): construct the renderer without a device list";
-		return 1;
-	}
 	vr_params p;
 	to_params(r, sampling_, &p);
-	const int rc = device_buffer_ ? vr_hip_render_backdrop_device(ctx_, &p, layer, buffer, nullptr) : vr_hip_render_backdrop(ctx_, &p, layer, (uint8_t *) buffer);
-	return rc == 0 ? 0 : 1;
+	return status(device_buffer_ ? vr_hip_render_backdrop_device(ctx_, &p, layer, buffer, nullptr) : vr_hip_render_backdrop(ctx_, &p, layer, (uint8_t *) buffer));
 }
 
 int HipRenderer::set_labels(const uint8_t *labels, const uint32_t dims[3]) {
-	if (!ok())
+	if (!open() || !single_device(SINGLE_DEVICE("label volumes belong to", "vr_hip_set_labels")))
 		return 1;
-	mirror_error_ = nullptr;
-	if (multi_) {
-		mirror_error_ = "label volumes belong to a single device (vr_hip_set_labels): construct the renderer without a device list";
-		return 1;
-	}
-	return vr_hip_set_labels(ctx_, labels, dims ? dims[0] : 0u, dims ? dims[1] : 0u, dims ? dims[2] : 0u) == 0 ? 0 : 1;
+	return status(vr_hip_set_labels(ctx_, labels, dims ? dims[0] : 0u, dims ? dims[1] : 0u, dims ? dims[2] : 0u));
 }
 
 int HipRenderer::set_label_table(const vr_label_entry *entries, uint32_t count) {
-	if (!ok())
+	if (!open() || !single_device(SINGLE_DEVICE("label tables belong to", "vr_hip_set_label_table")))
 		return 1;
-	mirror_error_ = nullptr;
-	if (multi_) {
-		mirror_error_ = "label tables belong to a single device (vr_hip_set_label_table): construct the renderer without a device list";
-		return 1;
-	}
-	return vr_hip_set_label_table(ctx_, entries, count) == 0 ? 0 : 1;
+	return status(vr_hip_set_label_table(ctx_, entries, count));
 }
 
 int HipRenderer::render_depth(Raycaster r, const vr_depth &depth, const vr_depth_out *out) {
-	if (!ok() || out == nullptr)
+	if (out == nullptr || !open() || !single_device(SINGLE_DEVICE("a depth frame renders on", "vr_hip_render_depth")))
 		return 1;
-	mirror_error_ = nullptr;
-	if (multi_) {
-		mirror_error_ = "a depth frame renders on a single device (vr_hip_render_depth): construct the renderer without a device list";
-		return 1;
-	}
 	vr_params p;
 	to_params(r, sampling_, &p);
-	const int rc = device_buffer_ ? vr_hip_render_depth_device(ctx_, &p, &depth, out, nullptr) : vr_hip_render_depth(ctx_, &p, &depth, out);
-	return rc == 0 ? 0 : 1;
+	return status(device_buffer_ ? vr_hip_render_depth_device(ctx_, &p, &depth, out, nullptr) : vr_hip_render_depth(ctx_, &p, &depth, out));
 }
 
 int HipRenderer::pick(Raycaster r, const vr_depth &depth, uint32_t n, const uint32_t *xy, vr_pick *out) {
-	if (!ok())
+	if (!open() || !single_device(SINGLE_DEVICE("a pick renders on", "vr_hip_pick")))
 		return 1;
-	mirror_error_ = nullptr;
-	if (multi_) {
-		mirror_error_ = "a pick renders on a single device (vr_hip_pick): construct the renderer without a device list";
-		return 1;
-	}
 	vr_params p;
 	to_params(r, sampling_, &p);
-	return vr_hip_pick(ctx_, &p, &depth, n, xy, out) == 0 ? 0 : 1;
+	return status(vr_hip_pick(ctx_, &p, &depth, n, xy, out));
 }
 
 }  // namespace volr

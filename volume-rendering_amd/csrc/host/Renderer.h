@@ -88,22 +88,27 @@ class HipRenderer : public Renderer {
 		// true: render_volume() produces the maximum-intensity projection (vr_hip_render_mip: the largest sample of every ray through one
 		// transfer-function lookup; Raycaster::esl then selects its exact fetch skipping) instead of the front-to-back composite.
 		// Single device only: with a device list render_volume() returns 1 and last_error() says why.
-		void set_mip(bool mip) { mip_ = mip; if (mip) iso_ = hybrid_ = section_ = labelled_ = false; }
+		void set_mip(bool mip) { hold(Kind::mip, mip); }
 		// on: render_volume() produces the shaded isosurface at `level` (raw voxel units) with `refine` bisection steps (vr_hip_render_iso;
 		// Raycaster::esl selects its exact fetch skipping, no depth comes back through this interface).  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip: the one set last holds.  Single device only, like set_mip.
-		void set_iso(bool on, float level, uint32_t refine) { iso_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = hybrid_ = section_ = labelled_ = false; }
+		void set_iso(bool on, float level, uint32_t refine) { iso_params_ = { level, refine }; hold(Kind::iso, on); }
 		// on: render_volume() produces the hybrid (vr_hip_render_hybrid): that isosurface seen through the translucent volume in front of it —
 		// the isosurface frame, then the composite frame stopped at its depth and blended over it; the composite pass sees the clip, the
 		// shadow, the lighting and the pre-integration of this renderer.  Needs a TRILINEAR sampling mode.  Excludes set_mip and set_iso:
 		// the one set last holds.  Single device only, like them.
-		void set_hybrid(bool on, float level, uint32_t refine) { hybrid_ = on; iso_params_.level = level; iso_params_.refine = refine; if (on) mip_ = iso_ = section_ = labelled_ = false; }
+		void set_hybrid(bool on, float level, uint32_t refine) { iso_params_ = { level, refine }; hold(Kind::hybrid, on); }
 		// on: render_volume() produces the section frame (vr_hip_render_section): the oblique slice `section` through the interpolated field, or
 		// its thick-slab maximum, minimum or mean, coloured by the transfer function or the section's grey window; in_volume: that section seen
 		// through the translucent volume in front of it (vr_hip_render_section_in_volume: the composite pass sees the clip, the shadow, the
 		// lighting and the pre-integration of this renderer).  No depth comes back through this interface.  Needs a TRILINEAR sampling mode.
 		// Excludes set_mip, set_iso and set_hybrid: the one set last holds.  Single device only, like them.
-		void set_section(bool on, const vr_section &section, bool in_volume) { section_ = on; section_in_volume_ = in_volume; section_params_ = section; if (on) mip_ = iso_ = hybrid_ = labelled_ = false; }
+		void set_section(bool on, const vr_section &section, bool in_volume) {
+			section_params_ = section;
+			if (kind_ == Kind::section_in_volume) kind_ = Kind::section;      // the two section kinds are one to this setter: off leaves either
+			hold(Kind::section, on);
+			if (on && in_volume) kind_ = Kind::section_in_volume;
+		}
 		// One composite frame over an opaque layer (vr_hip_render_backdrop / vr_hip_render_backdrop_device by the buffer flavour of this
 		// renderer): `layer` holds host or device pointers accordingly, view.dims pixels each.  Whatever set_mip / set_iso / set_hybrid say,
 		// this is a composite frame.  Single device only.  0 = ok, 1 = failure.
@@ -122,7 +127,7 @@ class HipRenderer : public Renderer {
 		// pre-integration, set_mip, set_iso, set_hybrid and set_section: the one set last holds.  Single device only.  0 = ok, 1 = failure.
 		int set_labels(const uint8_t *labels, const uint32_t dims[3]);
 		int set_label_table(const vr_label_entry *entries, uint32_t count);
-		void set_labelled(bool on) { labelled_ = on; if (on) mip_ = iso_ = hybrid_ = section_ = false; }
+		void set_labelled(bool on) { hold(Kind::labelled, on); }
 		// The clip region of every later frame of this renderer — composite, set_mip and set_iso alike, and with a device list every device's
 		// bands (vr_hip_set_clip / vr_hip_multi_set_clip: a crop box in model space and a kept half-space).  NULL switches clipping off.
 		// 0 = ok, 1 = failure (a non-finite member, box_min >= box_max), the reference's convention.
@@ -144,21 +149,24 @@ class HipRenderer : public Renderer {
 	private:
 		HipRenderer(const HipRenderer &);
 		HipRenderer &operator=(const HipRenderer &);
+		// what render_volume() produces: one kind at a time, so a setter that switches its kind on replaces whichever held before
+		enum class Kind { composite, mip, iso, hybrid, section, section_in_volume, labelled };
+		void hold(Kind kind, bool on) { if (on) kind_ = kind; else if (kind_ == kind) kind_ = Kind::composite; }
 		void prime(const Raycaster &r);
-		vr_ctx *ctx_;
-		vr_multi *multi_;
-		int create_status_;
+		bool open();                                    // ok(), and then no failure of this class stands any more
+		bool single_device(const char *refusal);       // false with `refusal` as last_error() when there is a device list
+		// one setter on the device list or on the context; 0 = ok, 1 = failure
+		template <typename... Params, typename... Args>
+		int forward(int (*on_list)(vr_multi *, Params...), int (*on_context)(vr_ctx *, Params...), Args... args);
+		vr_ctx *ctx_ = nullptr;
+		vr_multi *multi_ = nullptr;
+		int create_status_ = 0;
 		vr_sampling sampling_;
 		bool device_buffer_;
-		bool mip_;
-		bool iso_;
-		bool hybrid_;
-		vr_iso iso_params_;
-		bool section_;
-		bool section_in_volume_;
-		vr_section section_params_;
-		bool labelled_;
-		const char *mirror_error_;      // a failure of this class itself (nothing below the C ABI was called)
+		Kind kind_ = Kind::composite;
+		vr_iso iso_params_ = { 0.0f, 0u };             // of Kind::iso and Kind::hybrid: stored by their setters whether or not `on`
+		vr_section section_params_ = {};               // of the two section kinds, likewise
+		const char *mirror_error_ = nullptr;            // a failure of this class itself (nothing below the C ABI was called)
 };
 
 }  // namespace volr

@@ -308,36 +308,42 @@ int draw_depth(const vr_depth &d, std::vector<float> &depth) {
 	return rc;
 }
 
-}  // namespace
-
-int main(int argc, char **argv) {
-	std::string file_name, out_ppm;
-	bool benchmark_mode = false, persp = false, have_pose = false, mip = false, iso = false, hybrid = false;
-	float iso_level = 0.0f;
-	int iso_refine = 4;
-	bool depth_on = false, depth_mode_given = false, pick_on = false;
-	vr_depth depth_params = { 0.5f, VR_DEPTH_FIRST };
-	uint32_t pick_xy[2] = { 0u, 0u };
-	std::string labels_file;
-	bool labels_octants = false;
-	uint32_t label_entries = 0;                 // entries of the table given so far: the highest -label id + 1
-	std::vector<vr_label_entry> label_table(VR_LABEL_COUNT, vr_label_entry{ { 0.0f, 0.0f, 0.0f }, 0.0f, 1.0f });
-	bool section_on = false, section_in_volume = false, section_mode_given = false, section_window_given = false;
-	vr_section section = { { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f, VR_SECTION_POINT, { 0.0f, 0.0f } };
-	bool clip_box = false, clip_plane = false;
-	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
-	int shadow_dims = 0;
-	bool phong = false, preint = false;
-	vr_lighting lighting = { 0.25f, 0.65f, 0.4f, 4u };
-	float shadow_strength = 1.0f, shadow_step = 0.0f;
+// ---- the command line ----
+struct Options {
+	std::string file_name, out_ppm, labels_file;
+	bool loaded = false;                        // a volume is resident (main sets it after loading)
+	bool benchmark_mode = false, persp = false, have_pose = false;
 	float pose[4] = { 120, 0, 200, 3 };       // the reference's interactive start pose (VolR.cpp:436)
-	ViewBase::reset();
+	bool mip = false, iso = false, hybrid = false, section_on = false, depth_on = false, labels_octants = false;       // the frame kinds (`kinds` below)
+	float iso_level = 0.0f;                     // of -iso and -hybrid: the one given last
+	int iso_refine = 4;
+	bool section_in_volume = false, section_mode_given = false, section_window_given = false, depth_mode_given = false, pick_on = false;
+	vr_section section = { { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f, VR_SECTION_POINT, { 0.0f, 0.0f } };
+	vr_depth depth = { 0.5f, VR_DEPTH_FIRST };
+	uint32_t pick_xy[2] = { 0u, 0u };
+	uint32_t label_entries = 0;                 // entries of the table given so far: the highest -label id + 1
+	std::vector<vr_label_entry> label_table = std::vector<vr_label_entry>(VR_LABEL_COUNT, vr_label_entry{ { 0.0f, 0.0f, 0.0f }, 0.0f, 1.0f });
+	bool clip_box = false, clip_plane = false, phong = false, preint = false;       // state of every frame
+	vr_clip clip = { { -1.0f, -1.0f, -1.0f }, { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+	vr_lighting lighting = { 0.25f, 0.65f, 0.4f, 4u };
+	int shadow_dims = 0;
+	float shadow_strength = 1.0f, shadow_step = 0.0f;
+};
+
+const char *const section_mode_names[] = { "point", "max", "min", "mean" }, *const depth_mode_names[] = { "first", "peak", "mean" };      // by vr_section_mode / vr_depth_mode
+
+// Fills `o` (and the globals above) from the command line.  A refused option prints its message and is skipped, like the reference's
+// parser; -h and two malformed values end the program: the exit status then, else -1.
+int parse(int argc, char **argv, Options &o) {
 	for (int i = 1; i < argc; i++) {
 		const char *arg = argv[i];
 		auto need = [&](int n) { if (i + n >= argc) { printf("%s error: Not enough parameters. Use -h to help.\n", arg); return false; } return true; };
-		if (strcmp(arg, "-h") == 0) { print_usage(); return EXIT_SUCCESS; }
-		else if (strcmp(arg, "-f") == 0) { if (need(1)) file_name = argv[++i]; }
-		else if (strcmp(arg, "-raw") == 0) {
+		auto is = [&](const char *flag) { return strcmp(arg, flag) == 0; };
+		auto number = [&]() { return (float) atof(argv[++i]); };
+		auto mode = [&](const char *const *names, int first, int count) { const char *m = argv[++i]; for (int k = first; k < count; k++) if (strcmp(m, names[k]) == 0) return k; return -1; };
+		if (is("-h")) { print_usage(); return EXIT_SUCCESS; }
+		else if (is("-f")) { if (need(1)) o.file_name = argv[++i]; }
+		else if (is("-raw")) {
 			if (!need(3)) continue;
 			const unsigned w = atoi(argv[i + 1]), h = atoi(argv[i + 2]), d = atoi(argv[i + 3]);
 			i += 3;
@@ -345,244 +351,268 @@ int main(int argc, char **argv) {
 			if (i + 1 < argc && argv[i + 1][0] != '-') c = atoi(argv[++i]);
 			ModelBase::set_raw_dims(w, h, d, c);
 		}
-		else if (strcmp(arg, "-synthetic") == 0) { if (need(1)) synthetic_n = atoi(argv[++i]); }
-		else if (strcmp(arg, "-dir") == 0) { if (need(1)) dataset_dir = argv[++i]; }
-		else if (strcmp(arg, "-r") == 0) {
+		else if (is("-synthetic")) { if (need(1)) synthetic_n = atoi(argv[++i]); }
+		else if (is("-dir")) { if (need(1)) dataset_dir = argv[++i]; }
+		else if (is("-r")) {
 			if (!need(1)) continue;
 			const int r = atoi(argv[++i]);
 			if (r < 0 || r >= PROFILER_RENDERERS) { printf("%s error: Wrong parameters. Use -h to help.\n", arg); continue; }
 			renderer_id = r;
 		}
-		else if (strcmp(arg, "-s") == 0) {
+		else if (is("-s")) {
 			if (!need(2)) continue;
 			const int w = atoi(argv[++i]), h = atoi(argv[++i]);
 			if (w < 128 || h < 128 || w > 2048 || h > 2048) { printf("%s error: Wrong parameters. Use -h to help.\n", arg); continue; }   // VolR.cpp:392
 			ViewBase::set_viewport_dims(make_ushort2((unsigned short) w, (unsigned short) h));
 		}
-		else if (strcmp(arg, "-d") == 0) { if (need(1)) device = atoi(argv[++i]); }
-		else if (strcmp(arg, "-devices") == 0) {
+		else if (is("-d")) { if (need(1)) device = atoi(argv[++i]); }
+		else if (is("-devices")) {
 			if (!need(1)) continue;
 			for (const char *q = argv[++i]; *q; ) { device_list.push_back(atoi(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
 		}
-		else if (strcmp(arg, "-bg") == 0 || strcmp(arg, "-b") == 0) benchmark_mode = true;
-		else if (strcmp(arg, "-persp") == 0) persp = true;
-		else if (strcmp(arg, "-mip") == 0) mip = true;
-		else if (strcmp(arg, "-iso") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); iso = true; } }
-		else if (strcmp(arg, "-hybrid") == 0) { if (need(1)) { iso_level = (float) atof(argv[++i]); hybrid = true; } }
-		else if (strcmp(arg, "-section") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) section.plane[k] = (float) atof(argv[++i]); section_on = true; } }
-		else if (strcmp(arg, "-section-half") == 0) { if (need(1)) section.half_width = (float) atof(argv[++i]); }
-		else if (strcmp(arg, "-section-mode") == 0) {
+		else if (is("-bg") || is("-b")) o.benchmark_mode = true;
+		else if (is("-persp")) o.persp = true;
+		else if (is("-mip")) o.mip = true;
+		else if (is("-iso")) { if (need(1)) { o.iso_level = number(); o.iso = true; } }
+		else if (is("-hybrid")) { if (need(1)) { o.iso_level = number(); o.hybrid = true; } }
+		else if (is("-section")) { if (need(4)) { for (int k = 0; k < 4; k++) o.section.plane[k] = number(); o.section_on = true; } }
+		else if (is("-section-half")) { if (need(1)) o.section.half_width = number(); }
+		else if (is("-section-mode")) {
 			if (!need(1)) continue;
-			const char *m = argv[++i];
-			if (strcmp(m, "max") == 0) section.mode = VR_SECTION_MAX;
-			else if (strcmp(m, "min") == 0) section.mode = VR_SECTION_MIN;
-			else if (strcmp(m, "mean") == 0) section.mode = VR_SECTION_MEAN;
-			else { printf("%s error: Wrong parameters. Use -h to help.\n", arg); continue; }
-			section_mode_given = true;
+			const int m = mode(section_mode_names, 1, 4);           // "point" is what no -section-half gives, not a word of this option
+			if (m < 0) { printf("%s error: Wrong parameters. Use -h to help.\n", arg); continue; }
+			o.section.mode = (uint32_t) m; o.section_mode_given = true;
 		}
-		else if (strcmp(arg, "-section-window") == 0) { if (need(2)) { section.window[0] = (float) atof(argv[++i]); section.window[1] = (float) atof(argv[++i]); section_window_given = true; } }
-		else if (strcmp(arg, "-section-in-volume") == 0) section_in_volume = true;
-		else if (strcmp(arg, "-depth") == 0) { if (need(1)) { depth_params.opacity = (float) atof(argv[++i]); depth_on = true; } }
-		else if (strcmp(arg, "-depth-mode") == 0) {
-			if (need(1)) {
-				const char *m = argv[++i];
-				if (strcmp(m, "first") == 0) depth_params.mode = VR_DEPTH_FIRST;
-				else if (strcmp(m, "peak") == 0) depth_params.mode = VR_DEPTH_PEAK;
-				else if (strcmp(m, "mean") == 0) depth_params.mode = VR_DEPTH_MEAN;
-				else { printf("Error: -depth-mode takes first, peak or mean\n"); return EXIT_FAILURE; }
-				depth_mode_given = true;
-			}
+		else if (is("-section-window")) { if (need(2)) { o.section.window[0] = number(); o.section.window[1] = number(); o.section_window_given = true; } }
+		else if (is("-section-in-volume")) o.section_in_volume = true;
+		else if (is("-depth")) { if (need(1)) { o.depth.opacity = number(); o.depth_on = true; } }
+		else if (is("-depth-mode")) {
+			if (!need(1)) continue;
+			const int m = mode(depth_mode_names, 0, 3);
+			if (m < 0) { printf("Error: -depth-mode takes first, peak or mean\n"); return EXIT_FAILURE; }
+			o.depth.mode = (uint32_t) m; o.depth_mode_given = true;
 		}
-		else if (strcmp(arg, "-pick") == 0) { if (need(2)) { pick_xy[0] = (uint32_t) atoi(argv[++i]); pick_xy[1] = (uint32_t) atoi(argv[++i]); pick_on = true; } }
-		else if (strcmp(arg, "-labels") == 0) { if (need(1)) labels_file = argv[++i]; }
-		else if (strcmp(arg, "-labels-octants") == 0) labels_octants = true;
-		else if (strcmp(arg, "-label") == 0) {
+		else if (is("-pick")) { if (need(2)) { o.pick_xy[0] = (uint32_t) atoi(argv[++i]); o.pick_xy[1] = (uint32_t) atoi(argv[++i]); o.pick_on = true; } }
+		else if (is("-labels")) { if (need(1)) o.labels_file = argv[++i]; }
+		else if (is("-labels-octants")) o.labels_octants = true;
+		else if (is("-label")) {
 			if (!need(6)) continue;
 			const int id = atoi(argv[++i]);
 			vr_label_entry e;
-			for (int k = 0; k < 3; k++) e.colour[k] = (float) atof(argv[++i]);
-			e.mix = (float) atof(argv[++i]); e.opacity = (float) atof(argv[++i]);
+			for (int k = 0; k < 3; k++) e.colour[k] = number();
+			e.mix = number(); e.opacity = number();
 			if (id < 0 || id >= VR_LABEL_COUNT) { printf("Error: -label takes an id in 0..255\n"); return EXIT_FAILURE; }
-			label_table[(size_t) id] = e;
-			if ((uint32_t) id + 1u > label_entries) label_entries = (uint32_t) id + 1u;
+			o.label_table[(size_t) id] = e;
+			if ((uint32_t) id + 1u > o.label_entries) o.label_entries = (uint32_t) id + 1u;
 		}
-		else if (strcmp(arg, "-refine") == 0) { if (need(1)) iso_refine = atoi(argv[++i]); }
-		else if (strcmp(arg, "-clip-box") == 0) {
-			if (need(6)) { for (int k = 0; k < 3; k++) clip.box_min[k] = (float) atof(argv[++i]); for (int k = 0; k < 3; k++) clip.box_max[k] = (float) atof(argv[++i]); clip_box = true; }
+		else if (is("-refine")) { if (need(1)) o.iso_refine = atoi(argv[++i]); }
+		else if (is("-clip-box")) { if (need(6)) { for (int k = 0; k < 3; k++) o.clip.box_min[k] = number(); for (int k = 0; k < 3; k++) o.clip.box_max[k] = number(); o.clip_box = true; } }
+		else if (is("-clip-plane")) { if (need(4)) { for (int k = 0; k < 4; k++) o.clip.plane[k] = number(); o.clip_plane = true; } }
+		else if (is("-shadow")) { if (need(1)) o.shadow_dims = atoi(argv[++i]); }
+		else if (is("-shadow-strength")) { if (need(1)) o.shadow_strength = number(); }
+		else if (is("-shadow-step")) { if (need(1)) o.shadow_step = number(); }
+		else if (is("-preint")) o.preint = true;
+		else if (is("-phong")) {
+			if (need(4)) { o.lighting.ambient = number(); o.lighting.diffuse = number(); o.lighting.specular = number(); o.lighting.shininess_log2 = (uint32_t) atoi(argv[++i]); o.phong = true; }
 		}
-		else if (strcmp(arg, "-clip-plane") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) clip.plane[k] = (float) atof(argv[++i]); clip_plane = true; } }
-		else if (strcmp(arg, "-shadow") == 0) { if (need(1)) shadow_dims = atoi(argv[++i]); }
-		else if (strcmp(arg, "-shadow-strength") == 0) { if (need(1)) shadow_strength = (float) atof(argv[++i]); }
-		else if (strcmp(arg, "-shadow-step") == 0) { if (need(1)) shadow_step = (float) atof(argv[++i]); }
-		else if (strcmp(arg, "-preint") == 0) preint = true;
-		else if (strcmp(arg, "-phong") == 0) {
-			if (need(4)) { lighting.ambient = (float) atof(argv[++i]); lighting.diffuse = (float) atof(argv[++i]); lighting.specular = (float) atof(argv[++i]); lighting.shininess_log2 = (uint32_t) atoi(argv[++i]); phong = true; }
-		}
-		else if (strcmp(arg, "-pose") == 0) { if (need(4)) { for (int k = 0; k < 4; k++) pose[k] = (float) atof(argv[++i]); have_pose = true; } }
-		else if (strcmp(arg, "-o") == 0) { if (need(1)) out_ppm = argv[++i]; }
+		else if (is("-pose")) { if (need(4)) { for (int k = 0; k < 4; k++) o.pose[k] = number(); o.have_pose = true; } }
+		else if (is("-o")) { if (need(1)) o.out_ppm = argv[++i]; }
 		else printf("Warning: unknown argument: %s\n", arg);
 	}
+	return -1;
+}
 
-	// VolR.cpp:412-417
-	bool loaded = !file_name.empty() && ModelBase::load_model(file_name.c_str()) == 0;
-	if (!loaded) loaded = use_synthetic();
-	if (!loaded && !benchmark_mode) { printf("Warning: no volume data loaded (use -f or -synthetic).\n"); return EXIT_FAILURE; }
-	RaycasterBase::set_view(ViewBase::view);
-	RaycasterBase::reset_transfer_fn();
-	if (loaded) RaycasterBase::set_volume(ModelBase::volume);
-	Profiler::init();
+// "Error: <what the renderer says>" after a refused call
+bool accepted(HipRenderer *renderer, int rc) { if (rc != 0) printf("Error: %s\n", renderer->last_error()); return rc == 0; }
 
-	printf("Initializing renderers 0 - %d...\n", PROFILER_RENDERERS - 1);
-	if (!device_list.empty()) {
-		renderers[0] = new HipRenderer(RaycasterBase::raycaster, device_list.data(), (int) device_list.size(), VR_SAMPLE_NEAREST);
-		renderers[1] = new HipRenderer(RaycasterBase::raycaster, device_list.data(), (int) device_list.size(), VR_SAMPLE_TRILINEAR);
-		if (renderers[1]->ok()) printf("Frame split over %d device(s), bands gathered by %s\n", (int) device_list.size(), vr_hip_multi_transport(renderers[1]->multi()));
+// ---- the frame kinds.  apply: the kind's own last checks, its setter, its announcement; false = refused ----
+bool apply_mip(Options &) { for (int i = 0; i < PROFILER_RENDERERS; i++) renderers[i]->set_mip(true); printf("Maximum-intensity projection\n"); return true; }
+bool apply_iso(Options &o) { renderers[1]->set_iso(true, o.iso_level, (uint32_t) o.iso_refine); printf("Isosurface at level %g, %d bisection steps\n", o.iso_level, o.iso_refine); return true; }
+bool apply_hybrid(Options &o) {
+	renderers[1]->set_hybrid(true, o.iso_level, (uint32_t) o.iso_refine);
+	printf("Hybrid: isosurface at level %g, %d bisection steps, behind the composite\n", o.iso_level, o.iso_refine);
+	return true;
+}
+bool apply_section(Options &o) {
+	vr_section &section = o.section;
+	if (section.half_width > 0.0f && !o.section_mode_given) section.mode = VR_SECTION_MAX;      // a slab without a mode: the slab MIP
+	renderers[1]->set_section(true, section, o.section_in_volume);
+	printf("Section: plane %g x + %g y + %g z + %g = 0, half width %g, mode %s", section.plane[0], section.plane[1], section.plane[2], section.plane[3],
+	       section.half_width, section_mode_names[section.mode & 3u]);
+	if (section.window[0] != 0.0f || section.window[1] != 0.0f) printf(", grey window %g..%g", section.window[0], section.window[1]);
+	printf(o.section_in_volume ? ", behind the composite\n" : "\n");
+	return true;
+}
+bool apply_labels(Options &o) {
+	if (o.preint) { printf("Error: -labels excludes -preint: a slab between two labels has no single table entry\n"); return false; }
+	if (o.labels_octants && !o.labels_file.empty()) { printf("Error: -labels and -labels-octants exclude each other\n"); return false; }
+	if (!o.loaded) { printf("Error: -labels needs a volume\n"); return false; }
+	const uint32_t dims[3] = { ModelBase::volume.dims.x, ModelBase::volume.dims.y, ModelBase::volume.dims.z };
+	const size_t voxels = (size_t) dims[0] * dims[1] * dims[2];
+	std::vector<uint8_t> labels(voxels);
+	if (o.labels_octants) {                   // the label of a voxel is its octant: bit 0 the upper half in x, bit 1 in y, bit 2 in z
+		for (uint32_t z = 0; z < dims[2]; z++) for (uint32_t y = 0; y < dims[1]; y++) for (uint32_t x = 0; x < dims[0]; x++)
+			labels[((size_t) z * dims[1] + y) * dims[0] + x] = (uint8_t) ((x >= dims[0] / 2u ? 1u : 0u) | (y >= dims[1] / 2u ? 2u : 0u) | (z >= dims[2] / 2u ? 4u : 0u));
 	} else {
-		renderers[0] = new HipRenderer(RaycasterBase::raycaster, device, VR_SAMPLE_NEAREST);
-		renderers[1] = new HipRenderer(RaycasterBase::raycaster, device, VR_SAMPLE_TRILINEAR);
+		FILE *f = fopen(o.labels_file.c_str(), "rb");
+		const size_t got = f ? fread(labels.data(), 1, voxels, f) : 0;
+		const bool more = f && fgetc(f) != EOF;
+		if (f) fclose(f);
+		if (got != voxels || more) { printf("Error: -labels %s does not hold the %zu bytes of the volume's dims\n", o.labels_file.c_str(), voxels); return false; }
 	}
-	for (int i = 0; i < PROFILER_RENDERERS; i++)
-		if (!renderers[i]->ok()) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }
-	if (mip) {
-		if (!device_list.empty()) { printf("Error: -mip renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		for (int i = 0; i < PROFILER_RENDERERS; i++) renderers[i]->set_mip(true);
-		printf("Maximum-intensity projection\n");
-	}
+	if (!accepted(renderers[1], renderers[1]->set_labels(labels.data(), dims) != 0 || renderers[1]->set_label_table(o.label_table.data(), o.label_entries) != 0)) return false;
+	renderers[1]->set_labelled(true);
+	printf("Labels: %s, %u table entr%s\n", o.labels_octants ? "octants" : o.labels_file.c_str(), o.label_entries, o.label_entries == 1u ? "y" : "ies");
+	return true;
+}
 
-	if (iso) {
-		if (!device_list.empty()) { printf("Error: -iso renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		if (mip) { printf("Error: -iso and -mip exclude each other\n"); return EXIT_FAILURE; }
-		if (iso_refine < 0 || iso_refine > 16) { printf("Error: -refine must be in 0..16\n"); return EXIT_FAILURE; }
-		if (!benchmark_mode && renderer_id != 1) { printf("Error: -iso needs the trilinear renderer (-r 1): an isosurface is defined on the interpolated field\n"); return EXIT_FAILURE; }
-		renderers[1]->set_iso(true, iso_level, (uint32_t) iso_refine);
-		printf("Isosurface at level %g, %d bisection steps\n", iso_level, iso_refine);
-	}
+// One row per kind, walked in this order; a kind excludes every kind above it, so each pair is refused once, by the lower one.
+struct FrameKind {
+	const char *flag;                           // as the messages name the kind
+	bool (*given)(const Options &);
+	const char *excluded;                       // the answer to a kind above it on the same line
+	bool refines;                               // takes -refine
+	const char *trilinear_because;              // needs -r 1, for this reason (nullptr: either renderer) ...
+	bool nearest_in_benchmark;                  // ... but -b may keep -r 0, whose frames then stay composites
+	bool benchmark;                             // -b is allowed
+	bool (*apply)(Options &);                   // nullptr: the kind is a call of its own, not a state of the renderer
+	bool (*orphans)(const Options &);           // options of this kind given without it, and the answer to them
+	const char *orphaned;
+};
+const FrameKind kinds[] = {
+	{ "-mip", [](const Options &o) { return o.mip; }, nullptr, false, nullptr, false, true, apply_mip, nullptr, nullptr },
+	{ "-iso", [](const Options &o) { return o.iso; }, "Error: -iso and -mip exclude each other\n", true, "an isosurface is defined on the interpolated field", true, true, apply_iso, nullptr, nullptr },
+	{ "-hybrid", [](const Options &o) { return o.hybrid; }, "Error: -hybrid excludes -mip and -iso\n", true, "its surface is defined on the interpolated field", false, true, apply_hybrid, nullptr, nullptr },
+	{ "-section", [](const Options &o) { return o.section_on; }, "Error: -section excludes -mip, -iso and -hybrid\n", false, "a section is defined on the interpolated field", false, true, apply_section,
+	  [](const Options &o) { return o.section_in_volume || o.section_mode_given || o.section_window_given || o.section.half_width != 0.0f; },
+	  "Error: -section-half, -section-mode, -section-window and -section-in-volume need -section\n" },
+	{ "-depth", [](const Options &o) { return o.depth_on; }, "Error: -depth excludes -mip, -iso, -hybrid and -section\n", false, "a depth frame is defined on the interpolated field", false, false, nullptr,
+	  [](const Options &o) { return o.depth_mode_given || o.pick_on; }, "Error: -depth-mode and -pick need -depth\n" },
+	{ "-labels", [](const Options &o) { return o.labels_octants || !o.labels_file.empty(); }, "Error: -labels excludes -mip, -iso, -hybrid, -section and -depth\n", false,
+	  "a labelled frame is defined on the interpolated field", false, true, apply_labels, [](const Options &o) { return o.label_entries != 0u; }, "Error: -label entries need -labels or -labels-octants\n" },
+};
 
-	if (hybrid) {
-		if (!device_list.empty()) { printf("Error: -hybrid renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		if (mip || iso) { printf("Error: -hybrid excludes -mip and -iso\n"); return EXIT_FAILURE; }
-		if (iso_refine < 0 || iso_refine > 16) { printf("Error: -refine must be in 0..16\n"); return EXIT_FAILURE; }
-		if (renderer_id != 1) { printf("Error: -hybrid needs the trilinear renderer (-r 1): its surface is defined on the interpolated field\n"); return EXIT_FAILURE; }
-		renderers[1]->set_hybrid(true, iso_level, (uint32_t) iso_refine);
-		printf("Hybrid: isosurface at level %g, %d bisection steps, behind the composite\n", iso_level, iso_refine);
-	}
-
-	if (section_on) {
-		if (!device_list.empty()) { printf("Error: -section renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		if (mip || iso || hybrid) { printf("Error: -section excludes -mip, -iso and -hybrid\n"); return EXIT_FAILURE; }
-		if (renderer_id != 1) { printf("Error: -section needs the trilinear renderer (-r 1): a section is defined on the interpolated field\n"); return EXIT_FAILURE; }
-		if (section.half_width > 0.0f && !section_mode_given) section.mode = VR_SECTION_MAX;      // a slab without a mode: the slab MIP
-		renderers[1]->set_section(true, section, section_in_volume);
-		static const char *const mode_names[] = { "point", "max", "min", "mean" };
-		printf("Section: plane %g x + %g y + %g z + %g = 0, half width %g, mode %s", section.plane[0], section.plane[1], section.plane[2], section.plane[3],
-		       section.half_width, mode_names[section.mode & 3u]);
-		if (section.window[0] != 0.0f || section.window[1] != 0.0f) printf(", grey window %g..%g", section.window[0], section.window[1]);
-		printf(section_in_volume ? ", behind the composite\n" : "\n");
-	} else if (section_in_volume || section_mode_given || section_window_given || section.half_width != 0.0f) {
-		printf("Error: -section-half, -section-mode, -section-window and -section-in-volume need -section\n"); return EXIT_FAILURE;
-	}
-
-	static const char *const depth_mode_names[] = { "first", "peak", "mean" };
-	if (depth_on) {
-		if (!device_list.empty()) { printf("Error: -depth renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		if (mip || iso || hybrid || section_on) { printf("Error: -depth excludes -mip, -iso, -hybrid and -section\n"); return EXIT_FAILURE; }
-		if (renderer_id != 1) { printf("Error: -depth needs the trilinear renderer (-r 1): a depth frame is defined on the interpolated field\n"); return EXIT_FAILURE; }
-		if (benchmark_mode) { printf("Error: -depth renders single frames (drop -b)\n"); return EXIT_FAILURE; }
-	} else if (depth_mode_given || pick_on) {
-		printf("Error: -depth-mode and -pick need -depth\n"); return EXIT_FAILURE;
-	}
-
-	const bool labels_on = labels_octants || !labels_file.empty();
-	if (labels_on) {
-		if (!device_list.empty()) { printf("Error: -labels renders on a single device (drop -devices)\n"); return EXIT_FAILURE; }
-		if (mip || iso || hybrid || section_on || depth_on) { printf("Error: -labels excludes -mip, -iso, -hybrid, -section and -depth\n"); return EXIT_FAILURE; }
-		if (renderer_id != 1) { printf("Error: -labels needs the trilinear renderer (-r 1): a labelled frame is defined on the interpolated field\n"); return EXIT_FAILURE; }
-		if (preint) { printf("Error: -labels excludes -preint: a slab between two labels has no single table entry\n"); return EXIT_FAILURE; }
-		if (labels_octants && !labels_file.empty()) { printf("Error: -labels and -labels-octants exclude each other\n"); return EXIT_FAILURE; }
-		if (!loaded) { printf("Error: -labels needs a volume\n"); return EXIT_FAILURE; }
-		const uint32_t dims[3] = { ModelBase::volume.dims.x, ModelBase::volume.dims.y, ModelBase::volume.dims.z };
-		const size_t voxels = (size_t) dims[0] * dims[1] * dims[2];
-		std::vector<uint8_t> labels(voxels);
-		if (labels_octants) {                   // the label of a voxel is its octant: bit 0 the upper half in x, bit 1 in y, bit 2 in z
-			for (uint32_t z = 0; z < dims[2]; z++) for (uint32_t y = 0; y < dims[1]; y++) for (uint32_t x = 0; x < dims[0]; x++)
-				labels[((size_t) z * dims[1] + y) * dims[0] + x] = (uint8_t) ((x >= dims[0] / 2u ? 1u : 0u) | (y >= dims[1] / 2u ? 2u : 0u) | (z >= dims[2] / 2u ? 4u : 0u));
-		} else {
-			FILE *f = fopen(labels_file.c_str(), "rb");
-			const size_t got = f ? fread(labels.data(), 1, voxels, f) : 0;
-			const bool more = f && fgetc(f) != EOF;
-			if (f) fclose(f);
-			if (got != voxels || more) { printf("Error: -labels %s does not hold the %zu bytes of the volume's dims\n", labels_file.c_str(), voxels); return EXIT_FAILURE; }
+bool apply_kinds(Options &o) {
+	bool above = false;             // a kind above this one was given
+	for (const FrameKind &k : kinds) {
+		if (!k.given(o)) {
+			if (k.orphans != nullptr && k.orphans(o)) { printf("%s", k.orphaned); return false; }
+			continue;
 		}
-		if (renderers[1]->set_labels(labels.data(), dims) != 0 || renderers[1]->set_label_table(label_table.data(), label_entries) != 0) {
-			printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE;
+		if (!device_list.empty()) { printf("Error: %s renders on a single device (drop -devices)\n", k.flag); return false; }
+		if (above) { printf("%s", k.excluded); return false; }
+		if (k.refines && (o.iso_refine < 0 || o.iso_refine > 16)) { printf("Error: -refine must be in 0..16\n"); return false; }
+		if (k.trilinear_because != nullptr && renderer_id != 1 && !(k.nearest_in_benchmark && o.benchmark_mode)) {
+			printf("Error: %s needs the trilinear renderer (-r 1): %s\n", k.flag, k.trilinear_because); return false;
 		}
-		renderers[1]->set_labelled(true);
-		printf("Labels: %s, %u table entr%s\n", labels_octants ? "octants" : labels_file.c_str(), label_entries, label_entries == 1u ? "y" : "ies");
-	} else if (label_entries != 0u) {
-		printf("Error: -label entries need -labels or -labels-octants\n"); return EXIT_FAILURE;
+		if (!k.benchmark && o.benchmark_mode) { printf("Error: %s renders single frames (drop -b)\n", k.flag); return false; }
+		if (k.apply != nullptr && !k.apply(o)) return false;
+		above = true;
 	}
-	if (clip_box || clip_plane) {
+	return true;
+}
+
+// -shadow, -phong and -preint act on the composite of the trilinear renderer
+bool composite_option(const Options &o, const char *flag) {
+	if (o.mip || o.iso) { printf("Error: %s works with the composite (drop -mip / -iso)\n", flag); return false; }
+	if (!o.benchmark_mode && renderer_id != 1) { printf("Error: %s needs the trilinear renderer (-r 1)\n", flag); return false; }
+	return true;
+}
+
+// the clip, the start pose and the composite's options, in the order their announcements have
+bool apply_state(const Options &o) {
+	if (o.clip_box || o.clip_plane) {
+		const vr_clip &clip = o.clip;
 		for (int i = 0; i < PROFILER_RENDERERS; i++)
-			if (renderers[i]->set_clip(&clip) != 0) { printf("Error: %s\n", renderers[i]->last_error()); return EXIT_FAILURE; }
+			if (!accepted(renderers[i], renderers[i]->set_clip(&clip))) return false;
 		printf("Clip region:");
-		if (clip_box) printf(" box (%g, %g, %g) - (%g, %g, %g)", clip.box_min[0], clip.box_min[1], clip.box_min[2], clip.box_max[0], clip.box_max[1], clip.box_max[2]);
-		if (clip_plane) printf(" plane %g x + %g y + %g z + %g >= 0", clip.plane[0], clip.plane[1], clip.plane[2], clip.plane[3]);
+		if (o.clip_box) printf(" box (%g, %g, %g) - (%g, %g, %g)", clip.box_min[0], clip.box_min[1], clip.box_min[2], clip.box_max[0], clip.box_max[1], clip.box_max[2]);
+		if (o.clip_plane) printf(" plane %g x + %g y + %g z + %g >= 0", clip.plane[0], clip.plane[1], clip.plane[2], clip.plane[3]);
 		printf("\n");
 	}
-
-	int rc = EXIT_SUCCESS;
-	if (!benchmark_mode) {
-		if (persp) ViewBase::toggle_perspective(0);
-		ViewBase::set_camera_position(make_float3(pose[0], pose[1], pose[2]), have_pose ? pose[3] : 3.0f);
+	if (!o.benchmark_mode) {
+		if (o.persp) ViewBase::toggle_perspective(0);
+		ViewBase::set_camera_position(make_float3(o.pose[0], o.pose[1], o.pose[2]), o.have_pose ? o.pose[3] : 3.0f);
 	}
-	if (shadow_dims != 0) {
+	if (o.shadow_dims != 0) {
 		// the light is the view's (benchmark mode: the start view's — the reference's benchmark moves the camera, not the light); the
 		// trilinear renderer only: the light grid and its factor are defined on the interpolated field
-		if (mip || iso) { printf("Error: -shadow works with the composite (drop -mip / -iso)\n"); return EXIT_FAILURE; }
-		if (!benchmark_mode && renderer_id != 1) { printf("Error: -shadow needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
+		if (!composite_option(o, "-shadow")) return false;
 		vr_shadow sh;
 		sh.light_pos[0] = ViewBase::view.light_pos.x; sh.light_pos[1] = ViewBase::view.light_pos.y; sh.light_pos[2] = ViewBase::view.light_pos.z;
-		sh.dims = (uint32_t) shadow_dims; sh.step = shadow_step > 0.0f ? shadow_step : RaycasterBase::raycaster.ray_step;
-		sh.strength = shadow_strength; sh.cutoff = 1.0f / 256.0f; sh.sampling = VR_SAMPLE_TRILINEAR;
-		if (renderers[1]->set_shadow(&sh) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
-		printf("Shadow: %d^3 nodes, light (%g, %g, %g), step %g, strength %g\n", shadow_dims, sh.light_pos[0], sh.light_pos[1], sh.light_pos[2], sh.step, sh.strength);
+		sh.dims = (uint32_t) o.shadow_dims; sh.step = o.shadow_step > 0.0f ? o.shadow_step : RaycasterBase::raycaster.ray_step;
+		sh.strength = o.shadow_strength; sh.cutoff = 1.0f / 256.0f; sh.sampling = VR_SAMPLE_TRILINEAR;
+		if (!accepted(renderers[1], renderers[1]->set_shadow(&sh))) return false;
+		printf("Shadow: %d^3 nodes, light (%g, %g, %g), step %g, strength %g\n", o.shadow_dims, sh.light_pos[0], sh.light_pos[1], sh.light_pos[2], sh.step, sh.strength);
 	}
-	if (phong) {
-		if (mip || iso) { printf("Error: -phong works with the composite (drop -mip / -iso)\n"); return EXIT_FAILURE; }
-		if (!benchmark_mode && renderer_id != 1) { printf("Error: -phong needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
-		if (renderers[1]->set_lighting(&lighting) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
-		printf("Lighting: ambient %g, diffuse %g, specular %g, shininess 2^%u\n", lighting.ambient, lighting.diffuse, lighting.specular, lighting.shininess_log2);
+	if (o.phong) {
+		if (!composite_option(o, "-phong") || !accepted(renderers[1], renderers[1]->set_lighting(&o.lighting))) return false;
+		printf("Lighting: ambient %g, diffuse %g, specular %g, shininess 2^%u\n", o.lighting.ambient, o.lighting.diffuse, o.lighting.specular, o.lighting.shininess_log2);
 	}
-	if (preint) {
-		if (mip || iso) { printf("Error: -preint works with the composite (drop -mip / -iso)\n"); return EXIT_FAILURE; }
-		if (!benchmark_mode && renderer_id != 1) { printf("Error: -preint needs the trilinear renderer (-r 1)\n"); return EXIT_FAILURE; }
-		if (renderers[1]->set_preintegration(true) != 0) { printf("Error: %s\n", renderers[1]->last_error()); return EXIT_FAILURE; }
+	if (o.preint) {
+		if (!composite_option(o, "-preint") || !accepted(renderers[1], renderers[1]->set_preintegration(true))) return false;
 		printf("Classification: pre-integrated (slab)\n");
 	}
-	if (benchmark_mode) {
+	return true;
+}
+
+// the benchmark matrix, one depth frame (with its pick) or one frame; the exit status
+int run(const Options &o) {
+	int rc = EXIT_SUCCESS;
+	if (o.benchmark_mode) {
 		benchmark();
 		print_profiler();
-	} else if (depth_on) {
+	} else if (o.depth_on) {
 		std::vector<float> depth;
-		if (draw_depth(depth_params, depth) != 0) { printf("Error: %s\n", renderers[1]->last_error()); rc = EXIT_FAILURE; }
-		else {
-			size_t surfaces = 0;
-			for (float d : depth) surfaces += d >= 0.0f ? 1u : 0u;
-			printf("Depth: mode %s, opacity %g: %zu of %zu pixels carry a surface\n", depth_mode_names[depth_params.mode], depth_params.opacity, surfaces, depth.size());
-			printf("%s: %dx%d depth frame in %.2f ms\n", renderers[1]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);
-			if (pick_on) {
-				vr_pick pk;
-				if (renderers[1]->pick(RaycasterBase::raycaster, depth_params, 1u, pick_xy, &pk) != 0) { printf("Error: %s\n", renderers[1]->last_error()); rc = EXIT_FAILURE; }
-				else printf("Pick (%u, %u): hit %u k %.9g position (%.9g, %.9g, %.9g) voxel (%.9g, %.9g, %.9g) value %.9g alpha %.9g\n", pick_xy[0], pick_xy[1], pk.hit, pk.k,
-				            pk.position[0], pk.position[1], pk.position[2], pk.voxel[0], pk.voxel[1], pk.voxel[2], pk.value, pk.alpha);
-			}
-			if (!out_ppm.empty() && write_depth_ppm(out_ppm.c_str(), depth) != 0) { printf("Error: cannot write %s\n", out_ppm.c_str()); rc = EXIT_FAILURE; }
+		if (!accepted(renderers[1], draw_depth(o.depth, depth))) return EXIT_FAILURE;
+		size_t surfaces = 0;
+		for (float d : depth) surfaces += d >= 0.0f ? 1u : 0u;
+		printf("Depth: mode %s, opacity %g: %zu of %zu pixels carry a surface\n", depth_mode_names[o.depth.mode], o.depth.opacity, surfaces, depth.size());
+		printf("%s: %dx%d depth frame in %.2f ms\n", renderers[1]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);
+		if (o.pick_on) {
+			vr_pick pk;
+			if (!accepted(renderers[1], renderers[1]->pick(RaycasterBase::raycaster, o.depth, 1u, o.pick_xy, &pk))) rc = EXIT_FAILURE;
+			else printf("Pick (%u, %u): hit %u k %.9g position (%.9g, %.9g, %.9g) voxel (%.9g, %.9g, %.9g) value %.9g alpha %.9g\n", o.pick_xy[0], o.pick_xy[1], pk.hit, pk.k,
+			            pk.position[0], pk.position[1], pk.position[2], pk.voxel[0], pk.voxel[1], pk.voxel[2], pk.value, pk.alpha);
 		}
+		if (!o.out_ppm.empty() && write_depth_ppm(o.out_ppm.c_str(), depth) != 0) { printf("Error: cannot write %s\n", o.out_ppm.c_str()); rc = EXIT_FAILURE; }
 	} else {
 		draw_volume();
 		printf("%s: %dx%d frame in %.2f ms\n", renderers[renderer_id]->get_name(), ViewBase::view.dims.x, ViewBase::view.dims.y, Profiler::time_ms);
-		if (!out_ppm.empty() && write_ppm(out_ppm.c_str()) != 0) { printf("Error: cannot write %s\n", out_ppm.c_str()); rc = EXIT_FAILURE; }
+		if (!o.out_ppm.empty() && write_ppm(o.out_ppm.c_str()) != 0) { printf("Error: cannot write %s\n", o.out_ppm.c_str()); rc = EXIT_FAILURE; }
 	}
+	return rc;
+}
+
+}  // namespace
+
+// parse, load, create, apply the kind, apply the state, run.  Nothing is validated before the renderers exist: a refused line prints
+// what the reference's start-up prints up to there.
+int main(int argc, char **argv) {
+	Options o;
+	ViewBase::reset();
+	const int ended = parse(argc, argv, o);
+	if (ended >= 0) return ended;
+
+	// VolR.cpp:412-417
+	o.loaded = !o.file_name.empty() && ModelBase::load_model(o.file_name.c_str()) == 0;
+	if (!o.loaded) o.loaded = use_synthetic();
+	if (!o.loaded && !o.benchmark_mode) { printf("Warning: no volume data loaded (use -f or -synthetic).\n"); return EXIT_FAILURE; }
+	RaycasterBase::set_view(ViewBase::view);
+	RaycasterBase::reset_transfer_fn();
+	if (o.loaded) RaycasterBase::set_volume(ModelBase::volume);
+	Profiler::init();
+
+	printf("Initializing renderers 0 - %d...\n", PROFILER_RENDERERS - 1);
+	for (int i = 0; i < PROFILER_RENDERERS; i++)
+		renderers[i] = device_list.empty() ? new HipRenderer(RaycasterBase::raycaster, device, i == 0 ? VR_SAMPLE_NEAREST : VR_SAMPLE_TRILINEAR)
+		                                   : new HipRenderer(RaycasterBase::raycaster, device_list.data(), (int) device_list.size(), i == 0 ? VR_SAMPLE_NEAREST : VR_SAMPLE_TRILINEAR);
+	if (!device_list.empty() && renderers[1]->ok()) printf("Frame split over %d device(s), bands gathered by %s\n", (int) device_list.size(), vr_hip_multi_transport(renderers[1]->multi()));
+	for (int i = 0; i < PROFILER_RENDERERS; i++)
+		if (!accepted(renderers[i], renderers[i]->ok() ? 0 : 1)) return EXIT_FAILURE;
+
+	if (!apply_kinds(o) || !apply_state(o)) return EXIT_FAILURE;
+	const int rc = run(o);
 	for (int i = PROFILER_RENDERERS - 1; i >= 0; i--) delete renderers[i];      // reverse order like VolR.cpp:328-329
 	return rc;
 }

@@ -197,6 +197,14 @@ int retire(vr_multi *m, int slot) {
 	return VR_OK;
 }
 
+// one vr_hip_* setter on every device's context, in rank order; stops at the first failure, which becomes the list's error
+template <typename... Params, typename... Args>
+int on_every_context(vr_multi *m, int (*entry)(vr_ctx *, Params...), Args... args) {
+	if (m == nullptr) return VR_ERR_INVALID;
+	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, entry(m->ctx[r], args...)); if (rc) return rc; }
+	return VR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,53 +351,21 @@ int vr_hip_multi_set_window(vr_multi *m, uint32_t w, uint32_t h) {
 	return VR_OK;
 }
 
-int vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf, const uint32_t *esl) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_transfer_fn(m->ctx[r], tf, esl)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_transfer_fn(vr_multi *m, const float *tf, const uint32_t *esl) { return on_every_context(m, vr_hip_set_transfer_fn, tf, esl); }
 
-int vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_shadow(m->ctx[r], shadow)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_shadow(vr_multi *m, const vr_shadow *shadow) { return on_every_context(m, vr_hip_set_shadow, shadow); }
 
-int vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_lighting(m->ctx[r], lighting)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_lighting(vr_multi *m, const vr_lighting *lighting) { return on_every_context(m, vr_hip_set_lighting, lighting); }
 
-int vr_hip_multi_set_preintegration(vr_multi *m, uint32_t on) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_preintegration(m->ctx[r], on)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_preintegration(vr_multi *m, uint32_t on) { return on_every_context(m, vr_hip_set_preintegration, on); }
 
-int vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_clip(m->ctx[r], clip)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_clip(vr_multi *m, const vr_clip *clip) { return on_every_context(m, vr_hip_set_clip, clip); }
 
-int vr_hip_multi_set_volume(vr_multi *m, const void *host, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_set_volume(m->ctx[r], host, x, y, z, bpv)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_set_volume(vr_multi *m, const void *host, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) { return on_every_context(m, vr_hip_set_volume, host, x, y, z, bpv); }
 
-int vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bpv) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_generate_volume(m->ctx[r], kind, n, seed, bpv)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_generate_volume(vr_multi *m, uint32_t kind, uint32_t n, uint32_t seed, uint32_t bpv) { return on_every_context(m, vr_hip_generate_volume, kind, n, seed, bpv); }
 
-int vr_hip_multi_prepare(vr_multi *m, uint32_t copies) {
-	if (m == nullptr) return VR_ERR_INVALID;
-	for (int r = 0; r < m->n; r++) { int rc = forward(m, r, vr_hip_prepare(m->ctx[r], copies)); if (rc) return rc; }
-	return VR_OK;
-}
+int vr_hip_multi_prepare(vr_multi *m, uint32_t copies) { return on_every_context(m, vr_hip_prepare, copies); }
 
 // Queues one whole frame into `dev_rgba` on devices[0] and returns without waiting for it.  At most kFrames (three) frames are in
 // flight: the call first waits for the frame queued three calls ago (its band buffers are this frame's); frames in flight must not

@@ -4,11 +4,75 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import (VrBackdrop, VrDepthOut, VrError, VrIso, VrLabelEntry, VrLaunchInfo, VrParams, VrPick, VrTiming, lib, make_clip, make_depth, make_label_entry,
-                      make_lighting, make_section, make_shadow)
+from .binding import (VrBackdrop, VrDepthOut, VrError, VrIso, VrLabelEntry, VrLaunchInfo, VrPick, VrRunAlignedInfo, VrTiming, VrVolumeInfo, lib, make_clip, make_depth,
+                      make_label_entry, make_lighting, make_section, make_shadow)
 
 
-class HipRenderer:
+def _rgba(params):
+    """the (out_rows, out_width, 4) uint8 array a host-buffer frame fills"""
+    return np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
+
+
+def _floats(params, wanted=True):
+    """the (out_rows, out_width) float32 array of an optional host buffer (depth, value, alpha), None when it is not wanted"""
+    return np.empty((params.out_rows, params.out_width), dtype=np.float32) if wanted else None
+
+
+def _address(array):
+    return array.ctypes.data if array is not None else None
+
+
+def _ptr(address):
+    """an optional device address or raw hipStream_t as the ABI takes it: NULL for None / 0"""
+    return C.c_void_p(address) if address else None
+
+
+class _Frames:
+    """What HipRenderer and MultiRenderer share: the one call every frame goes through, and the shadow whose march step waits for a frame.
+    The class names its handle (_handle) and its shadow setter (_SET_SHADOW) and brings _L and _check."""
+
+    def _frame(self, what, entry, params, *args, composite):
+        """One frame: `entry`(handle, params, *args).  A composite-type frame (the composite itself and everything that runs a composite
+        pass: backdrop, hybrid, section in volume, labelled) first resolves a pending set_shadow(step=None); every other frame does not."""
+        if composite:
+            self._resolve_shadow(params.ray_step)
+        self._check(getattr(self._L, entry)(self._handle, C.byref(params), *args), what)
+
+    def _host_frame(self, what, entry, params, *args, composite, depth=None):
+        """A host-buffer frame: `entry`(handle, params, *args, rgba[, depth]) into fresh arrays -> rgba, or (rgba, depth) for depth=True;
+        depth=None: the entry takes no depth buffer."""
+        out, dep = _rgba(params), _floats(params, bool(depth))
+        self._frame(what, entry, params, *args, out.ctypes.data, *(() if depth is None else (_address(dep),)), composite=composite)
+        return (out, dep) if depth else out
+
+    def _set_shadow(self, shadow, what):
+        self._check(getattr(self._L, self._SET_SHADOW)(self._handle, C.byref(shadow) if shadow is not None else None), what)
+
+    def _hold_shadow(self, light_pos, dims, step, strength, cutoff, sampling):
+        """set_shadow of both classes: step=None keeps the arguments in _shadow until a frame's ray_step resolves the step"""
+        pending = None
+        if step is None:
+            pending = dict(light_pos=tuple(float(v) for v in light_pos), dims=dims, strength=strength, cutoff=cutoff, sampling=sampling)
+            step = 0.01                  # validated now with a placeholder, set again with the frame's ray_step (an identical struct rebuilds nothing)
+        self._set_shadow(make_shadow(light_pos, dims, step, strength, cutoff, sampling), "set_shadow")
+        self._shadow = pending           # (a refused shadow leaves the one before in place)
+
+    def clear_shadow(self):
+        """Shadows off (the default)."""
+        self._shadow = None
+        self._set_shadow(None, "clear_shadow")
+
+    def _resolve_shadow(self, ray_step):
+        """a set_shadow(step=None) takes this step, once"""
+        if self._shadow is not None:
+            self._set_shadow(make_shadow(step=float(ray_step), **self._shadow), "set_shadow")
+            self._shadow = None
+
+
+class HipRenderer(_Frames):
+    _SET_SHADOW = "vr_hip_set_shadow"
+    _handle = property(lambda self: self._ctx)
+
     def __init__(self, device=0):
         self._L = lib()
         self._ctx = C.c_void_p()
@@ -39,6 +103,12 @@ class HipRenderer:
     def _check(self, rc, what):
         if rc:
             raise VrError(rc, f"{what}: {self._L.vr_hip_last_error(self._ctx).decode()}")
+
+    def _counter(self, what, entry):
+        """one of the testing aids that count the frames a family of kernels launched"""
+        n = C.c_uint64(0)
+        self._check(entry(self._ctx, C.byref(n)), what)
+        return int(n.value)
 
     def get_name(self):
         return "HIP MI355X"
@@ -91,7 +161,6 @@ class HipRenderer:
 
     def run_aligned_info(self):
         """vr_run_aligned_info: dict(flavour, last_flavour (0 no run bricks, 1 nine-element, 2 aligned), copies, copies_refused, bytes, build_ms (z, y))."""
-        from .binding import VrRunAlignedInfo
         info = VrRunAlignedInfo()
         self._check(self._L.vr_hip_run_aligned_info(self._ctx, C.byref(info)), "run_aligned_info")
         return {"flavour": int(info.flavour), "last_flavour": int(info.last_flavour), "copies": int(info.copies), "copies_refused": int(info.copies_refused),
@@ -122,23 +191,7 @@ class HipRenderer:
         cutoff = the transmittance below which a light ray is black; sampling = how the builder samples the volume.  The frames must be
         TRILINEAR / TRILINEAR_Q8; MIP and isosurface frames ignore the shadow.  The light of the frames' own shading is params.view.light_pos:
         set it to the same point for a consistent picture."""
-        pending = None
-        if step is None:
-            pending = dict(light_pos=tuple(float(v) for v in light_pos), dims=dims, strength=strength, cutoff=cutoff, sampling=sampling)
-            step = 0.01                  # validated now with a placeholder, set again with the frame's ray_step (an identical struct rebuilds nothing)
-        self._check(self._L.vr_hip_set_shadow(self._ctx, C.byref(make_shadow(light_pos, dims, step, strength, cutoff, sampling))), "set_shadow")
-        self._shadow = pending           # (a refused shadow leaves the one before in place)
-
-    def clear_shadow(self):
-        """Shadows off (the default)."""
-        self._shadow = None
-        self._check(self._L.vr_hip_set_shadow(self._ctx, None), "clear_shadow")
-
-    def _resolve_shadow(self, ray_step):
-        """a set_shadow(step=None) takes this step, once"""
-        if self._shadow is not None:
-            self._check(self._L.vr_hip_set_shadow(self._ctx, C.byref(make_shadow(step=float(ray_step), **self._shadow))), "set_shadow")
-            self._shadow = None
+        self._hold_shadow(light_pos, dims, step, strength, cutoff, sampling)
 
     def download_shadow(self, ray_step=None):
         """vr_hip_download_shadow: the light grid as a (S, S, S) uint8 array indexed [z, y, x], 255 = fully lit; builds it if stale.  After a
@@ -172,9 +225,7 @@ class HipRenderer:
 
     def lighting_frames(self):
         """vr_hip_lighting_frames: the composite frames this context launched on the gradient-lit kernels"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_lighting_frames(self._ctx, C.byref(n)), "lighting_frames")
-        return int(n.value)
+        return self._counter("lighting_frames", self._L.vr_hip_lighting_frames)
 
     def set_preintegration(self, on=True):
         """vr_hip_set_preintegration: every later COMPOSITE frame classifies the slab between two consecutive samples — the mean of the
@@ -189,13 +240,10 @@ class HipRenderer:
 
     def preint_frames(self):
         """vr_hip_preint_frames: the composite frames this context launched on the slab kernels"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_preint_frames(self._ctx, C.byref(n)), "preint_frames")
-        return int(n.value)
+        return self._counter("preint_frames", self._L.vr_hip_preint_frames)
 
     def download_tf_integral(self):
         """vr_hip_download_tf_integral: K as uploaded, [128, 4] float32"""
-        import numpy as np
         out = np.zeros((128, 4), np.float32)
         self._check(self._L.vr_hip_download_tf_integral(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "download_tf_integral")
         return out
@@ -211,7 +259,6 @@ class HipRenderer:
 
     def tile_costs(self):
         """Cost map of the last frame rendered with set_tile_scheduling(2): [tiles_y, tiles_x] uint32, 64-cycle units per workgroup tile."""
-        import numpy as np
         tx, ty = C.c_uint32(0), C.c_uint32(0)
         self._check(self._L.vr_hip_read_tile_costs(self._ctx, None, 0, C.byref(tx), C.byref(ty)), "read_tile_costs")
         out = np.zeros((ty.value, tx.value), dtype=np.uint32)
@@ -233,28 +280,20 @@ class HipRenderer:
     # -- Renderer::render_volume
     def render_volume(self, params):
         """Host-buffer flavour (reference renderer ids 0-2): returns an (out_rows, out_width, 4) uint8 array."""
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render(self._ctx, C.byref(params), out.ctypes.data), "render_volume")
-        return out
+        return self._host_frame("render_volume", "vr_hip_render", params, composite=True)
 
     def render_volume_device(self, params, dev_ptr, stream=None):
         """Device-buffer flavour (ids 3-4): asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
-                                                 C.c_void_p(stream) if stream else None), "render_volume_device")
+        self._frame("render_volume_device", "vr_hip_render_device", params, C.c_void_p(dev_ptr), _ptr(stream), composite=True)
 
     # -- maximum-intensity projection (vr_hip_render_mip: the maximum sample of every ray through one transfer-function lookup)
     def render_mip(self, params):
         """Host-buffer flavour: returns an (out_rows, out_width, 4) uint8 array.  params.esl != 0 = exact fetch skipping by block maxima."""
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        self._check(self._L.vr_hip_render_mip(self._ctx, C.byref(params), out.ctypes.data), "render_mip")
-        return out
+        return self._host_frame("render_mip", "vr_hip_render_mip", params, composite=False)
 
     def render_mip_device(self, params, dev_ptr, stream=None):
         """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
-        self._check(self._L.vr_hip_render_mip_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr),
-                                                     C.c_void_p(stream) if stream else None), "render_mip_device")
+        self._frame("render_mip_device", "vr_hip_render_mip_device", params, C.c_void_p(dev_ptr), _ptr(stream), composite=False)
 
     # -- shaded isosurface with depth (vr_hip_render_iso: the first sample along every ray that reaches `level`, refined by bisection)
     def render_iso(self, params, level, refine=4, depth=False):
@@ -262,17 +301,12 @@ class HipRenderer:
         (out_rows, out_width), the ray parameter k of the surface point (position = origin + direction * k of the pixel's own ray; the
         perspective direction is not normalised) and -1 where there is none.  `level` in raw voxel units; params.sampling must be one of
         the TRILINEAR modes; params.esl != 0 = exact fetch skipping by block maxima."""
-        iso = VrIso(float(level), int(refine))
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
-        self._check(self._L.vr_hip_render_iso(self._ctx, C.byref(params), C.byref(iso), out.ctypes.data, dep.ctypes.data if depth else None), "render_iso")
-        return (out, dep) if depth else out
+        return self._host_frame("render_iso", "vr_hip_render_iso", params, C.byref(VrIso(float(level), int(refine))), composite=False, depth=bool(depth))
 
     def render_iso_device(self, params, level, refine, dev_ptr, depth_ptr=None, stream=None):
         """Device-buffer flavour: asynchronous launch into `dev_ptr` (RGBA8) and, if given, `depth_ptr` (float32) on `stream` (raw hipStream_t or None)."""
-        iso = VrIso(float(level), int(refine))
-        self._check(self._L.vr_hip_render_iso_device(self._ctx, C.byref(params), C.byref(iso), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
-                                                     C.c_void_p(stream) if stream else None), "render_iso_device")
+        self._frame("render_iso_device", "vr_hip_render_iso_device", params, C.byref(VrIso(float(level), int(refine))), C.c_void_p(dev_ptr), _ptr(depth_ptr), _ptr(stream),
+                    composite=False)
 
     # -- backdrop and hybrid (vr_hip_render_backdrop / vr_hip_render_hybrid: a composite frame that stops at an opaque layer and blends over it)
     def render_backdrop(self, params, rgba, depth):
@@ -284,43 +318,28 @@ class HipRenderer:
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         if rgba.size != params.out_rows * params.out_width * 4 or depth.size != params.out_rows * params.out_width:
             raise ValueError("render_backdrop: the layers must have out_rows * out_width pixels")
-        layer = VrBackdrop(rgba.ctypes.data, depth.ctypes.data)
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_backdrop(self._ctx, C.byref(params), C.byref(layer), out.ctypes.data), "render_backdrop")
-        return out
+        return self._host_frame("render_backdrop", "vr_hip_render_backdrop", params, C.byref(VrBackdrop(rgba.ctypes.data, depth.ctypes.data)), composite=True)
 
     def render_backdrop_device(self, params, rgba_ptr, depth_ptr, dev_ptr, stream=None):
         """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None); the layers are device addresses,
         and `dev_ptr` may be `rgba_ptr` (in place)."""
-        layer = VrBackdrop(rgba_ptr or None, depth_ptr or None)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_backdrop_device(self._ctx, C.byref(params), C.byref(layer), C.c_void_p(dev_ptr),
-                                                          C.c_void_p(stream) if stream else None), "render_backdrop_device")
+        self._frame("render_backdrop_device", "vr_hip_render_backdrop_device", params, C.byref(VrBackdrop(rgba_ptr or None, depth_ptr or None)), C.c_void_p(dev_ptr), _ptr(stream),
+                    composite=True)
 
     def render_hybrid(self, params, level, refine=4, depth=False):
         """Host-buffer flavour of the hybrid: the isosurface of `level` (render_iso with the same arguments) seen through the translucent
         volume in front of it.  An (out_rows, out_width, 4) uint8 array, or with depth=True (rgba, depth): the isosurface's depth."""
-        iso = VrIso(float(level), int(refine))
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_hybrid(self._ctx, C.byref(params), C.byref(iso), out.ctypes.data, dep.ctypes.data if depth else None), "render_hybrid")
-        return (out, dep) if depth else out
+        return self._host_frame("render_hybrid", "vr_hip_render_hybrid", params, C.byref(VrIso(float(level), int(refine))), composite=True, depth=bool(depth))
 
     def render_hybrid_device(self, params, level, refine, dev_ptr, depth_ptr=None, stream=None):
         """Device-buffer flavour: the isosurface frame into `dev_ptr` and `depth_ptr` (a context-owned buffer when None), then the backdrop
         frame in place, both on `stream` (raw hipStream_t or None)."""
-        iso = VrIso(float(level), int(refine))
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_hybrid_device(self._ctx, C.byref(params), C.byref(iso), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
-                                                        C.c_void_p(stream) if stream else None), "render_hybrid_device")
+        self._frame("render_hybrid_device", "vr_hip_render_hybrid_device", params, C.byref(VrIso(float(level), int(refine))), C.c_void_p(dev_ptr), _ptr(depth_ptr), _ptr(stream),
+                    composite=True)
 
     def backdrop_frames(self):
         """vr_hip_backdrop_frames: the composite frames this context launched on the backdrop kernels"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_backdrop_frames(self._ctx, C.byref(n)), "backdrop_frames")
-        return int(n.value)
+        return self._counter("backdrop_frames", self._L.vr_hip_backdrop_frames)
 
     # -- section frames (vr_hip_render_section: the oblique slice through the interpolated field, its thick-slab MIP / MinIP / mean, with depth)
     def render_section(self, params, plane, half_width=0.0, mode="point", window=None, depth=False):
@@ -329,44 +348,29 @@ class HipRenderer:
         point (thick modes: of the slab's front face) on the pixel's own ray, -1 where there is none.  mode "point", or with half_width > 0
         "max", "min", "mean" over the slab; window (lo, hi) in raw voxel units = opaque grey, None = the transfer function.
         params.sampling must be one of the TRILINEAR modes."""
-        sec = make_section(plane, half_width, mode, window)
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
-        self._check(self._L.vr_hip_render_section(self._ctx, C.byref(params), C.byref(sec), out.ctypes.data, dep.ctypes.data if depth else None), "render_section")
-        return (out, dep) if depth else out
+        return self._host_frame("render_section", "vr_hip_render_section", params, C.byref(make_section(plane, half_width, mode, window)), composite=False, depth=bool(depth))
 
     def render_section_device(self, params, plane, half_width, mode, window, dev_ptr, depth_ptr=None, stream=None):
         """Device-buffer flavour: asynchronous launch into `dev_ptr` (RGBA8) and, if given, `depth_ptr` (float32) on `stream` (raw hipStream_t or None)."""
-        sec = make_section(plane, half_width, mode, window)
-        self._check(self._L.vr_hip_render_section_device(self._ctx, C.byref(params), C.byref(sec), C.c_void_p(dev_ptr), C.c_void_p(depth_ptr) if depth_ptr else None,
-                                                         C.c_void_p(stream) if stream else None), "render_section_device")
+        self._frame("render_section_device", "vr_hip_render_section_device", params, C.byref(make_section(plane, half_width, mode, window)), C.c_void_p(dev_ptr), _ptr(depth_ptr),
+                    _ptr(stream), composite=False)
 
     def render_section_in_volume(self, params, plane, half_width=0.0, mode="point", window=None, depth=False):
         """Host-buffer flavour of the section inside the volume: render_section with the same arguments seen through the translucent volume
         in front of it (the context's clip, shadow, lighting and pre-integration apply to the composite pass).  An (out_rows, out_width, 4)
         uint8 array, or with depth=True (rgba, depth): the section's depth."""
-        sec = make_section(plane, half_width, mode, window)
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        dep = np.empty((params.out_rows, params.out_width), dtype=np.float32) if depth else None
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_section_in_volume(self._ctx, C.byref(params), C.byref(sec), out.ctypes.data, dep.ctypes.data if depth else None),
-                    "render_section_in_volume")
-        return (out, dep) if depth else out
+        return self._host_frame("render_section_in_volume", "vr_hip_render_section_in_volume", params, C.byref(make_section(plane, half_width, mode, window)), composite=True,
+                                depth=bool(depth))
 
     def render_section_in_volume_device(self, params, plane, half_width, mode, window, dev_ptr, depth_ptr=None, stream=None):
         """Device-buffer flavour: the section frame into `dev_ptr` and `depth_ptr` (a context-owned buffer when None), then the backdrop frame
         in place, both on `stream` (raw hipStream_t or None)."""
-        sec = make_section(plane, half_width, mode, window)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_section_in_volume_device(self._ctx, C.byref(params), C.byref(sec), C.c_void_p(dev_ptr),
-                                                                   C.c_void_p(depth_ptr) if depth_ptr else None, C.c_void_p(stream) if stream else None),
-                    "render_section_in_volume_device")
+        self._frame("render_section_in_volume_device", "vr_hip_render_section_in_volume_device", params, C.byref(make_section(plane, half_width, mode, window)), C.c_void_p(dev_ptr),
+                    _ptr(depth_ptr), _ptr(stream), composite=True)
 
     def section_frames(self):
         """vr_hip_section_frames: the section frames this context launched"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_section_frames(self._ctx, C.byref(n)), "section_frames")
-        return int(n.value)
+        return self._counter("section_frames", self._L.vr_hip_section_frames)
 
     # -- depth frames of the composite and picking (vr_hip_render_depth, vr_hip_pick)
     def render_depth(self, params, opacity, mode="first", value=False, alpha=False):
@@ -375,23 +379,17 @@ class HipRenderer:
         sample that contributes most) or "mean" (the contribution-weighted mean).  value=True adds the interpolated raw value there, alpha=True
         the pixel's final alpha — the alpha channel of the composite frame before it becomes a byte: (depth[, value][, alpha]).  The
         context's clip and pre-integration apply; shadow and lighting are ignored.  params.sampling must be one of the TRILINEAR modes."""
-        d = make_depth(opacity, mode)
-        shape = (params.out_rows, params.out_width)
-        dep = np.empty(shape, dtype=np.float32)
-        val = np.empty(shape, dtype=np.float32) if value else None
-        alp = np.empty(shape, dtype=np.float32) if alpha else None
-        out = VrDepthOut(dep.ctypes.data, val.ctypes.data if value else None, alp.ctypes.data if alpha else None)
-        self._check(self._L.vr_hip_render_depth(self._ctx, C.byref(params), C.byref(d), C.byref(out)), "render_depth")
-        got = (dep,) + ((val,) if value else ()) + ((alp,) if alpha else ())
+        dep, val, alp = _floats(params), _floats(params, value), _floats(params, alpha)
+        out = VrDepthOut(dep.ctypes.data, _address(val), _address(alp))
+        self._frame("render_depth", "vr_hip_render_depth", params, C.byref(make_depth(opacity, mode)), C.byref(out), composite=False)
+        got = tuple(a for a in (dep, val, alp) if a is not None)
         return got if len(got) > 1 else dep
 
     def render_depth_device(self, params, opacity, mode, depth_ptr, value_ptr=None, alpha_ptr=None, stream=None):
         """Device-buffer flavour: asynchronous launch into `depth_ptr` and, if given, `value_ptr` and `alpha_ptr` (float32 each) on `stream`
         (raw hipStream_t or None)."""
-        d = make_depth(opacity, mode)
-        out = VrDepthOut(depth_ptr if depth_ptr else None, value_ptr if value_ptr else None, alpha_ptr if alpha_ptr else None)
-        self._check(self._L.vr_hip_render_depth_device(self._ctx, C.byref(params), C.byref(d), C.byref(out), C.c_void_p(stream) if stream else None),
-                    "render_depth_device")
+        out = VrDepthOut(depth_ptr or None, value_ptr or None, alpha_ptr or None)
+        self._frame("render_depth_device", "vr_hip_render_depth_device", params, C.byref(make_depth(opacity, mode)), C.byref(out), _ptr(stream), composite=False)
 
     def pick(self, params, pixels, opacity, mode="first"):
         """What a whole-frame depth frame of `params` stores at each of `pixels` ((x, y) pairs of the view, y up; at most 256), as a list of
@@ -409,9 +407,7 @@ class HipRenderer:
 
     def depth_frames(self):
         """vr_hip_depth_frames: the depth frames this context launched (a pick counts one per pixel)"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_depth_frames(self._ctx, C.byref(n)), "depth_frames")
-        return int(n.value)
+        return self._counter("depth_frames", self._L.vr_hip_depth_frames)
 
     # -- label volumes (vr_hip_set_labels, vr_hip_set_label_table, vr_hip_render_labelled: per-segment colour and visibility for composite frames)
     def set_labels(self, labels):
@@ -450,22 +446,15 @@ class HipRenderer:
     def render_labelled(self, params):
         """Host-buffer flavour: the composite frame with every sample's colour passed through the table entry of its nearest voxel's label; an
         (out_rows, out_width, 4) uint8 array.  The context's clip, lighting and shadow apply; params.sampling must be one of the TRILINEAR modes."""
-        out = np.empty((params.out_rows, params.out_width, 4), dtype=np.uint8)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_labelled(self._ctx, C.byref(params), out.ctypes.data), "render_labelled")
-        return out
+        return self._host_frame("render_labelled", "vr_hip_render_labelled", params, composite=True)
 
     def render_labelled_device(self, params, dev_ptr, stream=None):
         """Device-buffer flavour: asynchronous launch into `dev_ptr` on `stream` (raw hipStream_t or None)."""
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_render_labelled_device(self._ctx, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream) if stream else None),
-                    "render_labelled_device")
+        self._frame("render_labelled_device", "vr_hip_render_labelled_device", params, C.c_void_p(dev_ptr), _ptr(stream), composite=True)
 
     def labelled_frames(self):
         """vr_hip_labelled_frames: the labelled frames this context launched"""
-        n = C.c_uint64(0)
-        self._check(self._L.vr_hip_labelled_frames(self._ctx, C.byref(n)), "labelled_frames")
-        return int(n.value)
+        return self._counter("labelled_frames", self._L.vr_hip_labelled_frames)
 
     # -- timing (Profiler.cpp:46-67)
     def timing(self):
@@ -493,7 +482,6 @@ class HipRenderer:
 
     def volume_info(self):
         """vr_volume_info: what the resident volume occupies (how many brick copies were actually built, linear array present)."""
-        from .binding import VrVolumeInfo
         info = VrVolumeInfo()
         self._check(self._L.vr_hip_volume_info(self._ctx, C.byref(info)), "volume_info")
         return info
@@ -523,9 +511,11 @@ class HipRenderer:
         return name.value.decode(), int(cus.value), int(mem.value)
 
 
-class MultiRenderer:
+class MultiRenderer(_Frames):
     """Several GPUs of ONE process behind one render call (vr_hip_multi_* of include/vr_hip.h): interleaved bands per device,
     gathered on devices[0] over xGMI (RCCL send/recv, or peer copies), de-interleaved there.  `params` describe the whole frame."""
+    _SET_SHADOW = "vr_hip_multi_set_shadow"
+    _handle = property(lambda self: self._m)
 
     def __init__(self, devices):
         self._L = lib()
@@ -578,21 +568,7 @@ class MultiRenderer:
     def set_shadow(self, light_pos, dims=128, step=None, strength=1.0, cutoff=1.0 / 256.0, sampling=1):
         """vr_hip_multi_set_shadow: HipRenderer.set_shadow on every device's context (every device builds its own light grid); step=None
         is resolved once, by the next frame's ray_step."""
-        pending = None
-        if step is None:
-            pending = dict(light_pos=tuple(float(v) for v in light_pos), dims=dims, strength=strength, cutoff=cutoff, sampling=sampling)
-            step = 0.01
-        self._check(self._L.vr_hip_multi_set_shadow(self._m, C.byref(make_shadow(light_pos, dims, step, strength, cutoff, sampling))), "set_shadow")
-        self._shadow = pending
-
-    def clear_shadow(self):
-        self._shadow = None
-        self._check(self._L.vr_hip_multi_set_shadow(self._m, None), "clear_shadow")
-
-    def _resolve_shadow(self, ray_step):
-        if self._shadow is not None:
-            self._check(self._L.vr_hip_multi_set_shadow(self._m, C.byref(make_shadow(step=float(ray_step), **self._shadow))), "set_shadow")
-            self._shadow = None
+        self._hold_shadow(light_pos, dims, step, strength, cutoff, sampling)
 
     def set_lighting(self, ambient=0.25, diffuse=0.65, specular=0.4, shininess_log2=4):
         """vr_hip_multi_set_lighting: HipRenderer.set_lighting on every device's context"""
@@ -615,20 +591,16 @@ class MultiRenderer:
 
     def render_volume(self, params):
         out = np.empty((params.view.height, params.view.width, 4), dtype=np.uint8)
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_multi_render(self._m, C.byref(params), out.ctypes.data), "render_volume")
+        self._frame("render_volume", "vr_hip_multi_render", params, out.ctypes.data, composite=True)
         return out
 
     def render_volume_device(self, params, dev_ptr):
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_multi_render_device(self._m, C.byref(params), C.c_void_p(dev_ptr)), "render_volume_device")
+        self._frame("render_volume_device", "vr_hip_multi_render_device", params, C.c_void_p(dev_ptr), composite=True)
 
     def render_volume_device_async(self, params, dev_ptr, consumer_stream=None):
         """Queues a frame (up to THREE in flight: kFrames in vr_multi.cpp; frames in flight must not share `dev_ptr`); `consumer_stream`
         (raw hipStream_t on devices[0]) waits for the assembled frame."""
-        self._resolve_shadow(params.ray_step)
-        self._check(self._L.vr_hip_multi_render_device_async(self._m, C.byref(params), C.c_void_p(dev_ptr),
-                                                             C.c_void_p(consumer_stream) if consumer_stream else None), "render_volume_device_async")
+        self._frame("render_volume_device_async", "vr_hip_multi_render_device_async", params, C.c_void_p(dev_ptr), _ptr(consumer_stream), composite=True)
 
     def sync(self):
         self._check(self._L.vr_hip_multi_sync(self._m), "sync")
@@ -638,7 +610,6 @@ class MultiRenderer:
 
     def context_timing(self, rank):
         """vr_timing of one device's context (kernel_ms_sum / launches since its last reset)."""
-        from .binding import VrTiming
         t = VrTiming()
         rc = self._L.vr_hip_timing(C.c_void_p(self._L.vr_hip_multi_context(self._m, rank)), C.byref(t))
         if rc:
