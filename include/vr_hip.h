@@ -653,6 +653,63 @@ int vr_hip_render_labelled(vr_ctx *ctx, const vr_params *params, uint8_t *host_r
 int vr_hip_render_labelled_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
 int vr_hip_labelled_frames(vr_ctx *ctx, uint64_t *frames_out);         /* testing aid: labelled frames launched */
 
+/* ---- 2D transfer-function frames: classify by value and gradient magnitude.  No reference counterpart. ----
+ * The gradient magnitude of the field is the second classification axis (Levoy 1988; Kniss et al. 2002): material interiors sit at a low
+ * gradient magnitude, the boundary between two materials is an arch that reaches a high one at intermediate values.  A table over (value,
+ * gradient magnitude) shows boundaries without the solid behind them, and separates two boundaries that cross the same values.
+ *  1. State.  `table` is rows * 128 float4, premultiplied: row r is a transfer function of the value in the layout vr_hip_set_transfer_fn
+ *     takes.  rows is 2..VR_TF2D_ROWS_MAX.  The table is context state and is copied; NULL drops it.  It survives a volume change, is
+ *     independent of the 1-D transfer function, and every other entry point ignores it.  esl_bits are 1024 words, the leaping bits of THIS
+ *     table in the format and with the meaning the 1-D function's bits have: the caller builds them from the envelope of step 7.  The call
+ *     waits for the context's frames first, as vr_hip_set_transfer_fn does.  Every existing struct keeps its size; the frames are counted
+ *     by vr_hip_tf2d_frames (testing aid).
+ *  2. Frame.  The composite frame vr_hip_render_device defines for a TRILINEAR or _Q8 frame under the context's clip (the identity clip when
+ *     none is set, always run), gradient lighting and shadow — leaping by params.esl on the table's own bits, the cue, early termination, the
+ *     band and crop partition — with one replacement: the looked-up colour c of a sample.  (xb, yb, zb) = fma(k, A, B) are the sample's
+ *     texel coordinates.
+ *  3. Value axis.  raw, tb, i = (uint32_t) (int) tb, i1 = min(i + 1, 127) and w = filter_weight(fract(tb)) are formed as the composite forms
+ *     them; w is rounded in _Q8.
+ *  4. Gradient.  Exactly step 1 of the lighting contract: the central differences one texel apart of the interpolated raw value, clamp
+ *     addressing, times half_x / y / z; gg = fma(gz, gz, fma(gy, gy, gx * gx)); g = gg > 0 ? gg * rsqrt_nr(gg) : 0.  No sqrtf: CPU and GPU
+ *     share every bit.
+ *  5. Row.  tg = fmed3(g * g_scale, 0, rows - 1); j = min((uint32_t) tg, rows - 2); wg = tg - (float) j, full fp32 in both sampling modes
+ *     (the shadow factor's precedent).
+ *  6. Colour, per channel: c_j = fma(w, T[j][i1] - T[j][i], T[j][i]); c_j1 the same in row j + 1; c = fma(wg, c_j1 - c_j, c_j).  Every
+ *     subtraction is rounded on its own.  Everything behind the lookup sees this c: the `c.w > 0.05f` test, the reference's cue when no
+ *     lighting is set, lighting steps 2-5 with the gradient of step 4 and not a second one, the shadow's factor, the accumulation and
+ *     `acc.w > ray_threshold`.
+ *  7. Envelope and exact shortcuts.  E[i] is the per-channel maximum over the rows.  tf_zero_below and the corner test of a tf2d frame are
+ *     derived from E exactly as vr_hip_set_transfer_fn derives them from the 1-D function: both transparency shortcuts of the composite
+ *     stay exact.  Entry i is g-independent when every row holds the bit patterns of row 0 at i and at i1; then c is row 0's lookup bit for
+ *     bit (fma(wg, 0, x) = x), and the gradient of a sample need not be fetched where nothing reads it: no counting lane's entry is
+ *     g-dependent and the wave has no lit dense lane.
+ *  8. Consequences.  (a) Every row equal to the context's transfer function, with the same ESL bits: the bytes of vr_hip_render under the
+ *     same state, for any g_scale.  (b) g_scale = 0: the bytes of vr_hip_render with row 0 as the transfer function.  (c) On a plateau
+ *     (gg = 0) only row 0 is seen.  (d) An all-zero table gives a zero frame.
+ *  9. Shadow.  The light grid is the context's, built from the 1-D transfer function (the label precedent): a boundary the table hides still
+ *     casts the shadow the 1-D function gives it.  A grid built from the 2-D table is a follow-up.
+ * 10. What it reads.  What a labelled frame reads — the linear array, quad bricks or oct bricks: vr_launch_info::layout is 0, 1 or 5, tiles
+ *     start in grid order and `ordered` is 0; vr_hip_set_layout, vr_hip_set_wide_addressing and vr_hip_set_brick_plane apply.  Frames are
+ *     counted by vr_hip_timing and described by vr_hip_last_launch.  Single device only.
+ * 11. Errors.  VR_ERR_INVALID for VR_SAMPLE_NEAREST, while pre-integration is on (a slab has no single row), for rows outside 2..8, for a
+ *     g_scale or a table member that is not finite or is negative, and for NULL esl_bits with a table.  VR_ERR_NOT_READY for a frame without
+ *     a table.  Everything else as for vr_hip_render*.
+ * 12. Histogram.  vr_hip_gradient_histogram places the rows: for every voxel of the resident volume, bin = the 1-D histogram's bin (the
+ *     byte, or the high byte of a u16); gx = ((float) v(x+1) - (float) v(x-1)) * half_x with indices clamped to the axis, gy and gz likewise
+ *     (step 4 at integer texel coordinates, where every filter weight is 0); gg and g as in step 4; tg = fmed3(g * g_scale, 0, g_bins - 1);
+ *     row = (uint32_t) (tg + 0.5f); hist[row * 256 + bin] += 1.  Preconditions and errors are vr_hip_volume_histogram's (the linear copy is
+ *     needed); g_bins outside 1..VR_GRADIENT_BINS_MAX and a g_scale that is not finite or is negative return VR_ERR_INVALID.  Summed over
+ *     the rows it equals vr_hip_volume_histogram's output.
+ * Out of scope: the device list (vr_hip_multi_*), a backdrop under a tf2d frame, labels together with a 2-D table, pre-integrated 2-D
+ * classification, a shadow built from the 2-D table, MIP, isosurface, section and depth frames. */
+#define VR_TF2D_ROWS_MAX 8
+int vr_hip_set_tf2d(vr_ctx *ctx, const float *table, uint32_t rows, float g_scale, const uint32_t *esl_bits);   /* table NULL = drop */
+int vr_hip_render_tf2d(vr_ctx *ctx, const vr_params *params, uint8_t *host_rgba);
+int vr_hip_render_tf2d_device(vr_ctx *ctx, const vr_params *params, void *dev_rgba, void *stream);
+int vr_hip_tf2d_frames(vr_ctx *ctx, uint64_t *frames_out);             /* testing aid: tf2d frames launched */
+#define VR_GRADIENT_BINS_MAX 32
+int vr_hip_gradient_histogram(vr_ctx *ctx, uint32_t g_bins, float g_scale, uint64_t *hist_out /* g_bins * 256 */, float *kernel_ms_out);
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

@@ -1,0 +1,278 @@
+"""CPU tier of the 2D transfer-function frames (include/vr_hip.h vr_hip_render_tf2d, vr_hip_gradient_histogram): tf2d_render of
+tests/tf2d_ref.c — the bytes the GPU tier expects — is tied to the composite restatements through the four consequences of the contract, the
+frames of the GPU tier's main test are shown to reach every row pair and both kinds of entry and to tell four wrong readings of the contract
+apart, gradient_histogram_ref is held to an independent numpy statement, and the tf2d kernels are held to 8 waves per SIMD."""
+import ctypes as C
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+import feature_random as fr
+from clip_helpers import ClipRef
+from label_helpers import tier_frames
+from light_helpers import LIT_VOLUMES, LightRef, lit_volumes
+from shadow_helpers import ShadowRef
+from tf2d_helpers import (PERTURBATIONS, ROWS, Tf2dRef, choose_g_scale, dependent_entries, envelope, equal_rows, esl_of, g_dependent, random_table,
+                          structured_table)
+
+NEW_SYMBOLS = ("vr_hip_set_tf2d", "vr_hip_render_tf2d", "vr_hip_render_tf2d_device", "vr_hip_tf2d_frames", "vr_hip_gradient_histogram")
+METHODS = ("set_tf2d", "clear_tf2d", "render_tf2d", "render_tf2d_device", "tf2d_frames", "gradient_histogram")
+READINGS = {1: "nearest row", 2: "row from gg", 3: "gradient without half", 4: "row weight in 8 bits"}
+
+
+@pytest.fixture(scope="module")
+def volumes(golden):
+    return lit_volumes(golden)
+
+
+def composite(case, tf=None, esl=None):
+    """the composite restatement of the case's frame with a 1-D function: light_render, shadow_render or clip_render — three entry points,
+    the independent composite text among them.  The shadow's grid stays the case's: it is built from the 1-D function of the context."""
+    tf = case.tf if tf is None else tf
+    esl = case.esl if esl is None else esl
+    if case.lighting is not None:
+        return LightRef.instance().render(case.p, case.vox, tf, esl, case.lighting, case.q, case.strength, clip=case.clip)
+    if case.q is not None:
+        return ShadowRef.instance().render(case.p, case.vox, tf, esl, case.q, case.strength, case.clip)
+    return ClipRef.instance().composite(case.p, case.vox, tf, esl, case.clip)
+
+
+def test_the_structured_table(vr, golden, oracle, volumes):
+    """Five rows; row 0 the function, row 1 half of it and row 2 zero on the odd bands; every member of rows 3-4 a multiple of 1/256 there; at least
+    a third of the 128 entries g-independent and at least a third g-dependent, on every volume's function; the envelope is the maximum and
+    the package's envelope() is the same array; random tables have 2 to 8 rows and no negative member"""
+    tf2d = importlib.import_module("volume-rendering_amd.tf2d")
+    for name in LIT_VOLUMES:
+        tf = np.asarray(next(iter(tier_frames(vr, golden, oracle, volumes, name, 1))).tf, np.float32).reshape(128, 4)
+        t = structured_table(tf)
+        assert t.shape == (ROWS, 128, 4) and np.array_equal(t[0], tf) and (t >= 0).all() and np.isfinite(t).all()
+        odd = (np.arange(128) // 16) % 2 == 1
+        assert np.array_equal(t[1][odd], tf[odd] * np.float32(0.5)) and not t[2][odd].any() and np.array_equal(t[1:, ~odd], np.repeat(tf[None, ~odd], 4, axis=0))
+        assert np.array_equal(t[3:, odd] * 256, np.round(t[3:, odd] * 256)) and (t[3:, odd, 3] > 0).all()
+        dep = dependent_entries(t)
+        assert 3 * int(dep.sum()) >= 128 and 3 * int((~dep).sum()) >= 128, (name, int(dep.sum()))
+        assert np.array_equal(envelope(t), t.max(axis=0)) and np.array_equal(tf2d.envelope(t), envelope(t))
+        assert not g_dependent(equal_rows(tf, 8)).any()
+    rng = np.random.default_rng(5)
+    seen = set()
+    for _ in range(40):
+        t = random_table(rng, tf)
+        seen.add(t.shape[0])
+        assert (t >= 0).all() and np.array_equal(t[0], tf)
+    assert seen == set(range(2, 9))
+
+
+@pytest.mark.parametrize("name", LIT_VOLUMES)
+def test_consequences(vr, golden, oracle, volumes, name):
+    """On every frame of the list.  (a) every row equal to the frame's transfer function, with its ESL bits: the bytes of the composite
+    restatement (clip_render, light_render or shadow_render), for two values of g_scale.  (b) g_scale = 0 with the structured table and the
+    bits of its envelope: the bytes of the composite restatement with row 0 as the function and those bits.  (d) an all-zero table: zero."""
+    ref = Tf2dRef.instance()
+    frames = nonzero = 0
+    for sampling in (1, 2):
+        for k, case in enumerate(tier_frames(vr, golden, oracle, volumes, name, sampling)):
+            plain = composite(case)
+            for g_scale in (0.37 * (k + 1), 1e30):
+                got = ref.render(case.p, case.vox, equal_rows(case.tf, 2 + k % 7), g_scale, case.esl, case.lighting, case.q, case.strength, case.clip)
+                assert np.array_equal(got.frame, plain), (case.what, "a", g_scale, int((got.frame != plain).any(axis=-1).sum()))
+            table = structured_table(case.tf)
+            bits = esl_of(oracle, case.vox, table)
+            want = composite(case, table[0], bits)
+            flat = ref.render(case.p, case.vox, table, 0.0, bits, case.lighting, case.q, case.strength, case.clip)
+            assert np.array_equal(flat.frame, want), (case.what, "b", int((flat.frame != want).any(axis=-1).sum()))
+            assert int(flat.by_row[1:].sum()) == 0
+            zero = ref.render(case.p, case.vox, np.zeros((3, 128, 4), np.float32), 1.0, np.zeros(1024, np.uint32), case.lighting, case.q, case.strength, case.clip)
+            assert not zero.frame.any() and zero.count.sum() >= got.count.sum() > 0, (case.what, "d")
+            frames, nonzero = frames + 1, nonzero + int(plain[..., 3].astype(bool).sum())
+    assert frames == 36 and nonzero > 36 * 300, (frames, nonzero)
+
+
+def test_a_plateau_sees_row_zero_alone(vr, golden, oracle, volumes):
+    """(c): a constant volume has gg = 0 at every sample — whatever g_scale is, the frames of the plateau's list over it are the composite's
+    with row 0 as the function, and only row pair 0 receives samples"""
+    ref = Tf2dRef.instance()
+    const = np.full((24, 24, 24), 150, np.uint8)
+    none = np.zeros(1024, np.uint32)
+    frames = 0
+    for case in tier_frames(vr, golden, oracle, volumes, "plateau", 1):
+        if case.q is not None:
+            continue                                    # (the case's light grid belongs to another volume)
+        table = structured_table(case.tf)
+        tf = table[0]
+        if case.lighting is not None:
+            want = LightRef.instance().render(case.p, const, tf, none, case.lighting, None, 1.0, clip=case.clip)
+        else:
+            want = ClipRef.instance().composite(case.p, const, tf, none, case.clip)
+        got = ref.render(case.p, const, table, 1e30, none, case.lighting, None, 1.0, case.clip)
+        assert np.array_equal(got.frame, want) and int(got.by_row[1:].sum()) == 0, case.what
+        frames += 1
+    assert frames == 10                                  # (the frames of the list without a shadow)
+
+
+@pytest.mark.parametrize("name", LIT_VOLUMES)
+def test_the_main_tests_frames_reach_every_row_pair_and_tell_wrong_readings_apart(vr, golden, oracle, volumes, name):
+    """The list tier_frames gives tests/test_gpu_tf2d.py, on the restatement alone, with the structured table, the volume's g_scale and the
+    bits of the envelope.  Each of the four row pairs and both kinds of entry receive samples with alpha (the shares are printed); the frames
+    differ from the composite's; and each wrong reading — the nearest row instead of the interpolated one, the row from gg instead of g, the
+    gradient without half_*, the row weight rounded as a _Q8 weight — changes bytes over the list."""
+    ref = Tf2dRef.instance()
+    g_scale = choose_g_scale(name, volumes[name])
+    rows, kinds = np.zeros(8, np.int64), np.zeros(2, np.int64)
+    changed = dict.fromkeys(PERTURBATIONS, 0)
+    differs = frames = 0
+    for sampling in (1, 2):
+        for case in tier_frames(vr, golden, oracle, volumes, name, sampling):
+            table = structured_table(case.tf)
+            bits = esl_of(oracle, case.vox, table)
+            got = ref.render(case.p, case.vox, table, g_scale, bits, case.lighting, case.q, case.strength, case.clip)
+            rows += got.by_row.astype(np.int64)
+            kinds += got.by_kind.astype(np.int64)
+            differs += int((got.frame != composite(case)).any(axis=-1).sum())
+            frames += 1
+            for perturb in PERTURBATIONS:
+                wrong = ref.render(case.p, case.vox, table, g_scale, bits, case.lighting, case.q, case.strength, case.clip, perturb=perturb)
+                changed[perturb] += int((wrong.frame != got.frame).any(axis=-1).sum())
+    print(f"{name}: g_scale {g_scale}, {frames} frames; samples with alpha by row pair: " + ", ".join(f"{j} {n / rows.sum():.3f}" for j, n in enumerate(rows[:ROWS - 1])) +
+          f"; g-independent {kinds[0] / kinds.sum():.3f}, g-dependent {kinds[1] / kinds.sum():.3f}; pixels that differ from the composite's {differs}; "
+          "pixels changed by the wrong readings " + ", ".join(f"{READINGS[k]} {n}" for k, n in changed.items()))
+    assert frames == 36 and (rows[:ROWS - 1] > 0).all() and not rows[ROWS - 1:].any() and (kinds > 0).all(), (rows, kinds)
+    assert differs > 36 * 100 and all(n > 0 for n in changed.values()), (differs, changed)
+
+
+# ---- the histogram ----
+
+def _fma(a, b, c):
+    """fmaf on float32 arrays through float64: the product of two float32 is exact there, the sum is rounded once to 53 bits and once to 24"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _rsqrt_nr(x):
+    y = (np.uint32(0x5f3759df) - (x.view(np.uint32) >> np.uint32(1))).view(np.float32)
+    h = np.float32(0.5) * x
+    for _ in range(3):
+        y = y * _fma(-(h * y), y, np.full_like(y, 1.5))
+    return y
+
+
+def numpy_gradient_histogram(vox, g_bins, g_scale):
+    """step 12 of the contract in whole-array numpy float32 operations, independent of tests/tf2d_ref.c"""
+    z, y, x = vox.shape
+    v = vox.astype(np.float32)
+    half = [np.float32(0.5) * np.float32(n) for n in (z, y, x)]
+    g = []
+    for axis, n in enumerate((z, y, x)):
+        up = np.take(v, np.minimum(np.arange(n) + 1, n - 1), axis=axis)
+        down = np.take(v, np.maximum(np.arange(n) - 1, 0), axis=axis)
+        g.append((up - down) * half[axis])
+    gz, gy, gx = g
+    gg = _fma(gz, gz, _fma(gy, gy, gx * gx))
+    with np.errstate(all="ignore"):
+        length = np.where(gg > 0, gg * _rsqrt_nr(np.ascontiguousarray(gg)), np.float32(0)).astype(np.float32)
+    tg = np.clip(length * np.float32(g_scale), np.float32(0), np.float32(g_bins - 1)).astype(np.float32)
+    row = (tg + np.float32(0.5)).astype(np.uint32)
+    bins = (vox if vox.dtype == np.uint8 else vox >> 8).astype(np.uint32)
+    return np.bincount((row * 256 + bins).ravel(), minlength=g_bins * 256).astype(np.uint64).reshape(g_bins, 256)
+
+
+def histogram_volumes(golden, volumes):
+    yield "bucky", volumes["bucky"], choose_g_scale("bucky", volumes["bucky"])
+    yield "blob_40x24x56", volumes["blob_40x24x56"], choose_g_scale("blob_40x24x56", volumes["blob_40x24x56"])
+    for shape in fr.EDGE_SHAPES:
+        for dtype in fr.EDGE_DTYPES:
+            yield (shape, dtype), fr.edge_volume(shape, dtype), 2.0 ** -7 if dtype == "uint8" else 2.0 ** -15
+
+
+def test_the_histogram_restatement_equals_the_numpy_statement(golden, oracle, volumes):
+    """gradient_histogram_ref against whole-array numpy on bucky, the blob and all EDGE_SHAPES x EDGE_DTYPES (extents of 1 and 2: every
+    difference of such an axis is clamped on one side or both), with 1, 5 and 32 rows; summed over the rows both equal Oracle.histogram"""
+    ref = Tf2dRef.instance()
+    checked = rows_used = 0
+    for what, vox, g_scale in histogram_volumes(golden, volumes):
+        plain = oracle.histogram(vox)
+        for g_bins in (1, 5, 32):
+            got = ref.histogram(vox, g_bins, g_scale * g_bins / 5.0)
+            want = numpy_gradient_histogram(vox, g_bins, np.float32(g_scale * g_bins / 5.0))
+            assert np.array_equal(got, want), (what, g_bins, int((got != want).sum()))
+            assert np.array_equal(got.sum(axis=0), plain) and int(got.sum()) == vox.size, (what, g_bins)
+            checked += 1
+            rows_used = max(rows_used, int((got.sum(axis=1) > 0).sum()))
+    assert checked == 3 * (2 + len(fr.EDGE_SHAPES) * len(fr.EDGE_DTYPES)) and rows_used >= 16
+
+
+# ---- the build ----
+
+def _kernels(text, pattern):
+    out = {}
+    for m in re.finditer(r"Function Name: (\S*?" + pattern + r"\S*).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+                         r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+).*?LDS Size \[bytes/block\]: (\d+)", text, flags=re.S):
+        out[m.group(1)] = tuple(int(g) for g in m.groups()[1:])
+    return out
+
+
+ROW_KEY = r"ILi(\d)ELi(\d)ELi(\d)ELi(\d)E"
+
+
+def test_tf2d_kernels_keep_eight_waves(vr):
+    """The ninth log, resource_usage_tf2d.log: its names appear once each and in no other log — tf2d_kernel over the 24 rows of the depth
+    kernel and gradient_histogram_kernel for both voxel sizes.  No scratch, no SGPR or VGPR spilled anywhere; on every tf2d row <= 80 SGPRs,
+    <= 64 VGPRs and 8 waves per SIMD, and LDS that leaves two workgroups of 1024 or four of 512 on a CU's 160 KiB; the histogram's counters
+    are 32 KiB.  The eight older logs keep their 269 / 36 / 24 / 48 / 96 / 24 / 25 / 24 names."""
+    import subprocess
+    from test_abi import ROOT
+    csrc = os.path.join(ROOT, "volume-rendering_amd", "csrc")
+    logs = [os.path.join(csrc, n) for n in ("resource_usage.log", "resource_usage_shadow.log", "resource_usage_light.log", "resource_usage_slab.log",
+                                            "resource_usage_backdrop.log", "resource_usage_section.log", "resource_usage_depth.log", "resource_usage_label.log",
+                                            "resource_usage_tf2d.log")]
+    if not all(os.path.exists(p) for p in logs):
+        subprocess.check_call(["make", "-B", "-C", csrc])
+    texts = [open(p).read() for p in logs]
+    names = [re.findall(r"Function Name: (\S+)", t) for t in texts]
+    assert [len(n) for n in names[:8]] == [269, 36, 24, 48, 96, 24, 25, 24], [len(n) for n in names]
+    assert len(names[8]) == 26 and len(set(sum(names, []))) == 269 + 36 + 24 + 48 + 96 + 24 + 25 + 24 + 26
+    mine = lambda n: "tf2d_kernel" in n or "gradient_histogram_kernel" in n      # noqa: E731
+    assert all(mine(n) for n in names[8]) and not [n for n in sum(names[:8], []) if mine(n)]
+    key = lambda name: tuple(int(g) for g in re.search(ROW_KEY, name).groups())      # noqa: E731
+    rows = {key(n): v for n, v in _kernels(texts[8], r"\d+tf2d_kernel" + ROW_KEY.replace("(", "(?:")).items()}
+    depth_rows = {key(n) for n in names[6] if re.search(r"\d+depth_kernel" + ROW_KEY, n)}
+    assert len(rows) == 24 and set(rows) == depth_rows
+    for row, (sgprs, vgprs, scratch, occupancy, sspill, vspill, lds) in rows.items():
+        assert scratch == 0 and sspill == 0 and vspill == 0, (row, scratch, sspill, vspill)
+        assert sgprs <= 80 and vgprs <= 64 and occupancy == 8, (row, sgprs, vgprs, occupancy)
+        assert lds * (2 if row[2] == 1 and row[3] != 0 else 4) <= 160 * 1024, (row, lds)
+    hist = _kernels(texts[8], r"gradient_histogram_kernel")
+    assert len(hist) == 2
+    for name, (sgprs, vgprs, scratch, occupancy, sspill, vspill, lds) in hist.items():
+        assert scratch == 0 and sspill == 0 and vspill == 0 and lds == 32 * 256 * 4, (name, scratch, sspill, vspill, lds)
+
+
+def test_binding_and_header(vr):
+    """The five entry points are declared in include/vr_hip.h, exported and resolved by the binding; without a context they return
+    VR_ERR_INVALID; vr_params keeps its 132 bytes, VrLaunchInfo its 13 members and 52 bytes, VrVolumeInfo its 128 bytes; Tf2dRenderer is a
+    HipRenderer with the six methods, HipRenderer, MultiRenderer and the package's __all__ stay without them."""
+    from test_abi import ROOT
+    tf2d = importlib.import_module("volume-rendering_amd.tf2d")
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vr_hip.h")).read(), flags=re.S)
+    L = vr.lib()
+    raw = C.CDLL(vr.library_path())
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint\s+" + name + r"\(", text), name
+        assert hasattr(L, name) and hasattr(raw, name), name
+    assert re.search(r"#define VR_TF2D_ROWS_MAX 8\b", text) and re.search(r"#define VR_GRADIENT_BINS_MAX 32\b", text)
+    assert vr.binding.TF2D_ROWS_MAX == 8 and vr.binding.GRADIENT_BINS_MAX == 32
+    assert C.sizeof(vr.VrParams) == 132 and len(vr.VrLaunchInfo._fields_) == 13 and C.sizeof(vr.VrLaunchInfo) == 52 and C.sizeof(vr.binding.VrVolumeInfo) == 128
+    p, count, ms = vr.VrParams(), C.c_uint64(0), C.c_float(0)
+    buf = (C.c_uint8 * 64)()
+    table = np.zeros((2, 128, 4), np.float32)
+    bits = np.zeros(1024, np.uint32)
+    hist = np.zeros(256, np.uint64)
+    assert L.vr_hip_set_tf2d(None, table.ctypes.data, 2, 1.0, bits.ctypes.data) == 1 and L.vr_hip_set_tf2d(None, None, 0, 0.0, None) == 1
+    assert L.vr_hip_render_tf2d(None, C.byref(p), buf) == 1 and L.vr_hip_render_tf2d_device(None, C.byref(p), buf, None) == 1
+    assert L.vr_hip_tf2d_frames(None, C.byref(count)) == 1 and L.vr_hip_gradient_histogram(None, 1, 1.0, hist.ctypes.data, C.byref(ms)) == 1
+    assert issubclass(tf2d.Tf2dRenderer, vr.HipRenderer)
+    for method in METHODS:
+        assert callable(getattr(tf2d.Tf2dRenderer, method)), method
+        assert not hasattr(vr.HipRenderer, method) and not hasattr(vr.MultiRenderer, method), method
+    assert "Tf2dRenderer" not in vr.__all__ and "tf2d" not in vr.__all__ and callable(tf2d.envelope)

@@ -153,6 +153,8 @@ def make_depth(opacity, mode="first"):
 
 
 LABEL_COUNT = 256
+TF2D_ROWS_MAX = 8              # VR_TF2D_ROWS_MAX
+GRADIENT_BINS_MAX = 32         # VR_GRADIENT_BINS_MAX
 
 
 class VrLabelEntry(C.Structure):
@@ -272,6 +274,11 @@ def lib():
         "vr_hip_render_labelled": (C.c_int, [vp, P(VrParams), vp]),
         "vr_hip_render_labelled_device": (C.c_int, [vp, P(VrParams), vp, vp]),
         "vr_hip_labelled_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_set_tf2d": (C.c_int, [vp, vp, u32, C.c_float, vp]),
+        "vr_hip_render_tf2d": (C.c_int, [vp, P(VrParams), vp]),
+        "vr_hip_render_tf2d_device": (C.c_int, [vp, P(VrParams), vp, vp]),
+        "vr_hip_tf2d_frames": (C.c_int, [vp, P(u64)]),
+        "vr_hip_gradient_histogram": (C.c_int, [vp, u32, C.c_float, vp, f32p]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

@@ -453,6 +453,25 @@ struct LabelArgs {
 hipError_t launch_labelled(const RayKernelArgs &a, const void *labels_linear, const void *labels_xy_bricks, const void *linear, const void *bricked,
                            uint32_t bytes_per_voxel, const float *tf_premult, const uint32_t *esl_bits, const float *table, void *out_rgba, hipStream_t stream);
 
+// ---- 2D transfer-function frames (include/vr_hip.h vr_hip_render_tf2d) ----
+// The second axis of one frame, a kernel argument of its own behind the ones a composite frame takes.
+struct Tf2dArgs {
+	float    g_scale;                  // row coordinate = fmed3(g * g_scale, 0, top)
+	float    top;                      // (float) (rows - 1)
+	uint32_t last;                     // rows - 2: the highest lower row
+	uint32_t rows;                     // 2..VR_TF2D_ROWS_MAX: rows * VR_TF_SIZE entries of the table are staged
+	uint32_t g_dependent[4];           // bit i: some row differs from row 0 at entry i or at min(i + 1, 127)
+};
+// One tf2d frame.  `a`, `linear` and `bricked` as for launch_labelled (the same rows), the clip, lighting and shadow words likewise; a.p.esl,
+// a.esl_div_* as launch_depth takes them; a.skip_mask / skip_cmp / tf_zero_below are the ENVELOPE's (the per-channel maximum over the rows).
+// table: rows * VR_TF_SIZE float4 on the device, row-major; esl_bits: the table's own 1024 words.
+hipError_t launch_tf2d(const RayKernelArgs &a, const Tf2dArgs &d, const void *linear, const void *bricked, uint32_t bytes_per_voxel,
+                       const float *table, const uint32_t *esl_bits, void *out_rgba, hipStream_t stream);
+// The histogram over (value bin, gradient-magnitude row) of the linear array: hist_dev[g_bins * 256] is zeroed and filled on `stream`.
+// `bc` (bounds-checked build alone): volume_args with bc_base / bc_bytes / bc_fault armed for the linear array.
+hipError_t launch_gradient_histogram(const void *volume, uint32_t bytes_per_voxel, const uint32_t dims[3], uint32_t g_bins, float g_scale,
+                                     unsigned long long *hist_dev, const RayKernelArgs *bc, hipStream_t stream);
+
 // ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
 // What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
 struct ShadowBuildArgs {

@@ -137,6 +137,14 @@ struct vr_ctx {
 	uint8_t *labels = nullptr, *label_bricks = nullptr; bool label_bricks_failed = false;
 	float *label_table = nullptr;
 	uint64_t labelled_frames = 0;
+	// 2D transfer-function frames (vr_hip_set_tf2d, vr_hip_render_tf2d*): the table (VR_TF2D_ROWS_MAX * VR_TF_SIZE float4, the rows given and
+	// zeros behind them) and its own ESL words on the device, both NULL until a table is set; what the host derives from the table — the
+	// envelope's leading all-zero entries (tf_zero_below of such a frame) and the 128 g-dependence flags —; the frames launched; and the
+	// counters of vr_hip_gradient_histogram (VR_GRADIENT_BINS_MAX * 256), allocated on first use
+	float *tf2d_table = nullptr; uint32_t *tf2d_esl = nullptr;
+	uint32_t tf2d_rows = 0; float tf2d_g_scale = 0.0f, tf2d_zero_below = -1.0f; uint32_t tf2d_g_dependent[4] = { 0, 0, 0, 0 };
+	uint64_t tf2d_frames = 0;
+	unsigned long long *gradient_hist = nullptr;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
 #endif
@@ -424,16 +432,18 @@ void volume_args(const vr_ctx *c, const vr_params *p, RayKernelArgs &a) {
 
 // the corner test of the transparent-sample shortcut (RayKernelArgs::skip_mask / skip_cmp) for the resident transfer function: the largest
 // power of two P with fma(P, tf_scale, -0.5) <= tf_zero_below — raw < P implies a transparent sample
-void transparent_corner_test(const vr_ctx *c, RayKernelArgs &a) {
+// (zero_below: the leading all-zero entries of the function the frame classifies with — the resident one's, or a tf2d table's envelope's)
+void transparent_corner_test(const vr_ctx *c, RayKernelArgs &a, float zero_below) {
 	uint32_t below = 0;
 	const uint32_t top = c->bpv == 1 ? 256u : 65536u;
 	for (uint32_t P = 1; P <= top; P <<= 1)
-		if (c->tf_zero_below >= 0.0f && std::fmaf((float) P, a.tf_scale, -0.5f) <= c->tf_zero_below) below = P;
+		if (zero_below >= 0.0f && std::fmaf((float) P, a.tf_scale, -0.5f) <= zero_below) below = P;
 	a.skip_cmp = below == 0 ? 1u : 0u;
 	if (below == 0) a.skip_mask = 0u;
 	else if (c->bpv == 1) a.skip_mask = ((0xffu & ~(below - 1u)) * 0x01010101u);
 	else a.skip_mask = ((0xffffu & ~(below - 1u)) * 0x00010001u);
 }
+void transparent_corner_test(const vr_ctx *c, RayKernelArgs &a) { transparent_corner_test(c, a, c->tf_zero_below); }
 
 // index / block edge of the ESL grid, prepared as shift or multiply-high (RaycasterBase.h:59-63)
 void esl_divisor(RayKernelArgs &a, uint32_t block_dims) {
@@ -1503,6 +1513,36 @@ int launch_labelled_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStre
 	return rc;
 }
 
+// what the two tf2d entry points check beyond render_preamble (include/vr_hip.h, step 11 of the tf2d contract)
+int validate_tf2d(vr_ctx *c, const vr_params *p) {
+	if (const int rc = need_interpolated(c, p, "a tf2d frame")) return rc;
+	if (c->preint_on)
+		return fail(c, VR_ERR_INVALID, "pre-integration is set: a slab between two samples has no single row of the 2-D table "
+		                               "(vr_hip_set_preintegration(ctx, 0) switches it off)");
+	if (c->tf2d_table == nullptr) return fail(c, VR_ERR_NOT_READY, "no 2-D transfer function is set (vr_hip_set_tf2d)");
+	return VR_OK;
+}
+
+// One tf2d frame (include/vr_hip.h vr_hip_render_tf2d): what a labelled frame of the same view and sampling reads and maps — the context's
+// forced plane is left alone —, with the composite's leaping in the kernel argument, the lighting and the shadow as launch_frame puts them
+// there, and tf_zero_below and the corner test of the table's ENVELOPE in this frame's copy of the arguments.  volume_args has filled the
+// clip words.
+int launch_tf2d_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t stream) {
+	if (c->shadow_on) { if (const int rc = build_shadow(c)) return rc; }
+	const FullMarch f = { "tf2d", false, true, -1 };
+	const int rc = launch_full_march_frame(c, p, stream, f, [&](RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		lighting_shadow_args(c, a);
+		a.tf_zero_below = c->tf2d_zero_below;
+		transparent_corner_test(c, a, c->tf2d_zero_below);
+		Tf2dArgs d;
+		d.g_scale = c->tf2d_g_scale; d.top = (float) (c->tf2d_rows - 1u); d.last = c->tf2d_rows - 2u; d.rows = c->tf2d_rows;
+		for (int i = 0; i < 4; i++) d.g_dependent[i] = c->tf2d_g_dependent[i];
+		return launch_tf2d(a, d, c->vol, brick_copy, c->bpv, c->tf2d_table, c->tf2d_esl, dev_rgba, stream);
+	});
+	if (rc == VR_OK) c->tf2d_frames++;
+	return rc;
+}
+
 // the depth buffer of the host entry points that hand a depth back (vr_hip_render_iso, vr_hip_render_section): one float per pixel of the
 // window, sized with the window (render_preamble: the frame fits), allocated on first use behind the context's frames
 int size_host_depth(vr_ctx *c) {
@@ -1631,6 +1671,9 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->pick_stage) (void) hipFree(c->pick_stage);
 	drop_labels(c);
 	if (c->label_table) (void) hipFree(c->label_table);
+	if (c->tf2d_table) (void) hipFree(c->tf2d_table);
+	if (c->tf2d_esl) (void) hipFree(c->tf2d_esl);
+	if (c->gradient_hist) (void) hipFree(c->gradient_hist);
 	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
 	if (c->stream_first) { (void) hipStreamSynchronize(c->stream_first); (void) hipStreamDestroy(c->stream_first); }
@@ -2184,6 +2227,66 @@ int vr_hip_render_labelled(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 
 int vr_hip_labelled_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::labelled_frames, frames_out); }
 
+// ---- 2D transfer-function frames (include/vr_hip.h vr_hip_set_tf2d) ----
+
+int vr_hip_set_tf2d(vr_ctx *c, const float *table, uint32_t rows, float g_scale, const uint32_t *esl_bits) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	VR_TRY(c, hipSetDevice(c->device));
+	if (table == nullptr) {
+		VR_TRY(c, drain(c));                     // frames still reading the table we are about to drop
+		if (c->tf2d_table) { (void) hipFree(c->tf2d_table); c->tf2d_table = nullptr; }
+		if (c->tf2d_esl) { (void) hipFree(c->tf2d_esl); c->tf2d_esl = nullptr; }
+		c->tf2d_rows = 0;
+		return VR_OK;
+	}
+	if (rows < 2u || rows > VR_TF2D_ROWS_MAX) return fail(c, VR_ERR_INVALID, "a 2-D transfer function has 2..8 rows");
+	if (!std::isfinite(g_scale) || g_scale < 0.0f) return fail(c, VR_ERR_INVALID, "g_scale must be finite and not negative");
+	if (esl_bits == nullptr) return fail(c, VR_ERR_INVALID, "esl_bits is NULL");
+	const size_t members = (size_t) rows * VR_TF_SIZE * 4u;
+	for (size_t i = 0; i < members; i++)
+		if (!std::isfinite(table[i]) || table[i] < 0.0f) return fail(c, VR_ERR_INVALID, "2-D transfer function members must be finite and not negative");
+	// the envelope's leading all-zero entries: every row is zero there (no member is negative, so the maximum is 0 only where all are)
+	int zero = -1;
+	auto entry_zero = [&](int i) {
+		for (uint32_t r = 0; r < rows; r++)
+			for (int ch = 0; ch < 4; ch++) if (table[((size_t) r * VR_TF_SIZE + i) * 4u + ch] != 0.0f) return false;
+		return true;
+	};
+	while (zero + 1 < VR_TF_SIZE && entry_zero(zero + 1)) zero++;
+	// entry i is g-dependent unless every row holds row 0's bit patterns at i and at min(i + 1, 127)
+	uint32_t dependent[4] = { 0, 0, 0, 0 };
+	auto same_as_row0 = [&](int i) {
+		for (uint32_t r = 1; r < rows; r++)
+			if (memcmp(table + ((size_t) r * VR_TF_SIZE + i) * 4u, table + (size_t) i * 4u, 4u * sizeof(float)) != 0) return false;
+		return true;
+	};
+	for (int i = 0; i < VR_TF_SIZE; i++) {
+		const int i1 = i + 1 < VR_TF_SIZE ? i + 1 : VR_TF_SIZE - 1;
+		if (!same_as_row0(i) || !same_as_row0(i1)) dependent[i >> 5] |= 1u << (i & 31);
+	}
+	VR_TRY(c, drain(c));                         // frames still reading the table we are about to replace (vr_hip_set_transfer_fn)
+	constexpr size_t kTableBytes = (size_t) VR_TF2D_ROWS_MAX * VR_TF_SIZE * 4u * sizeof(float);
+	if (c->tf2d_table == nullptr) VR_TRY(c, hipMalloc((void **) &c->tf2d_table, kTableBytes));
+	if (c->tf2d_esl == nullptr) VR_TRY(c, hipMalloc((void **) &c->tf2d_esl, VR_ESL_VOLUME_SIZE * sizeof(uint32_t)));
+	VR_TRY(c, hipMemsetAsync(c->tf2d_table, 0, kTableBytes, c->stream));
+	VR_TRY(c, hipMemcpyAsync(c->tf2d_table, table, members * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	VR_TRY(c, hipMemcpyAsync(c->tf2d_esl, esl_bits, VR_ESL_VOLUME_SIZE * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	c->tf2d_rows = rows; c->tf2d_g_scale = g_scale; c->tf2d_zero_below = (float) zero;
+	for (int i = 0; i < 4; i++) c->tf2d_g_dependent[i] = dependent[i];
+	return VR_OK;
+}
+
+int vr_hip_render_tf2d_device(vr_ctx *c, const vr_params *p, void *dev_rgba, void *stream) {
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_tf2d(c, p); }, [&](hipStream_t on) { return launch_tf2d_frame(c, p, dev_rgba, on); });
+}
+
+int vr_hip_render_tf2d(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
+	return render_to_host(c, p, host_rgba, nullptr, nullptr, [&] { return validate_tf2d(c, p); }, [&](void *) { return launch_tf2d_frame(c, p, c->fb, c->stream); });
+}
+
+int vr_hip_tf2d_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::tf2d_frames, frames_out); }
+
 #ifdef VR_MIP_STATS
 // probe build only (scripts/mip_probe.py): { samples, fetches issued } of the MIP frames that skipped since the last call
 int vr_hip_debug_mip_stats(vr_ctx *c, uint64_t *out2) {
@@ -2253,6 +2356,41 @@ int vr_hip_volume_histogram(vr_ctx *c, uint64_t *hist_out, float *kernel_ms_out)
 	VR_TRY(c, hipEventRecord(c->aux_stop, c->stream));
 	VR_TRY(c, hipMemcpyAsync(hist_out, c->hist, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
 	VR_TRY(c, hipStreamSynchronize(c->stream));
+	if (kernel_ms_out) VR_TRY(c, hipEventElapsedTime(kernel_ms_out, c->aux_start, c->aux_stop));
+	return VR_OK;
+}
+
+int vr_hip_gradient_histogram(vr_ctx *c, uint32_t g_bins, float g_scale, uint64_t *hist_out, float *kernel_ms_out) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (hist_out == nullptr) return fail(c, VR_ERR_INVALID, "hist_out is NULL");
+	if (g_bins < 1u || g_bins > VR_GRADIENT_BINS_MAX) return fail(c, VR_ERR_INVALID, "g_bins must be in 1..32");
+	if (!std::isfinite(g_scale) || g_scale < 0.0f) return fail(c, VR_ERR_INVALID, "g_scale must be finite and not negative");
+	if (const int rc = need_linear(c, "set the volume again")) return rc;
+	if (c->vol == nullptr) return fail(c, VR_ERR_NOT_READY, "histogram before set_volume");
+	VR_TRY(c, hipSetDevice(c->device));
+	if (c->gradient_hist == nullptr) VR_TRY(c, hipMalloc((void **) &c->gradient_hist, (size_t) VR_GRADIENT_BINS_MAX * 256u * sizeof(unsigned long long)));
+	const RayKernelArgs *bc = nullptr;
+#ifdef VR_BOUNDS_CHECK
+	// the net of the debug build: every load of the kernel is held against the linear array (without its tail slack: no voxel lies there)
+	vr_params none;
+	memset(&none, 0, sizeof none);
+	RayKernelArgs a;
+	volume_args(c, &none, a);
+	if (c->bc_fault == nullptr) {
+		VR_TRY(c, hipMalloc((void **) &c->bc_fault, 8 * sizeof(uint32_t)));
+		VR_TRY(c, hipMemset(c->bc_fault, 0, 8 * sizeof(uint32_t)));
+	}
+	a.bc_base = (uint64_t) (uintptr_t) c->vol; a.bc_bytes = c->vol_elems * c->bpv; a.bc_fault = c->bc_fault;
+	bc = &a;
+#endif
+	VR_TRY(c, hipEventRecord(c->aux_start, c->stream));
+	VR_TRY(c, launch_gradient_histogram(c->vol, c->bpv, c->dim, g_bins, g_scale, c->gradient_hist, bc, c->stream));
+	VR_TRY(c, hipEventRecord(c->aux_stop, c->stream));
+	VR_TRY(c, hipMemcpyAsync(hist_out, c->gradient_hist, (size_t) g_bins * 256u * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+#ifdef VR_BOUNDS_CHECK
+	{ const int verdict = bounds_check_verdict(c, c->stream, kLayoutLinear); if (verdict) return verdict; }
+#endif
 	if (kernel_ms_out) VR_TRY(c, hipEventElapsedTime(kernel_ms_out, c->aux_start, c->aux_stop));
 	return VR_OK;
 }
