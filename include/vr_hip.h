@@ -710,6 +710,79 @@ int vr_hip_tf2d_frames(vr_ctx *ctx, uint64_t *frames_out);             /* testin
 #define VR_GRADIENT_BINS_MAX 32
 int vr_hip_gradient_histogram(vr_ctx *ctx, uint32_t g_bins, float g_scale, uint64_t *hist_out /* g_bins * 256 */, float *kernel_ms_out);
 
+/* ---- fused frames: a second, co-registered field with a transfer function of its own.  No reference counterpart. ----
+ * Two fields over the same grid in one frame — PET over CT, a dose or a flow inside anatomy, a temperature inside a density.  Each field
+ * is classified by its own transfer function and the two are weighted against each other.  Compositing along a ray is not separable: the
+ * second field's samples enter the same front-to-back accumulation at the same ray positions and the early termination is shared, so two
+ * frames layered from outside do not give this frame.  A is the resident volume, B the second field.
+ *  1. State.  B is context state beside the resident volume: dx * dy * dz voxels, x fastest, with the dims AND the bytes per voxel of the
+ *     resident volume (other dims or another voxel size: VR_ERR_INVALID; no resident volume: VR_ERR_NOT_READY).  The bytes are copied; the
+ *     host entry is synchronous, the device entry copies on the context's stream.  NULL drops B.  vr_hip_set_volume*, vr_hip_generate_volume
+ *     drop it too: vr_hip_render_fused* then returns VR_ERR_NOT_READY.  B's transfer function is 128 premultiplied float4 in the layout
+ *     vr_hip_set_transfer_fn takes; it is set together with 1024 ESL words, which are THE FUSED FRAME'S OWN leaping bits.  A bit means "block
+ *     empty": the fused frame's bits are the AND of A's bits under A's function and B's bits under B's function; the caller builds them
+ *     (vr_hip_set_tf2d's precedent: it takes the envelope's bits).  The call waits for the context's frames first, as
+ *     vr_hip_set_transfer_fn does.  B's function and the bits survive a volume change until they are replaced.  Every other entry point
+ *     ignores all of this; every existing struct keeps its size; the frames are counted by vr_hip_fused_frames (testing aid).  vr_fusion is
+ *     given per call and is no state.
+ *  2. Frame.  The composite frame vr_hip_render_device defines for a TRILINEAR or _Q8 frame under the context's clip (the identity clip when
+ *     none is set, always run), gradient lighting and shadow.  The ray, clip_segment, leaping by params.esl on the fused bits, the k
+ *     sequence, the band and crop partition and the pixel store are the labelled frame's.  (xb, yb, zb) = fma(k, A, B) are the sample's
+ *     texel coordinates; steps 3-7 are one sample.
+ *  3. Field A, unchanged.  cA is what the composite makes of A's sample: the filtered lookup, the `cA.w > 0.05f` test on the looked-up alpha,
+ *     then the reference's cue or lighting steps 1-5, then the shadow's factor.  Nothing of A's arithmetic is new.
+ *  4. Field B.  rawB is the interpolated value of B at the same coordinates with the same filter weights (rounded in _Q8); tbB is formed from
+ *     rawB exactly as tb is formed from raw; cB is the filtered lookup in B's function.  B is emissive: no cue, no lighting, no shadow factor.
+ *  5. Weights.  cA' = cA * weight_a and cB' = cB * weight_b, plain products on all four channels, formed behind step 3's shading.
+ *  6. VR_FUSE_SUM.  Per channel c = fmaf(cB, weight_b, cA'); one accumulation acc = fmaf(c, 1 - acc.w, acc); then `acc.w > ray_threshold`.
+ *  7. VR_FUSE_OVER.  A in front of B within the sample: acc = fmaf(cA', 1 - acc.w, acc); then, with the new acc.w,
+ *     acc = fmaf(cB', 1 - acc.w, acc).  The termination test runs once, behind both.
+ *  8. Exact acceleration.  A field's contribution is exactly 0 where its lookup is.  Its corner test and its tf_zero_below are derived from
+ *     ITS OWN function exactly as vr_hip_set_transfer_fn derives them.  A wave may skip a field's unpacking and lookup when that field's test
+ *     says so for every counting lane, and the whole sample only when both tests say so.  The cue, lighting and shadow fetches are needed
+ *     for lanes dense in A alone.
+ *  9. Consequences, each with equal leaping bits on both sides (or params.esl = 0).  (a) weight_b = 0 with any B, or B's function all zero,
+ *     weight_a = 1 and A's own bits as the frame's bits, both modes: the bytes of vr_hip_render under the same state (x * 1 == x,
+ *     fmaf(finite, 0, x) == x).  (b) weight_a = 0, weight_b = 1, no lighting, no shadow: the bytes of vr_hip_render with light_kd = 0 on a
+ *     context whose resident volume is B, under B's function and the same bits.  (c) the special case of (b) one context shows: B a copy of
+ *     A and B's function A's.  (d) Both weights 0, or both functions zero: all zero bytes.  (a)-(c) are NOT promised under the fused (AND)
+ *     bits against a frame under one field's own bits: the single-field frame leaps blocks that are empty in its field alone, and a leap
+ *     moves where the k sequence of the ray starts (k restarts at the leapt kx: other roundings behind it).  What holds with the AND bits: a
+ *     field whose function is all zero has every bit set, so the AND is the other field's bits — (a) with B's function zero and (d) hold
+ *     under the fused bits as well.
+ *     In VR_FUSE_SUM, exchanging the two fields with their weights does NOT give the same accumulated values even without cue, lighting
+ *     and shadow: fmaf(cB, wb, cA * wa) rounds cA * wa on its own and cB * wb not at all.  The difference is a rounding in the last bit of
+ *     a float, so a byte of the frame differs only now and then.  The product and the fma are the contract; two fmas are not.
+ * 10. Shadow.  The light grid is the context's, built from A under A's function (the label precedent).  B casts no shadow.
+ * 11. Pre-integration.  VR_ERR_INVALID while vr_hip_set_preintegration(1) holds (the label precedent).
+ * 12. What it reads.  A as a labelled frame reads it — the linear array, quad bricks or oct bricks: vr_launch_info::layout is 0, 1 or 5.  B is
+ *     read in the same layout by the same kernel row: its base address is a kernel argument and A's staged address tables address it.  B's
+ *     copy for the layout and chunk plane the frame chose is built from B's linear array on first use, on the context's stream and
+ *     synchronous like any first use, while half of the HBM stays free; it is kept per kind and dropped with B.  Where the copy cannot be had
+ *     the frame runs from both linear arrays (layout 0) instead of failing.  vr_hip_set_layout, vr_hip_set_wide_addressing and
+ *     vr_hip_set_brick_plane apply.  Tiles start in grid order.  Frames are counted by vr_hip_timing and vr_hip_fused_frames and described
+ *     by vr_hip_last_launch.
+ * 13. Errors.  VR_ERR_INVALID for VR_SAMPLE_NEAREST, a NULL vr_fusion, mode > 1, reserved != 0, a weight that is not finite or lies outside
+ *     [0, 1], a member of B's function that is negative or not finite, NULL bits with a function, and the dims or voxel-size mismatch.
+ *     VR_ERR_NOT_READY without B or without B's function.  Everything else as for vr_hip_render*.
+ * Out of scope: fields of differing dims, voxel size or registration; more than two fields; the device list (vr_hip_multi_*); a backdrop
+ * under a fused frame; labels or a 2-D table together with fusion; B in MIP, isosurface, section and depth frames; a shadow cast by B;
+ * volr_bench options and volr::HipRenderer. */
+typedef struct vr_fusion {
+	uint32_t mode;            /* VR_FUSE_SUM or VR_FUSE_OVER */
+	float    weight_a;        /* 0..1: scales what field A contributes to a sample */
+	float    weight_b;        /* 0..1: ... and field B */
+	uint32_t reserved;        /* 0 */
+} vr_fusion;                  /* 16 bytes; per call, not state */
+#define VR_FUSE_SUM  0u
+#define VR_FUSE_OVER 1u
+int vr_hip_set_second_volume(vr_ctx *ctx, const void *host_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);   /* NULL = drop */
+int vr_hip_set_second_volume_device(vr_ctx *ctx, const void *dev_voxels, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t bytes_per_voxel);
+int vr_hip_set_second_transfer_fn(vr_ctx *ctx, const float *tf_premult_rgba, const uint32_t *fused_esl_bits);   /* waits for the context's frames first */
+int vr_hip_render_fused(vr_ctx *ctx, const vr_params *params, const vr_fusion *fusion, uint8_t *host_rgba);
+int vr_hip_render_fused_device(vr_ctx *ctx, const vr_params *params, const vr_fusion *fusion, void *dev_rgba, void *stream);
+int vr_hip_fused_frames(vr_ctx *ctx, uint64_t *frames_out);            /* testing aid: fused frames launched */
+
 /* What the last vr_hip_render* call of this context launched (tuning aid and test hook; no reference counterpart): the volume copy,
  * the lane order / wave shape / tile phase that were chosen (or forced), and the kernel's tile grid. */
 typedef struct vr_launch_info {

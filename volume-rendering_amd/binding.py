@@ -172,6 +172,22 @@ def make_label_entry(colour=(0.0, 0.0, 0.0), mix=0.0, opacity=1.0):
     return e
 
 
+FUSE_MODES = {"sum": 0, "over": 1}      # VR_FUSE_SUM, VR_FUSE_OVER
+
+
+class VrFusion(C.Structure):
+    """vr_fusion: how the two fields of a fused frame meet in a sample — the mode and a weight per field, both in 0..1"""
+    _fields_ = [("mode", C.c_uint32), ("weight_a", C.c_float), ("weight_b", C.c_float), ("reserved", C.c_uint32)]
+
+
+def make_fusion(weight_a=1.0, weight_b=1.0, mode="sum"):
+    """A VrFusion; mode "sum", "over" or the number.  Weights outside 0..1 and unknown numbers are the ABI's to refuse (VR_ERR_INVALID)."""
+    f = VrFusion()
+    f.mode = FUSE_MODES[mode] if isinstance(mode, str) else int(mode)
+    f.weight_a, f.weight_b, f.reserved = float(weight_a), float(weight_b), 0
+    return f
+
+
 class VrVolumeInfo(C.Structure):
     _fields_ = [("dim_x", C.c_uint32), ("dim_y", C.c_uint32), ("dim_z", C.c_uint32), ("bytes_per_voxel", C.c_uint32),
                 ("layout", C.c_uint32), ("brick_copies", C.c_uint32), ("brick_copies_wanted", C.c_uint32), ("brick_planes", C.c_uint32),
@@ -279,6 +295,12 @@ def lib():
         "vr_hip_render_tf2d_device": (C.c_int, [vp, P(VrParams), vp, vp]),
         "vr_hip_tf2d_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_gradient_histogram": (C.c_int, [vp, u32, C.c_float, vp, f32p]),
+        "vr_hip_set_second_volume": (C.c_int, [vp, vp, u32, u32, u32, u32]),
+        "vr_hip_set_second_volume_device": (C.c_int, [vp, vp, u32, u32, u32, u32]),
+        "vr_hip_set_second_transfer_fn": (C.c_int, [vp, vp, vp]),
+        "vr_hip_render_fused": (C.c_int, [vp, P(VrParams), P(VrFusion), vp]),
+        "vr_hip_render_fused_device": (C.c_int, [vp, P(VrParams), P(VrFusion), vp, vp]),
+        "vr_hip_fused_frames": (C.c_int, [vp, P(u64)]),
         "vr_hip_timing": (C.c_int, [vp, P(VrTiming)]),
         "vr_hip_timing_reset": (C.c_int, [vp]),
         "vr_hip_volume_minmax": (C.c_int, [vp, vp, P(u32), f32p, f32p]),

@@ -472,6 +472,23 @@ hipError_t launch_tf2d(const RayKernelArgs &a, const Tf2dArgs &d, const void *li
 hipError_t launch_gradient_histogram(const void *volume, uint32_t bytes_per_voxel, const uint32_t dims[3], uint32_t g_bins, float g_scale,
                                      unsigned long long *hist_dev, const RayKernelArgs *bc, hipStream_t stream);
 
+// ---- fused composite frames (include/vr_hip.h vr_hip_render_fused) ----
+// The second field of one frame, a kernel argument of its own behind the ones a composite frame takes.
+struct FusedArgs {
+	uint64_t vol_b;                    // field B in the order of the array the row reads of field A (filled by launch_fused)
+	float    weight_a, weight_b;       // vr_fusion
+	uint32_t mode;                     // VR_FUSE_SUM / VR_FUSE_OVER, wave-uniform
+	uint32_t skip_mask_b, skip_cmp_b;  // the corner test of B's transfer function (RayKernelArgs::skip_mask / skip_cmp are A's)
+	float    tf_zero_below_b;          // ... and its leading all-zero entries
+};
+// One fused frame.  `a`, `linear` and `bricked` as for launch_labelled (the same rows), the clip, lighting and shadow words likewise; a.p.esl,
+// a.esl_div_* as launch_depth takes them; a.skip_mask / skip_cmp / tf_zero_below are field A's function's.  second_linear: B's linear array
+// (+ the tail slack of the volume's); second_bricked: B's copy in the layout and chunk plane of `bricked`, NULL exactly where `bricked` is.
+// esl_bits: the fused frame's own 1024 words.  fusion.vol_b is the launcher's to fill.
+hipError_t launch_fused(const RayKernelArgs &a, const FusedArgs &fusion, const void *linear, const void *bricked, const void *second_linear,
+                        const void *second_bricked, uint32_t bytes_per_voxel, const float *tf_premult, const uint32_t *esl_bits,
+                        const float *second_tf_premult, void *out_rgba, hipStream_t stream);
+
 // ---- light-source shadows (include/vr_hip.h vr_hip_set_shadow) ----
 // What shadow_build_kernel marches with, besides the volume geometry of RayKernelArgs: one lane per node of the S^3 light grid.
 struct ShadowBuildArgs {

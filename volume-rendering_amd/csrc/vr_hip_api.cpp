@@ -144,6 +144,14 @@ struct vr_ctx {
 	float *tf2d_table = nullptr; uint32_t *tf2d_esl = nullptr;
 	uint32_t tf2d_rows = 0; float tf2d_g_scale = 0.0f, tf2d_zero_below = -1.0f; uint32_t tf2d_g_dependent[4] = { 0, 0, 0, 0 };
 	uint64_t tf2d_frames = 0;
+	// fused frames (vr_hip_set_second_volume, vr_hip_set_second_transfer_fn, vr_hip_render_fused*): field B in the linear order of the
+	// resident volume (+ its tail slack), dropped with it (drop_second); B's copies in the orders a fused frame reads the resident volume in —
+	// the three quad copies and the oct copy —, each built by the first frame that reads it (second_copy_failed: refused, not retried until B
+	// changes); B's transfer function and the fused frame's own ESL words on the device, which survive a volume change; the frames launched
+	void *second = nullptr;
+	void *second_copy[4] = { nullptr, nullptr, nullptr, nullptr }; bool second_copy_failed[4] = { false, false, false, false };
+	float *second_tf = nullptr; uint32_t *fused_esl = nullptr; float second_zero_below = -1.0f;
+	uint64_t fused_frames = 0;
 	unsigned long long *gradient_hist = nullptr;
 #ifdef VR_BOUNDS_CHECK
 	uint32_t *bc_fault = nullptr;           // debug build: first out-of-bounds access of a frame (RayKernelArgs::bc_fault)
@@ -1155,6 +1163,15 @@ void drop_labels(vr_ctx *c) {
 	c->label_bricks_failed = false;
 }
 
+// field B belongs to one volume (its dims and voxel size): nothing of it may be in flight here.  Its function and the fused bits stay.
+void drop_second(vr_ctx *c) {
+	if (c->second) { (void) hipFree(c->second); c->second = nullptr; }
+	for (int k = 0; k < 4; k++) {
+		if (c->second_copy[k]) { (void) hipFree(c->second_copy[k]); c->second_copy[k] = nullptr; }
+		c->second_copy_failed[k] = false;
+	}
+}
+
 int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	if (x == 0 || y == 0 || z == 0 || x > 65535u || y > 65535u || z > 65535u)       // Model::dims is ushort3
 		return fail(c, VR_ERR_INVALID, "volume dims out of range (1..65535)");
@@ -1163,6 +1180,7 @@ int alloc_volume(vr_ctx *c, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
 	if (c->vol) { (void) hipFree(c->vol); c->vol = nullptr; }
 	free_bricks(c);
 	drop_labels(c);                              // vr_hip_set_labels: the labels go with the volume they were set for
+	drop_second(c);                              // vr_hip_set_second_volume: ... and so does field B
 	forget_tile_mappings(c);                     // cached tile mappings belong to the previous volume
 	c->mip_mapped = 0; c->mip_map_next = 0; c->mip_bounds_ready = false;       // ... and so do the block maxima of the MIP frames
 	c->shadow_ready = false;                     // ... and the light grid of a shadow
@@ -1199,9 +1217,10 @@ int build_mip_bounds(vr_ctx *c) {
 // (oct bricks for 2-byte voxels where a DVR frame takes them), the linear array (NULL) under VR_LAYOUT_LINEAR; a copy that is refused falls
 // back to the first quad copy, then to whatever is resident.  plane_force is read as vr_ctx::brick_plane_force is: below 0 = the chunk plane
 // across a view along a volume axis, 0..2 = that plane (and no voxel bricks).  Also what build_shadow reads, for its own params and plane.
-const void *full_march_copy(vr_ctx *c, const vr_params *p, int32_t plane_force, RayKernelArgs &a) {
+// force_linear: the answer under VR_LAYOUT_LINEAR whatever the context's layout is (a fused frame whose second field has no such copy).
+const void *full_march_copy(vr_ctx *c, const vr_params *p, int32_t plane_force, RayKernelArgs &a, bool force_linear = false) {
 	const float half[3] = { a.half_x, a.half_y, a.half_z };
-	const bool bricked = c->layout == VR_LAYOUT_BRICKED, nearest = p->sampling == VR_SAMPLE_NEAREST, forced = plane_force >= 0 && plane_force < (int32_t) kPlanes;
+	const bool bricked = c->layout == VR_LAYOUT_BRICKED && !force_linear, nearest = p->sampling == VR_SAMPLE_NEAREST, forced = plane_force >= 0 && plane_force < (int32_t) kPlanes;
 	a.force_wide = c->force_wide;
 	a.layout = bricked ? kLayoutBricked : kLayoutLinear;
 	a.brick_plane = kPlaneXY;
@@ -1216,7 +1235,7 @@ const void *full_march_copy(vr_ctx *c, const vr_params *p, int32_t plane_force, 
 		}
 		if (copy_possible(c, kCopyQuadXY + plane)) a.brick_plane = plane;
 	}
-	if (takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
+	if (!force_linear && takes_oct_bricks(c, p, half)) a.layout = kLayoutOct;
 	if (a.layout == kLayoutLinear) return nullptr;
 	const void *brick_copy = copy_for(c, copy_kind_of(a, p->sampling));
 	if (brick_copy == nullptr) {                         // refused or not buildable any more: the first quad copy, then whatever is resident
@@ -1230,8 +1249,11 @@ const void *full_march_copy(vr_ctx *c, const vr_params *p, int32_t plane_force, 
 // What a caller of launch_full_march_frame asks for: `what` names the frame in messages; block_maxima: params.esl skips fetches by the
 // volume's block maxima (MIP, isosurface) — without it the frame is planned and cached as the same frame with esl off; leaping: the kernel
 // argument carries the composite's leaping instead (params.esl, the divisor of params.esl_block_dims, the transparent-sample test: depth,
-// labelled); plane: a chunk plane that stands in for the context's forced plane, -1 = as the context says.
-struct FullMarch { const char *what; bool block_maxima, leaping; int32_t plane; };
+// labelled); plane: a chunk plane that stands in for the context's forced plane, -1 = as the context says; second_field: the frame reads the
+// context's second field in the order of the copy it reads of the volume (fused) — where that copy of the field cannot be had
+// (second_copy_for), the frame is planned as a VR_LAYOUT_LINEAR frame: both from their linear arrays.
+struct FullMarch { const char *what; bool block_maxima, leaping; int32_t plane; bool second_field = false; };
+const void *second_copy_for(vr_ctx *c, uint32_t layout, uint32_t plane);
 
 // One frame that marches every ray in full — MIP, isosurface, section, depth, labelled: the copy it reads (full_march_copy), the block maxima
 // where it skips by them, the tile mapping of a DVR frame of the same view, one launch, one event pair.  launch(a, brick_copy, bounds or
@@ -1244,6 +1266,8 @@ int launch_full_march_frame(vr_ctx *c, const vr_params *params, hipStream_t stre
 	RayKernelArgs a;
 	volume_args(c, p, a);
 	const void *brick_copy = full_march_copy(c, p, f.plane >= 0 ? f.plane : c->brick_plane_force, a);
+	if (f.second_field && brick_copy != nullptr && second_copy_for(c, a.layout, a.brick_plane) == nullptr)
+		brick_copy = full_march_copy(c, p, f.plane >= 0 ? f.plane : c->brick_plane_force, a, true);
 	// Skipping and stopping by block maxima.  The grid is the volume's own (vr_hip_volume_minmax), whatever params.esl_block_* say.  Not
 	// for views so far away that fp32 sample coordinates are not exact to a small fraction of a cell (the condition under which DVR
 	// frames clamp every fetch, launch_frame): the TRILINEAR bound covers one voxel around the block of the sample's position.
@@ -1543,6 +1567,69 @@ int launch_tf2d_frame(vr_ctx *c, const vr_params *p, void *dev_rgba, hipStream_t
 	return rc;
 }
 
+// Field B in the order of the copy a fused frame reads the resident volume in — layout kLayoutBricked on chunk plane `plane`, or kLayoutOct —:
+// built from B's linear array by the builder of that copy (launch_brickify, launch_brickify_oct: free functions over a linear array), on the
+// context's stream and synchronous like a brick copy's first use, under build_copy's rule that half of the HBM stays free; kept per kind
+// until B goes.  NULL where it cannot be had: the frame then reads both linear arrays.  Testing aid: VR_SECOND_COPY_REFUSE=1 in the
+// environment refuses every build as the HBM rule would (read at a copy's first use; a refusal holds until B is set again).
+const void *second_copy_for(vr_ctx *c, uint32_t layout, uint32_t plane) {
+	if (c->second == nullptr || (layout != kLayoutBricked && layout != kLayoutOct) || plane >= kPlanes || (layout == kLayoutOct && c->bpv != 2u)) return nullptr;
+	const uint32_t slot = layout == kLayoutOct ? 3u : plane;
+	if (c->second_copy[slot] != nullptr || c->second_copy_failed[slot]) return c->second_copy[slot];
+	const uint64_t bytes = copy_bytes(c, layout == kLayoutOct ? (uint32_t) kCopyOct : kCopyQuadXY + plane);
+	size_t free_b = 0, total_b = 0;
+	void *dst = nullptr;
+	hipError_t e = hipMemGetInfo(&free_b, &total_b);
+	if (e == hipSuccess && (bytes >= free_b || free_b - bytes < total_b / 2)) e = hipErrorOutOfMemory;
+	if (const char *refuse = getenv("VR_SECOND_COPY_REFUSE")) if (atoi(refuse) == 1) e = hipErrorOutOfMemory;
+	if (e == hipSuccess) e = hipMalloc(&dst, bytes);
+	if (e == hipSuccess) e = layout == kLayoutOct ? launch_brickify_oct(c->second, dst, c->dim[0], c->dim[1], c->dim[2], c->stream)
+	                                              : launch_brickify(c->second, dst, c->bpv, plane, c->dim[0], c->dim[1], c->dim[2], c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) { (void) hipGetLastError(); if (dst) (void) hipFree(dst); c->second_copy_failed[slot] = true; return nullptr; }
+	c->second_copy[slot] = dst;
+	return dst;
+}
+
+// what the two fused entry points check beyond render_preamble (include/vr_hip.h, step 13 of the fusion contract)
+int validate_fused(vr_ctx *c, const vr_params *p, const vr_fusion *f) {
+	if (f == nullptr) return fail(c, VR_ERR_INVALID, "fusion is NULL");
+	if (const int rc = need_interpolated(c, p, "a fused frame")) return rc;
+	if (f->mode > VR_FUSE_OVER) return fail(c, VR_ERR_INVALID, "fusion mode must be VR_FUSE_SUM or VR_FUSE_OVER");
+	if (f->reserved != 0u) return fail(c, VR_ERR_INVALID, "fusion reserved must be 0");
+	if (!std::isfinite(f->weight_a) || !std::isfinite(f->weight_b) || f->weight_a < 0.0f || f->weight_a > 1.0f || f->weight_b < 0.0f || f->weight_b > 1.0f)
+		return fail(c, VR_ERR_INVALID, "fusion weights must be finite and in [0, 1]");
+	if (c->preint_on)
+		return fail(c, VR_ERR_INVALID, "pre-integration is set: a fused frame is defined per sample, not per slab (vr_hip_set_preintegration(ctx, 0) switches it off)");
+	if (c->second == nullptr) return fail(c, VR_ERR_NOT_READY, "no second volume is set for the resident volume (vr_hip_set_second_volume)");
+	if (c->second_tf == nullptr) return fail(c, VR_ERR_NOT_READY, "no transfer function is set for the second volume (vr_hip_set_second_transfer_fn)");
+	return VR_OK;
+}
+
+// One fused frame (include/vr_hip.h vr_hip_render_fused): what a tf2d frame of the same view and sampling reads and maps — the context's forced
+// plane is left alone —, with the composite's leaping on the fused frame's own bits in the kernel argument, the lighting and the shadow as
+// launch_frame puts them there, and B's corner test and zero count beside A's.  B is read in the order the frame reads the resident volume
+// in (FullMarch::second_field): where full_march_copy picks a brick copy and B's copy of that kind cannot be had, the frame is planned and
+// launched as a VR_LAYOUT_LINEAR frame instead — both fields from their linear arrays.  volume_args has filled the clip words.
+int launch_fused_frame(vr_ctx *c, const vr_params *p, const vr_fusion *fusion, void *dev_rgba, hipStream_t stream) {
+	if (c->shadow_on) { if (const int rc = build_shadow(c)) return rc; }
+	const FullMarch f = { "fused", false, true, -1, true };
+	const int rc = launch_full_march_frame(c, p, stream, f, [&](RayKernelArgs &a, const void *brick_copy, const uint8_t *) {
+		lighting_shadow_args(c, a);
+		RayKernelArgs b = a;                         // B's corner test from B's own function: the same derivation on a scratch copy
+		transparent_corner_test(c, b, c->second_zero_below);
+		FusedArgs d;
+		memset(&d, 0, sizeof d);
+		d.weight_a = fusion->weight_a; d.weight_b = fusion->weight_b; d.mode = fusion->mode;
+		d.skip_mask_b = b.skip_mask; d.skip_cmp_b = b.skip_cmp; d.tf_zero_below_b = c->second_zero_below;
+		// (the copy is there: launch_full_march_frame planned a linear frame where it is not)
+		return launch_fused(a, d, c->vol, brick_copy, c->second, brick_copy != nullptr ? second_copy_for(c, a.layout, a.brick_plane) : nullptr, c->bpv,
+		                    c->tf, c->fused_esl, c->second_tf, dev_rgba, stream);
+	});
+	if (rc == VR_OK) c->fused_frames++;
+	return rc;
+}
+
 // the depth buffer of the host entry points that hand a depth back (vr_hip_render_iso, vr_hip_render_section): one float per pixel of the
 // window, sized with the window (render_preamble: the frame fits), allocated on first use behind the context's frames
 int size_host_depth(vr_ctx *c) {
@@ -1673,6 +1760,9 @@ void vr_hip_destroy(vr_ctx *c) {
 	if (c->label_table) (void) hipFree(c->label_table);
 	if (c->tf2d_table) (void) hipFree(c->tf2d_table);
 	if (c->tf2d_esl) (void) hipFree(c->tf2d_esl);
+	drop_second(c);
+	if (c->second_tf) (void) hipFree(c->second_tf);
+	if (c->fused_esl) (void) hipFree(c->fused_esl);
 	if (c->gradient_hist) (void) hipFree(c->gradient_hist);
 	if (c->shadow_q) (void) hipFree(c->shadow_q);
 	if (c->hist) (void) hipFree(c->hist);
@@ -2286,6 +2376,77 @@ int vr_hip_render_tf2d(vr_ctx *c, const vr_params *p, uint8_t *host_rgba) {
 }
 
 int vr_hip_tf2d_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::tf2d_frames, frames_out); }
+
+// ---- fused frames (include/vr_hip.h vr_fusion) ----
+
+namespace {
+int set_second_from(vr_ctx *c, const void *src, bool host, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	VR_TRY(c, hipSetDevice(c->device));
+	if (src == nullptr) {                          // drop
+		VR_TRY(c, drain(c));
+		drop_second(c);
+		return VR_OK;
+	}
+	if (c->dim[0] == 0) return fail(c, VR_ERR_NOT_READY, "no volume is resident: a second volume carries the dims and voxel size of the volume it belongs to (vr_hip_set_volume)");
+	if (x != c->dim[0] || y != c->dim[1] || z != c->dim[2]) return fail(c, VR_ERR_INVALID, "the second volume's dims differ from the dims of the resident volume");
+	if (bpv != c->bpv) return fail(c, VR_ERR_INVALID, "the second volume's bytes_per_voxel differ from the resident volume's");
+	VR_TRY(c, drain(c));                         // frames still reading the field we are about to replace
+	const uint64_t elems = (uint64_t) x * y * z, slack = volume_tail_slack(x, y);
+	void *linear = c->second;                    // (same dims and voxel size: the allocation is reused, the copies are not)
+	c->second = nullptr;
+	drop_second(c);
+	c->second = linear;
+	hipError_t e = hipSuccess;
+	if (c->second == nullptr) {
+		if (hipMalloc(&c->second, (elems + slack) * bpv) != hipSuccess) { (void) hipGetLastError(); c->second = nullptr; return fail(c, VR_ERR_ALLOC, "second volume allocation failed"); }
+		e = hipMemsetAsync((uint8_t *) c->second + elems * bpv, 0, slack * bpv, c->stream);
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(c->second, src, elems * bpv, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream);
+	const hipError_t w = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess || w != hipSuccess) {
+		(void) hipGetLastError();
+		drop_second(c);
+		return fail(c, VR_ERR_HIP, "copying the second volume failed", e != hipSuccess ? e : w);
+	}
+	return VR_OK;
+}
+}  // namespace
+
+int vr_hip_set_second_volume(vr_ctx *c, const void *host_voxels, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) { return set_second_from(c, host_voxels, true, x, y, z, bpv); }
+
+int vr_hip_set_second_volume_device(vr_ctx *c, const void *dev_voxels, uint32_t x, uint32_t y, uint32_t z, uint32_t bpv) { return set_second_from(c, dev_voxels, false, x, y, z, bpv); }
+
+int vr_hip_set_second_transfer_fn(vr_ctx *c, const float *tf, const uint32_t *fused_esl_bits) {
+	if (c == nullptr) return VR_ERR_INVALID;
+	if (tf == nullptr) return fail(c, VR_ERR_INVALID, "the second transfer function is NULL");
+	if (fused_esl_bits == nullptr) return fail(c, VR_ERR_INVALID, "fused_esl_bits is NULL: a fused frame leaps by bits of its own (the AND of both fields' bits)");
+	for (uint32_t i = 0; i < VR_TF_SIZE * 4u; i++)
+		if (!std::isfinite(tf[i]) || tf[i] < 0.0f) return fail(c, VR_ERR_INVALID, "members of the second transfer function must be finite and not negative");
+	VR_TRY(c, hipSetDevice(c->device));
+	VR_TRY(c, drain(c));                         // frames still reading the function and the bits we are about to replace
+	if (c->second_tf == nullptr) VR_TRY(c, hipMalloc((void **) &c->second_tf, VR_TF_SIZE * 4 * sizeof(float)));
+	if (c->fused_esl == nullptr) VR_TRY(c, hipMalloc((void **) &c->fused_esl, VR_ESL_VOLUME_SIZE * sizeof(uint32_t)));
+	VR_TRY(c, hipMemcpyAsync(c->second_tf, tf, VR_TF_SIZE * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	VR_TRY(c, hipMemcpyAsync(c->fused_esl, fused_esl_bits, VR_ESL_VOLUME_SIZE * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	VR_TRY(c, hipStreamSynchronize(c->stream));
+	int zero = -1;                               // the leading all-zero entries, as vr_hip_set_transfer_fn counts them
+	while (zero + 1 < VR_TF_SIZE && tf[4 * (zero + 1)] == 0.0f && tf[4 * (zero + 1) + 1] == 0.0f && tf[4 * (zero + 1) + 2] == 0.0f &&
+	       tf[4 * (zero + 1) + 3] == 0.0f)
+		zero++;
+	c->second_zero_below = (float) zero;
+	return VR_OK;
+}
+
+int vr_hip_render_fused_device(vr_ctx *c, const vr_params *p, const vr_fusion *fusion, void *dev_rgba, void *stream) {
+	return render_to_device(c, p, dev_rgba, stream, [&] { return validate_fused(c, p, fusion); }, [&](hipStream_t on) { return launch_fused_frame(c, p, fusion, dev_rgba, on); });
+}
+
+int vr_hip_render_fused(vr_ctx *c, const vr_params *p, const vr_fusion *fusion, uint8_t *host_rgba) {
+	return render_to_host(c, p, host_rgba, nullptr, nullptr, [&] { return validate_fused(c, p, fusion); }, [&](void *) { return launch_fused_frame(c, p, fusion, c->fb, c->stream); });
+}
+
+int vr_hip_fused_frames(vr_ctx *c, uint64_t *frames_out) { return frames_counted(c, &vr_ctx::fused_frames, frames_out); }
 
 #ifdef VR_MIP_STATS
 // probe build only (scripts/mip_probe.py): { samples, fetches issued } of the MIP frames that skipped since the last call
