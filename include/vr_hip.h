@@ -13,7 +13,11 @@
  *     exit(EXIT_FAILURE) policy, cuda_utils.h:21-31, is deliberately NOT reproduced below the ABI);
  *   - one opaque vr_ctx per GPU, no globals (the reference keeps everything in statics, Renderer.h:39-43);
  *   - a context is not thread-safe (neither is the reference);
- *   - there is NO CPU fallback: without a usable HIP device vr_hip_create() fails with VR_ERR_NO_DEVICE.
+ *   - there is NO CPU fallback: without a usable HIP device vr_hip_create() fails with VR_ERR_NO_DEVICE;
+ *   - a frame depends on the context's CURRENT state alone — the last value every setter below was given, and what the text of a setter
+ *     says it drops — never on the calls that led there (tests/test_gpu_session.py).  Where a frame is refused for more than one reason,
+ *     VR_ERR_INVALID (arguments, or a state under which the call can never succeed: the sampling mode, pre-integration) is reported
+ *     before the VR_ERR_NOT_READY of a missing state (labels, the 2-D table, the second field or its function).
  */
 #ifndef VR_HIP_H
 #define VR_HIP_H
@@ -321,7 +325,8 @@ int vr_hip_set_clip(vr_ctx *ctx, const vr_clip *clip);       /* NULL = clipping 
  * their size and layout.
  * Shadow volume.  S^3 bytes q (S = dims), x fastest, built on the context's stream — synchronous, like a brick copy — by the first composite
  * frame, or vr_hip_download_shadow, that finds it missing or stale.  It goes stale on a vr_hip_set_shadow whose struct differs from the
- * current one in more than `strength` (q does not depend on it: a change of the strength alone keeps the grid), on vr_hip_set_volume* / vr_hip_generate_volume, on vr_hip_set_transfer_fn, and on a vr_hip_set_clip that differs from the
+ * current one in more than `strength` (q does not depend on it: a change of the strength alone keeps the grid; after NULL there is no
+ * current one: setting the same shadow again rebuilds), on vr_hip_set_volume* / vr_hip_generate_volume, on vr_hip_set_transfer_fn, and on a vr_hip_set_clip that differs from the
  * current clip.  Per node (i, j, k):
  *  1. Position.  n = fma((float) i, 2.0f / (float) (S - 1), -1.0f) per axis.
  *  2. Light vector.  d = light_pos - n, len2 = fma(d.z, d.z, fma(d.y, d.y, d.x * d.x)).  If !(len2 > 0) then T = 1.  Otherwise
@@ -932,8 +937,10 @@ int vr_hip_download_copy(vr_ctx *ctx, uint32_t kind, void *host_out, uint64_t ca
  * smaller than `brick_copies_wanted` — a speed cliff this call makes visible (axis-aligned views along x / y then read the
  * (x,y) copy).  vr_hip_release_linear_copy frees the linear array once nothing will need it again: afterwards frames read the
  * copies that are resident (no further copy can be built: prepare first), while vr_hip_volume_minmax / _histogram /
- * vr_hip_download_volume / vr_hip_set_layout / vr_hip_prepare return VR_ERR_NOT_READY until the next set_volume, and so does a
- * frame that no resident copy can serve.  Refused (VR_ERR_INVALID) when no brick copy is resident yet, for edges above 2048,
+ * vr_hip_download_volume / vr_hip_set_layout / vr_hip_set_wide_addressing(1) / vr_hip_prepare return VR_ERR_NOT_READY until the next set_volume (vr_hip_prepare: where it
+ * would have to build a copy — naming only copies that are resident, or that the policy does not have, stays VR_OK), and so does a
+ * frame that no resident copy can serve.  A second release is VR_OK.
+ * Refused (VR_ERR_INVALID) when no brick copy is resident yet, for edges above 2048,
  * and while the index-arithmetic path is forced (vr_hip_set_wide_addressing 1). */
 typedef struct vr_volume_info {
 	uint32_t dim_x, dim_y, dim_z, bytes_per_voxel;
