@@ -676,7 +676,8 @@ int vr_hip_labelled_frames(vr_ctx *ctx, uint64_t *frames_out);         /* testin
  *     them; w is rounded in _Q8.
  *  4. Gradient.  Exactly step 1 of the lighting contract: the central differences one texel apart of the interpolated raw value, clamp
  *     addressing, times half_x / y / z; gg = fma(gz, gz, fma(gy, gy, gx * gx)); g = gg > 0 ? gg * rsqrt_nr(gg) : 0.  No sqrtf: CPU and GPU
- *     share every bit.
+ *     share every bit.  The differences span two texels and are not halved: g is TWICE the length of the model-space gradient (on a ramp
+ *     of slope s per voxel along x, g = 2 s half_x), and g_scale is chosen against that g.
  *  5. Row.  tg = fmed3(g * g_scale, 0, rows - 1); j = min((uint32_t) tg, rows - 2); wg = tg - (float) j, full fp32 in both sampling modes
  *     (the shadow factor's precedent).
  *  6. Colour, per channel: c_j = fma(w, T[j][i1] - T[j][i], T[j][i]); c_j1 the same in row j + 1; c = fma(wg, c_j1 - c_j, c_j).  Every

@@ -1,7 +1,9 @@
 """CPU tier of the depth frames (include/vr_hip.h vr_hip_render_depth / vr_hip_pick): depth_render of tests/depth_ref.c — the depths, values and
 alphas the GPU tier expects — is tied to the composite restatements through the alpha byte, its three modes are held to the relations
 the contract implies, the frames of the GPU tier's main test are shown to carry surfaces and rays without one (so that test cannot pass by
-being empty) and to tell four wrong readings of the contract apart, and the depth kernels are held to 8 waves per SIMD."""
+being empty) and to tell four wrong readings of the contract apart, and the depth kernels are held to 8 waves per SIMD.
+A reading this restatement and its kernel SHARE is not visible here: tests/test_f64_model.py holds the restatement, and tests/test_gpu_f64_model.py the
+kernel, to an independent float64 statement of the contract (tests/f64_model.py)."""
 import ctypes as C
 import os
 import re

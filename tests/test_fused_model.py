@@ -1,7 +1,9 @@
 """CPU tier of the fused frames (include/vr_hip.h vr_hip_render_fused): fused_render of tests/fused_ref.c — the bytes the GPU tier expects — is
 tied to the composite restatements through the consequences of the contract, the frames of the GPU tier's main test are shown to hold every
 kind of contribution and to tell six wrong readings of the contract apart, the ABI is held to the header, and the fused kernels are held to
-the registers and the wave count this build reaches."""
+the registers and the wave count this build reaches.
+A reading this restatement and its kernel SHARE is not visible here: tests/test_f64_model.py holds the restatement, and tests/test_gpu_f64_model.py the
+kernel, to an independent float64 statement of the contract (tests/f64_model.py)."""
 import ctypes as C
 import importlib
 import os

@@ -1,7 +1,9 @@
 """CPU tier of the labelled composite frames (include/vr_hip.h vr_hip_render_labelled): label_render of tests/label_ref.c — the bytes the GPU
 tier expects — is tied to the composite restatements through the three consequences of the contract, the frames of the GPU tier's main test
 are shown to reach every kind of table entry and to tell four wrong readings of the contract apart, and the label kernels are held to 8
-waves per SIMD."""
+waves per SIMD.
+A reading this restatement and its kernel SHARE is not visible here: tests/test_f64_model.py holds the restatement, and tests/test_gpu_f64_model.py the
+kernel, to an independent float64 statement of the contract (tests/f64_model.py)."""
 import ctypes as C
 import itertools
 import os

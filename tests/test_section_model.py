@@ -1,7 +1,9 @@
 """CPU tier of the section frames (include/vr_hip.h vr_hip_render_section / vr_hip_render_section_in_volume): section_render of
 tests/section_ref.c — the frames and depths the GPU tier expects — is tied to the clipped MIP restatement and to a numpy restatement of
 the colouring, the frames of the GPU tier's main test are shown to carry sections (so that test cannot pass by being empty) and to tell
-four wrong readings of the contract apart, and the section kernels are held to the registers of their mip_clipped twins."""
+four wrong readings of the contract apart, and the section kernels are held to the registers of their mip_clipped twins.
+A reading this restatement and its kernel SHARE is not visible here: tests/test_f64_model.py holds the restatement, and tests/test_gpu_f64_model.py the
+kernel, to an independent float64 statement of the contract (tests/f64_model.py)."""
 import ctypes as C
 import os
 import re

@@ -1,7 +1,9 @@
 """CPU tier of the 2D transfer-function frames (include/vr_hip.h vr_hip_render_tf2d, vr_hip_gradient_histogram): tf2d_render of
 tests/tf2d_ref.c — the bytes the GPU tier expects — is tied to the composite restatements through the four consequences of the contract, the
 frames of the GPU tier's main test are shown to reach every row pair and both kinds of entry and to tell four wrong readings of the contract
-apart, gradient_histogram_ref is held to an independent numpy statement, and the tf2d kernels are held to 8 waves per SIMD."""
+apart, gradient_histogram_ref is held to an independent numpy statement, and the tf2d kernels are held to 8 waves per SIMD.
+A reading this restatement and its kernel SHARE is not visible here: tests/test_f64_model.py holds the restatement, and tests/test_gpu_f64_model.py the
+kernel, to an independent float64 statement of the contract (tests/f64_model.py)."""
 import ctypes as C
 import importlib
 import os
